@@ -2,6 +2,7 @@
 """Headline benchmark: gate-apps/sec + achieved HBM GB/s on a 28-qubit complex128 register per GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--config cfg2|cfg3|cfg4|cfg5]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 ``python bench.py --gpus N`` with N > 1 and no torchrun environment starts the N ranks itself: before anything
@@ -20,11 +21,19 @@ One *step* = one pass of the configuration's circuit over the register, every ga
   probability checked against sin^2(17 asin 2^(-n/2)).
 
 ``value`` is the whole-job aggregate in 28-qubit gate-app equivalents (amplitude updates / 2^28 per second); the raw
-gate-apps/s on the register is given beside it.  Rank 0 prints ONE JSON line.  ``roofline`` is measured live with HIP
-events around every dense-kernel launch of the timed region; ``cpu_baseline`` is the C/OpenMP restatement (oracle/,
-"port") timed on this host on a bounded prefix of the same circuit (rank 0, N = 1 only), and doubles as a full-size
-parity check of both the per-gate and the fused path.  ``secondary`` (N = 1, cfg2) adds, outside the timed region,
-config 4 and the two other CPU baselines of BASELINE.md section 4.
+gate-apps/s on the register is given beside it.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps and prints the line; everything else is measured or checked only with
+``--full``.  There ``roofline`` is measured live with HIP events around every launch of the timed region;
+``cpu_baseline`` is the C/OpenMP restatement (oracle/, "port") timed on this host on a bounded prefix of the same
+circuit (rank 0, N = 1 only), and doubles as a full-size parity check of both the per-gate and the fused path.
+``secondary`` (N = 1, cfg2) adds, outside the timed region, config 4 and the two other CPU baselines of BASELINE.md
+section 4.  ``--no-cpu-baseline``, ``--no-fusion`` and ``--no-secondary`` leave parts of ``--full`` out.
+
+``--dump-outputs DIR`` writes, after the timed steps, what the last step left in the register (float64 ``.npy``):
+one GPU: ``amplitudes`` (real, imag) and their flat ``amplitude_index`` on 128 windows of 4096 consecutive amplitudes
+at seeded offsets, and ``norm2``; N > 1: ``probabilities`` at 4096 seeded basis indices (``probability_index``,
+reference order) and ``norm2``.  The inputs depend only on the arguments, so two builds compare output for output.
 """
 from __future__ import annotations
 
@@ -51,6 +60,10 @@ HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E spec (MI355X_MICROARCH.md); the copy rat
 NCCL_TIMEOUT_S = 180     # a stalled collective ends the rank with a message instead of running into the driver's limit
 CPU_THREADS = 16         # the GPU box's CPU share for one GPU
 PMC_QUBITS = 28          # register size profiles/pmc_traffic.json was collected on
+DUMP_SEED = 2024         # --dump-outputs: where the sample of the register is taken
+DUMP_WINDOWS, DUMP_WINDOW = 128, 4096      # 2^19 amplitudes = 8 MiB of (real, imag) pairs
+DUMP_POINTS = 4096       # N > 1: basis states whose probability is written
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def self_launch(args) -> int:
@@ -173,9 +186,10 @@ def gate_class_and_regime(op, n):
 
 
 # ---- config 4: the Fock-truncated CV path ---------------------------------------------------------------------------
-def run_cfg4(steps=1, n_modes=6, d=32, gates=60):
+def run_cfg4(steps=1, full=True, dump_dir=None, n_modes=6, d=32, gates=60):
     """6 modes x cutoff 32 (2^30 amplitudes, 16 GiB), 60 gates alternating S(r = 0.1 k mod 0.5) on mode k mod 6 and
-    BS(i, i + 1, pi / 4).  Returns per-gate-class device times from HIP events."""
+    BS(i, i + 1, pi / 4).  With ``full``: per-gate-class device times from HIP events and a full-size
+    spot check, both after the timed passes."""
     from quantum_computations_amd.cv_simulator import fock
 
     st = fock.FockState(n_modes, d)
@@ -205,21 +219,27 @@ def run_cfg4(steps=1, n_modes=6, d=32, gates=60):
         one_pass(None)
     st.reg.sync()
     dt = time.perf_counter() - t0
+    if dump_dir is not None:
+        dump_register(dump_dir, st.reg, d ** n_modes)
+    gbytes = 2 * 16 * d ** n_modes / 1e9
+    out = {"workload": f"{n_modes} modes x Fock cutoff d={d} ({16 * d ** n_modes / 2**30:.0f} GiB), {len(seq)} gates: "
+                       f"S(r) on mode k mod {n_modes} alternating with BS(i, i+1, pi/4) (BASELINE.json configs[3])",
+           "gate_apps_per_sec": steps * len(seq) / dt, "ms_per_step": 1e3 * dt / steps,
+           "algorithmic_bytes_per_gate": gbytes * 1e9}
+    if not full:
+        del st
+        return out
     per = {}
     one_pass(per)                                                   # per-gate device times (events serialise: untimed)
-    gbytes = 2 * 16 * d ** n_modes / 1e9
 
     def cls(kind, pick=lambda i: True):
         t = [x for (k, i), v in per.items() if k == kind and pick(i) for x in v]
         ms = float(np.mean(t))
         return {"avg_ms": ms, "GBps": gbytes / (ms * 1e-3), "frac_of_peak": gbytes / (ms * 1e-3) / HBM_PEAK_GBPS}
-    out = {"workload": f"{n_modes} modes x Fock cutoff d={d} ({16 * d ** n_modes / 2**30:.0f} GiB), {len(seq)} gates: "
-                       f"S(r) on mode k mod {n_modes} alternating with BS(i, i+1, pi/4) (BASELINE.json configs[3])",
-           "gate_apps_per_sec": steps * len(seq) / dt, "ms_per_step": 1e3 * dt / steps,
-           "algorithmic_bytes_per_gate": gbytes * 1e9, "norm2": st.reg.norm2(),
-           "S": cls("S"), "S_on_last_mode": cls("S", lambda i: i == n_modes - 1),
-           "BS": cls("BS"), "BS_interior_pairs": cls("BS", lambda i: i < n_modes - 2),
-           "BS_last_pair": cls("BS", lambda i: i == n_modes - 2)}
+    out.update({"norm2": st.reg.norm2(),
+                "S": cls("S"), "S_on_last_mode": cls("S", lambda i: i == n_modes - 1),
+                "BS": cls("BS"), "BS_interior_pairs": cls("BS", lambda i: i < n_modes - 2),
+                "BS_last_pair": cls("BS", lambda i: i == n_modes - 2)})
     # full-size parity, outside the timed region: one S on every mode and one BS on every pair of the 16 GiB register,
     # sampled fibres / planes against U @ in computed from their own inputs (quantum_computations_amd.cv_simulator.fock)
     spot = fock.spot_check_register(st.reg, np.random.default_rng(32))
@@ -287,6 +307,42 @@ def fail_rank(rank, where, dev, exc):
     os._exit(3)
 
 
+# ---- --dump-outputs -------------------------------------------------------------------------------------------------
+def write_outputs(dirpath, arrays):
+    """``DIR/<name>.npy`` for every array, float64, at most DUMP_LIMIT_BYTES in all."""
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float64) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    out = Path(dirpath)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
+
+
+def dump_register(dirpath, reg, num_amps):
+    """A one-GPU register (DeviceState or QuditState): DUMP_WINDOWS disjoint windows of DUMP_WINDOW consecutive
+    amplitudes at offsets drawn with DUMP_SEED, read back with bounds-checked downloads, and the squared norm."""
+    width = min(DUMP_WINDOW, num_amps)
+    slots = num_amps // width
+    starts = np.sort(np.random.default_rng(DUMP_SEED).choice(slots, size=min(DUMP_WINDOWS, slots), replace=False))
+    starts = starts * width
+    amps = np.concatenate([reg.download(int(s), width) for s in starts])
+    write_outputs(dirpath, {"amplitudes": np.stack([amps.real, amps.imag], axis=1),
+                            "amplitude_index": (starts[:, None] + np.arange(width)).ravel(),
+                            "norm2": [reg.norm2()]})
+
+
+def dump_sharded(dirpath, dev, n, rank):
+    """A sharded register (every rank takes part): probabilities at DUMP_POINTS basis indices in reference order,
+    drawn with DUMP_SEED, whatever the layout of the shards; rank 0 writes them."""
+    index = np.sort(np.random.default_rng(DUMP_SEED).choice(1 << n, size=min(DUMP_POINTS, 1 << n), replace=False))
+    probs = dev.probabilities(index.tolist())
+    norm2 = dev.norm2()
+    if rank == 0:
+        write_outputs(dirpath, {"probabilities": probs, "probability_index": index, "norm2": [norm2]})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -294,9 +350,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
     ap.add_argument("--config", choices=("cfg2", "cfg3", "cfg4", "cfg5"), default="cfg2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fusion", action="store_true", help="skip the informational fused-circuit measurement")
-    ap.add_argument("--no-secondary", action="store_true", help="skip config 4 and the extra CPU baselines (N = 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: per-kernel times and roofline, "
+                         "CPU baselines with full-size parity, fused circuits, secondary configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write a seeded sample of the final register as DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-fusion", action="store_true", help="--full without the informational fused-circuit measurement")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="--full without config 4 and the extra CPU baselines (N = 1)")
     ap.add_argument("--qubits-per-gpu", type=int, default=0, help="weak scaling: register qubits per GPU")
     ap.add_argument("--rehearse", action="store_true",
                     help="development aid: no GPU -- ranks rendezvous over gloo and only compute the exchange schedule")
@@ -429,15 +490,8 @@ def main():
         passes[0] += 1
         return slot[0]
 
-    # which kernel each gate of the circuit lands in (asked of the library, not guessed)
-    kernels = []
-    if world == 1:
-        for gate in gates:
-            gate.apply(dev)
-            kernels.append(dev.last_kernel())
-        passes[0] += 1
-    # the event ring holds 16384 marks
-    recorded_steps = min(args.steps, 16000 // (2 * len(gates)))
+    # --full: HIP events around every launch of the timed steps (the event ring holds 16384 marks)
+    recorded_steps = min(args.steps, 16000 // (2 * len(gates))) if args.full else 0
     try:
         for _ in range(args.warmup):
             step(False)
@@ -457,10 +511,27 @@ def main():
             raise
         fail_rank(rank, f"pass {passes[0] + 1} of the {args.config} circuit", dev, exc)
 
+    if args.dump_outputs:                        # before anything below touches the register
+        if world == 1:
+            dump_register(args.dump_outputs, dev, dev.num_amps)
+        else:
+            try:
+                dump_sharded(args.dump_outputs, dev, n, rank)
+            except Exception as exc:
+                fail_rank(rank, "--dump-outputs read-out", dev, exc)
+
+    # which kernel each gate of the circuit lands in (asked of the library, not guessed; one more untimed pass)
+    kernels = []
+    if world == 1 and args.full:
+        for gate in gates:
+            gate.apply(dev)
+            kernels.append(dev.last_kernel())
+        passes[0] += 1
+
     # The CPU leg and the full-size parity check run AFTER the timed region: 12 s of 16 OpenMP threads, 4 GiB host
     # arrays and their release in front of it left one launch in a few runs 18 ms long (whole-job value 892-908 instead
     # of 920: the default run differed from the same run with --no-cpu-baseline in nothing else).
-    if args.config == "cfg2" and world == 1 and not args.no_cpu_baseline:
+    if args.config == "cfg2" and world == 1 and args.full and not args.no_cpu_baseline:
         dev.fill_random(STATE_SEED)             # back to the initial state: the CPU leg downloads it
         cpu, cpu_gates, cpu_ket = cpu_baseline(ops, dev, n)
         # parity at full size: run the same prefix on the GPU from the same initial state and compare every amplitude
@@ -469,13 +540,13 @@ def main():
         parity_err = float(np.max(np.abs(dev.to_numpy() - cpu_ket)))
 
     extra = {}
-    if args.config == "cfg5":                    # all ranks take part in the read-out
+    if args.full and args.config == "cfg5":      # all ranks take part in the read-out
         total_iterations = passes[0] * iterations
         p = float(dev.probabilities([marked])[0])
         want = W.grover_success_probability(n, total_iterations)
         extra["grover"] = {"iterations_applied": total_iterations, "success_probability": p, "analytic": want,
                            "rel_err": abs(p - want) / want, "norm2": dev.norm2()}
-    elif world > 1:
+    elif args.full and world > 1:
         extra["norm2"] = dev.norm2()
 
     if rank != 0:
@@ -587,7 +658,7 @@ def main():
     if cpu is not None:
         result["cpu_baseline"] = cpu
         result["parity_max_abs_err_vs_cpu_at_full_size"] = parity_err
-    if args.config == "cfg2" and world == 1 and not args.no_fusion:
+    if args.config == "cfg2" and world == 1 and args.full and not args.no_fusion:
         # Informational, outside the timed region and NOT part of `value`: the same circuit through the gate-fusion
         # scheduler of Simulator(fuse=k) (quantum_computations_amd/fusion.py) -- fewer, denser launches.
         from quantum_computations_amd.fusion import fuse_circuit, fusion_stats
@@ -614,7 +685,7 @@ def main():
                     gate.apply(dev)
                 result["with_gate_fusion"][f"max_{k}_qubits"]["parity_max_abs_err_vs_cpu_at_full_size"] = \
                     float(np.max(np.abs(dev.to_numpy() - cpu_ket)))
-    if args.config == "cfg2" and world == 1 and not args.no_secondary:
+    if args.config == "cfg2" and world == 1 and args.full and not args.no_secondary:
         dev.close()
         del cpu_ket
         secondary = {"cfg4": run_cfg4(), "cfg5_single_gpu": run_cfg5_single_gpu()}
@@ -633,20 +704,22 @@ def main_cfg4(args):
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: the gate path has no CPU fallback")
-    r = run_cfg4(steps=max(1, args.steps))
+    steps = max(1, args.steps)
+    r = run_cfg4(steps=steps, full=args.full, dump_dir=args.dump_outputs)
     gb = r["algorithmic_bytes_per_gate"]
     result = {
         "metric": "gate_apps_per_sec", "value": r["gate_apps_per_sec"] * gb / (2 * 16 * 2.0 ** 28),
-        "unit": "gate-apps/s", "n_gpus": 1, "steps": args.steps, "warmup": 1, "ms_per_step": r["ms_per_step"],
+        "unit": "gate-apps/s", "n_gpus": 1, "steps": steps, "warmup": 1, "ms_per_step": r["ms_per_step"],
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
         "config": {"workload": r["workload"], "name": "cfg4",
                    "unit_note": "value = mode-gate-apps/s x (32 GiB / 8 GiB): 28-qubit gate-app equivalents"},
         "gate_apps_per_sec_on_register": r["gate_apps_per_sec"],
-        "roofline": {"bound": "hbm", "achieved": r["BS"]["GBps"], "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": r["BS"]["frac_of_peak"], "traffic": None, "kernel": "k_mode2_blocks (all pairs)",
-                     "algorithmic_bytes_per_launch": gb, "avg_launch_ms": r["BS"]["avg_ms"]},
-        "detail": r,
     }
+    if args.full:
+        result["roofline"] = {"bound": "hbm", "achieved": r["BS"]["GBps"], "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                              "frac": r["BS"]["frac_of_peak"], "traffic": None, "kernel": "k_mode2_blocks (all pairs)",
+                              "algorithmic_bytes_per_launch": gb, "avg_launch_ms": r["BS"]["avg_ms"]}
+        result["detail"] = r
     print(json.dumps(result), flush=True)
 
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Secondary BASELINE.json configurations that fit one MI355X, plus the host<->device transfer rates.
-(Round 2: ``bench.py --config cfg3|cfg4|cfg5`` and the ``secondary`` block of the default bench line cover the same
+(Round 2: ``bench.py --config cfg3|cfg4|cfg5`` and the ``secondary`` block of the ``--full`` bench line cover the same
 configurations in the driver-visible line; this script stays as the longer stand-alone form.)
 
     python tools/bench_configs.py [--out gpurun_out/configs.json] [--grover-n 30] [--skip-cv]

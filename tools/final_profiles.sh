@@ -7,25 +7,25 @@ O=$R/gpurun_out/final
 PART=${1:-all}
 mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-B="$R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fusion --no-secondary"
+B="$R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-fusion --no-secondary"
 if [ "$PART" = bench ] || [ "$PART" = all ]; then
-python3 $R/bench.py > $O/bench.json 2> $O/bench.err
+python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err
 echo "bench done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-fusion --no-secondary > $O/prof_stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -- python3 $R/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-fusion --no-secondary > $O/prof_stats.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/prof_fetch -- python3 $B > $O/prof_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/prof_write -- python3 $B > $O/prof_write.log 2>&1
 echo "bench profiles done"
-python3 $R/bench.py --config cfg4 --steps 3 --warmup 1 > $O/cfg4.json 2> $O/cfg4.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/cfg4_stats -- python3 $R/bench.py --config cfg4 --steps 1 --warmup 1 > $O/cfg4_stats.log 2>&1
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/cfg4_fetch -- python3 $R/bench.py --config cfg4 --steps 1 --warmup 0 > $O/cfg4_fetch.log 2>&1
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/cfg4_write -- python3 $R/bench.py --config cfg4 --steps 1 --warmup 0 > $O/cfg4_write.log 2>&1
+python3 $R/bench.py --full --config cfg4 --steps 3 --warmup 1 > $O/cfg4.json 2> $O/cfg4.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/cfg4_stats -- python3 $R/bench.py --full --config cfg4 --steps 1 --warmup 1 > $O/cfg4_stats.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/cfg4_fetch -- python3 $R/bench.py --full --config cfg4 --steps 1 --warmup 0 > $O/cfg4_fetch.log 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/cfg4_write -- python3 $R/bench.py --full --config cfg4 --steps 1 --warmup 0 > $O/cfg4_write.log 2>&1
 echo "cfg4 profiles done"
-python3 $R/bench.py --config cfg5 --qubits-per-gpu 30 --steps 1 --warmup 1 > $O/cfg5_n30.json 2> $O/cfg5_n30.err
+python3 $R/bench.py --full --config cfg5 --qubits-per-gpu 30 --steps 1 --warmup 1 > $O/cfg5_n30.json 2> $O/cfg5_n30.err
 # the N > 1 code path on this one GPU (ranks share GPU 0, send / recv staged through the host: timings meaningless)
 cd $R
-QSV_BENCH_ONE_GPU=1 python3 bench.py --gpus 4 --scaling strong --steps 2 --warmup 1 > $O/rehearsal_strong4.json 2> $O/rehearsal_strong4.err
-QSV_BENCH_ONE_GPU=1 python3 bench.py --gpus 2 --config cfg5 --qubits-per-gpu 24 --steps 2 --warmup 1 > $O/rehearsal_cfg5.json 2> $O/rehearsal_cfg5.err
-QSV_BENCH_ONE_GPU=1 python3 bench.py --gpus 4 --config cfg3 --qubits-per-gpu 26 --steps 2 --warmup 1 > $O/rehearsal_cfg3.json 2> $O/rehearsal_cfg3.err
+QSV_BENCH_ONE_GPU=1 python3 bench.py --full --gpus 4 --scaling strong --steps 2 --warmup 1 > $O/rehearsal_strong4.json 2> $O/rehearsal_strong4.err
+QSV_BENCH_ONE_GPU=1 python3 bench.py --full --gpus 2 --config cfg5 --qubits-per-gpu 24 --steps 2 --warmup 1 > $O/rehearsal_cfg5.json 2> $O/rehearsal_cfg5.err
+QSV_BENCH_ONE_GPU=1 python3 bench.py --full --gpus 4 --config cfg3 --qubits-per-gpu 26 --steps 2 --warmup 1 > $O/rehearsal_cfg3.json 2> $O/rehearsal_cfg3.err
 cd /tmp
 echo "rehearsals done"
 fi

@@ -52,7 +52,7 @@ def main():
     ap.add_argument("--stats", type=Path)
     ap.add_argument("--fetch", type=Path)
     ap.add_argument("--write", type=Path)
-    ap.add_argument("--command", default="python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline")
+    ap.add_argument("--command", default="python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline")
     ap.add_argument("--name", default="pmc_traffic", help="profiles/rNN_<name>.md (pmc_traffic.json only for the default)")
     ap.add_argument("--alg-bytes", type=float, default=0.0, help="algorithmic bytes per launch, for a ratio column")
     args = ap.parse_args()

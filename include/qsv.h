@@ -308,6 +308,20 @@ int qsv_tensor_outer(int device, void *hip_stream, const void *dev_p, const void
  * density matrix once both environments are contracted into z (mps.py:188-189). */
 int qsv_tensor_axis_overlap(int device, void *hip_stream, const void *dev_z, const void *dev_t, uint64_t L, uint64_t d,
                             uint64_t R, void *dev_out);
+/* rho[i, j] = sum_{l, r} z[l, i, r] conj(t[l, j, r]) as a (d x d) device matrix: the whole reduced density matrix of a
+ * site once both environments are contracted into z (partial_density_mps, mps.py:176-190, without the host einsum).
+ * Synchronises `hip_stream` before it returns (the re-layout uses the decomposition pool). */
+int qsv_tensor_axis_density(int device, void *hip_stream, const void *dev_z, const void *dev_t, uint64_t L, uint64_t d,
+                            uint64_t R, void *dev_out);
+/* Wigner functions of `batch` density matrices rho_b (batch x d x d, contiguous, device) sampled on x_k = x0 + k dx (hbar = 1):
+ * W_b(q, p) = (1/pi) int rho_b(q - y, q + y) e^{2ipy} dy by the grid quadrature over x_k, the off-grid argument
+ * sinc-interpolated (the Wigner function utils.wigner of the reference leaves unimplemented, cv_simulator/utils.py:6-7).
+ * `q` (nq) and `p` (np) are HOST arrays; dev_w receives W as (batch x np x nq) doubles, row-major.  Nothing is
+ * renormalised (the integral of W is dx Tr rho) unless `normalised` != 0, which divides by dx Tr rho_b.  QSV_EINVAL for
+ * d < 2, batch < 1, nq < 1, np < 1, dx not positive and finite, any q or p not finite, or |p| > pi / (2 dx), past which
+ * the quadrature aliases; every check runs before the first HIP call.  Synchronises `hip_stream` before it returns. */
+int qsv_tensor_wigner(int device, void *hip_stream, const void *dev_rho, int batch, uint64_t d, double x0, double dx,
+                      const double *q, uint64_t nq, const double *p, uint64_t np, int normalised, void *dev_w);
 
 /* ---- whole circuits in one launch (registers of at most 13 qubits) ------------------------------------------------
  * Replaces the caller loop itself -- `for gate in self.circuit: ... gate.apply(state)` with its measurement record and

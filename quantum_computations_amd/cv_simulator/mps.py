@@ -179,6 +179,34 @@ class MPS:
         psi = np.moveaxis(self.contract(), axis, 0).reshape(len(self.domain), -1)
         return (psi @ psi.conj().T) * self.diff ** (len(self) - 1)
 
+    def wigner(self, mode, q, p, *, normalised: bool = False) -> np.ndarray:
+        """Wigner function of the reduced state of ``mode`` on the window ``q x p`` (hbar = 1), shape ``(len(p), len(q))``
+        -- the orientation of ``contourf(*np.meshgrid(q, p), W)``.  A sequence of modes gives ``(len(modes), len(p),
+        len(q))`` from one batched launch.  The density matrices carry the grid measure ``diff^(m-1)`` of
+        :meth:`partial_density_mps`, so the integral of ``W`` is ``norm()**2`` unless ``normalised`` divides by it.
+
+        ``layout="sites"``: the reduced density matrices are contracted on the device
+        (``SiteRegister.reduced_density_device``) and never leave it.  ``layout="dense"``: they are built on the host by
+        :meth:`partial_density_mps` and uploaded."""
+        from .utils import wigner_device
+        modes = [mode] if np.ndim(mode) == 0 else list(mode)
+        for axis in modes:
+            if int(axis) != axis or axis < 0 or axis >= len(self):
+                raise IndexError(f"mode={axis} out of bounds")
+        modes = [int(axis) for axis in modes]
+        if self.layout == "sites":
+            rho = self.reg.reduced_density_device(modes)
+            w = wigner_device(rho, self.domain, q, p, normalised=normalised)
+            if not normalised:
+                w *= self.diff ** (len(self) - 1)
+        else:
+            from .site_register import _torch
+            torch = _torch()
+            host = np.stack([self.partial_density_mps(axis) for axis in modes])
+            rho = torch.from_numpy(np.ascontiguousarray(host, dtype=np.complex128)).to(torch.device("cuda", int(self.reg.device)))
+            w = wigner_device(rho, self.domain, q, p, normalised=normalised)
+        return w if np.ndim(mode) else w[0]
+
     @staticmethod
     def fidelity(a: "MPS", b: "MPS") -> float:
         """``|<a|b>|^2`` on a shared grid.  (The reference's version, mps.py:192-201, contracts ``a`` with itself

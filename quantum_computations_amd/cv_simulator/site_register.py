@@ -209,6 +209,20 @@ class SiteRegister:
         host_t = t.cpu().numpy()
         return np.einsum("bid,bjd -> ij", z.cpu().numpy().reshape(host_t.shape), np.conj(host_t), optimize=True)
 
+    def reduced_density_device(self, axes) -> "torch.Tensor":
+        """Reduced density matrices of the sites ``axes`` as one device tensor ``(len(axes), d, d)`` (no grid-measure
+        factors): :meth:`reduced_density` with the last contraction on the GPU too (``qsv_tensor_axis_density``: the
+        physical index moved to the front of the dressed site and of its conjugate, then one GEMM), so no site tensor
+        leaves the device."""
+        axes = [int(a) for a in axes]
+        out = self._empty(len(axes), self.d, self.d)
+        for slot, axis in enumerate(axes):
+            z, t = self._dressed_site(axis)
+            cl, d, cr = (int(x) for x in t.shape)
+            _lib.call("qsv_tensor_axis_density", self.device, self._stream(), self._p(z), self._p(t), cl, d, cr,
+                      self._p(out[slot]))
+        return out
+
     # ---- gates ------------------------------------------------------------------------------------------------
     def apply_mode(self, operator: np.ndarray, mode: int) -> None:
         t = self.sites[mode]

@@ -7,6 +7,7 @@ array-in/array-out functions are kept for API compatibility and small host array
 """
 from __future__ import annotations
 
+import ctypes as C
 import logging
 
 import numpy as np
@@ -110,5 +111,72 @@ def plane_resample_table(qs: np.ndarray, x_new: np.ndarray, y_new: np.ndarray):
     return cols, vals.astype(np.complex128)
 
 
-def wigner(state, q, p):
-    raise NotImplementedError("Evaluation of Wigner function not yet implemented")
+# ---- Wigner function (the reference leaves utils.py:6-7 unimplemented) ----------------------------------------
+def _window(values, name: str) -> np.ndarray:
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    if values.ndim != 1 or values.size == 0:
+        raise ValueError(f"{name} must be a non-empty 1-D array")
+    return values
+
+
+def wigner_device(rho, domain: np.ndarray, q, p, *, normalised: bool = False) -> np.ndarray:
+    """``W_b[p, q] = (1/pi) int rho_b(q - y, q + y) e^{2ipy} dy`` (hbar = 1) for a device tensor ``rho`` of shape
+    ``(B, d, d)`` sampled on ``domain``, evaluated by ``qsv_tensor_wigner`` in one batched launch; returns the host
+    array ``(B, len(p), len(q))``.  Nothing is renormalised (the integral of ``W_b`` is ``dx Tr rho_b``) unless
+    ``normalised``.  ``ValueError`` for ``|p| > pi / (2 dx)``, where the grid quadrature aliases."""
+    from .. import _lib
+    from .site_register import _torch
+
+    torch = _torch()
+    q, p = _window(q, "q"), _window(p, "p")
+    if rho.dim() != 3 or rho.shape[1] != rho.shape[2] or rho.shape[1] != len(domain):
+        raise ValueError("rho must be (B, d, d) with d = len(domain)")
+    batch, d = int(rho.shape[0]), int(rho.shape[1])
+    rho = rho.to(torch.complex128).contiguous()
+    device = rho.device
+    out = torch.empty((batch, len(p), len(q)), dtype=torch.float64, device=device)
+    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    dbl = C.POINTER(C.c_double)
+    _lib.call("qsv_tensor_wigner", device.index, stream, C.c_void_p(rho.data_ptr()), batch, d, float(domain[0]),
+              float(_spacing(domain)), q.ctypes.data_as(dbl), len(q), p.ctypes.data_as(dbl), len(p), int(bool(normalised)),
+              C.c_void_p(out.data_ptr()))
+    return out.cpu().numpy()
+
+
+def wigner(state, q, p, *, domain: np.ndarray = None, mode: int = 0, normalised: bool = False, device: int = 0):
+    """Wigner function of one mode on the window ``q x p``: returns ``(Q, P, W)`` with ``Q, P = np.meshgrid(q, p)`` and
+    ``W`` of the same shape, ready for ``contourf(Q, P, W)``.
+
+    ``state`` is an ``MPS`` (``mode`` picks the mode; see ``MPS.wigner``), a 1-D ket or a 2-D density matrix sampled on
+    ``domain``.  Without ``domain`` an array is read as the reference's signature ``wigner(state, q, p)``: ``q`` is then
+    its grid too and ``len(state)`` must equal ``len(q)``.  hbar = 1, momentum as in :func:`CFT`; ``normalised`` divides
+    by the integral of ``W`` (``dx Tr rho``)."""
+    from .mps import MPS
+
+    q, p = _window(q, "q"), _window(p, "p")
+    Q, P = np.meshgrid(q, p)
+    if isinstance(state, MPS):
+        return Q, P, state.wigner(mode, q, p, normalised=normalised)
+    state = np.asarray(state)
+    if domain is None:
+        if state.ndim not in (1, 2) or state.shape[0] != len(q):
+            raise ValueError("without a domain, q is the state's grid: len(state) must equal len(q)")
+        domain = q
+    domain = np.asarray(domain, dtype=np.float64)
+    d = len(domain)
+    if state.ndim == 1:
+        if state.shape[0] != d:
+            raise ValueError(f"a ket of {state.shape[0]} samples on a grid of {d} points")
+        rho = np.outer(state, np.conj(state))
+    elif state.ndim == 2:
+        if state.shape[0] != state.shape[1]:
+            raise ValueError(f"a density matrix must be square, got {state.shape}")
+        if state.shape[0] != d:
+            raise ValueError(f"a density matrix of {state.shape[0]} samples on a grid of {d} points")
+        rho = state
+    else:
+        raise ValueError("state must be an MPS, a 1-D ket or a 2-D density matrix")
+    from .site_register import _torch
+    torch = _torch()
+    dev_rho = torch.from_numpy(np.ascontiguousarray(rho, dtype=np.complex128)[None]).to(torch.device("cuda", int(device)))
+    return Q, P, wigner_device(dev_rho, domain, q, p, normalised=normalised)[0]

@@ -76,14 +76,38 @@ enum {
                                 per 32 amplitudes (256 per one-qubit gate, 512 per two-qubit gate; the dense block costs
                                 4096).  Longer sequences report handled = 0.  -1 (default) = $QSV_SEQUENCE_WORK or 0, 0 = never: the
                                 sequence form measured no faster than the dense block; kept for measurements */
-    QSV_OPT_TILE_SEQUENCE_GATES = 12 /* qsv_apply_sequence: blocks made of at most this many 1- and 2-qubit gates are
+    QSV_OPT_TILE_SEQUENCE_GATES = 12, /* qsv_apply_sequence: blocks made of at most this many 1- and 2-qubit gates are
                                 applied as that gate list on LDS-resident tiles (k_seq_tile) instead of their dense
                                 product.  -1 (default) = 6-qubit blocks of at most 12 gates ($QSV_TILE_SEQUENCE_GATES);
                                 an explicit value also admits 5-qubit blocks (slower than their dense product: for
                                 measurements); 0 = never */
+    QSV_OPT_DEFER = 13      /* deferred 1- and 2-qubit gates (see "deferred gates" below): 0 = off, every qsv_apply_* call
+                               launches its own kernel; 1 = auto, on registers made by qsv_create of at least 2^22
+                               amplitudes; 2 = always (registers made by qsv_create of at least 12 qubits); -1 (default)
+                               = $QSV_DEFER or 1.  Same results bit for bit; only the number of passes over HBM changes */
 };
 
 typedef struct qsv_state qsv_state;
+
+/* ---- deferred gates ------------------------------------------------------------------------
+ * On a register the library allocated (qsv_create) with QSV_OPT_DEFER on, qsv_apply_1q / _2q / _diag_1q / _diag_2q / _cx
+ * / _swap / _controlled_1q check their arguments, classify the gate and QUEUE it instead of launching a kernel.  The queue
+ * is applied in passes: each pass brings every 4096-amplitude tile of the register into LDS once and applies an ordered
+ * list of queued gates to it (k_pass_tile), each with the arithmetic of its own per-gate kernel, so the amplitudes are
+ * bit for bit those of the per-gate path.  Gates keep call order, except that CX, CZ, SWAP (any gate whose matrix holds
+ * only 0 and +-1) may move ahead of earlier gates on other qubits -- that changes no bit either.
+ *  - A rejected call (QSV_EINVAL, ...) returns at once and leaves the queue as it was.
+ *  - Every other entry point that takes the register flushes the queue first: sync, download, upload, copy (both
+ *    registers), fill_random, scale, set_basis, norm2, inner, expect_*, probabilities, reduced_density, sample,
+ *    measure*, collapse, insert, permute, apply_kq, apply_mcphase, apply_sequence, set_stream, set_option, device_ptr,
+ *    timer_*, event_*, last_kernel, and qsv_flush itself.  qsv_destroy drops what is pending.
+ *  - A launch error during a flush is returned by the call that flushed; the rest of the queue is dropped.
+ *  - Views (qsv_create_view, qsv_rebind_view) never defer, nor does a register once qsv_device_ptr has handed out its
+ *    address (the caller may then touch the amplitudes directly): that call flushes and switches deferral off for good.
+ *  - Passes are launched while gates are still being queued (once 64 are pending), so the GPU is not idle meanwhile. */
+int qsv_flush(qsv_state *st);
+/* Gates that went through the queue, and the launches that applied them (passes plus gates run on their own). */
+int qsv_defer_stats(const qsv_state *st, uint64_t *gates_queued, uint64_t *launches);
 
 /* ---- library ---------------------------------------------------------------------------- */
 int qsv_version(void);

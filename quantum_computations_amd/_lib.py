@@ -11,7 +11,7 @@ LIB_PATH = Path(os.environ.get("QSV_LIBRARY", PKG_DIR / "libqsv.so"))
 QSV_OK, QSV_EINVAL, QSV_ENOMEM, QSV_EHIP, QSV_ESTATE = 0, -1, -2, -3, -4
 OPT_SPECIALIZE, OPT_UNROLL, OPT_GRID_CAP, OPT_NONTEMPORAL, OPT_ITEM_STRIDE_BIT, OPT_TILE_REGIONS = 1, 2, 3, 4, 5, 6
 OPT_KQ_VARIANT, OPT_PLANE_KERNEL, OPT_READOUT_VARIANT, OPT_COMPLEX_PRODUCT, OPT_SEQUENCE_WORK = 7, 8, 9, 10, 11
-OPT_TILE_SEQUENCE_GATES = 12
+OPT_TILE_SEQUENCE_GATES, OPT_DEFER = 12, 13
 
 RANK_NEEDS_OMEGA = (1 << 64) - 1     # qsv_tensor_rsvd_split without a test matrix: call again with one
 
@@ -34,6 +34,8 @@ SIGNATURES: dict[str, list] = {
     "qsv_num_amps": [_state_p, _u64_p],
     "qsv_device_ptr": [_state_p, C.POINTER(C.c_void_p)],
     "qsv_sync": [_state_p],
+    "qsv_flush": [_state_p],
+    "qsv_defer_stats": [_state_p, _u64_p, _u64_p],
     "qsv_set_basis": [_state_p, C.c_uint64],
     "qsv_upload": [_state_p, C.c_void_p, C.c_uint64, C.c_uint64],
     "qsv_download": [_state_p, C.c_void_p, C.c_uint64, C.c_uint64],

@@ -2,6 +2,7 @@
 // The device work lives in qsv_kernels.hip (qubits) and qsv_qudit.hip (d-level modes).
 
 #include "qsv_internal.h"
+#include "qsv_plan.h"
 
 #include <sys/mman.h>
 
@@ -115,45 +116,85 @@ bool matrix_equals(int D, const double *m, const double *ref_real) {
 // the matrix and the gate runs at full traffic.
 constexpr int QSV_MIN_CTRL_BIT = 3;
 
-// 1-qubit diagonal with the traffic-saving special cases: d0 == 1 touches only the bit = 1 half.
-int diag_1q_bits(qsv_state *st, int bit, const double d[4]) {
-    if (st->specialize && is_one(d[0], d[1])) {
-        if (is_one(d[2], d[3])) return QSV_OK;  // identity
-        if (bit >= QSV_MIN_CTRL_BIT) return qsvk_phase(st, 1, &bit, d[2], d[3]);
-    }
-    return qsvk_diag(st, 1, &bit, 0, nullptr, d);
+constexpr int OP_NONE = -1;   // the gate is the identity: nothing to launch
+
+QsvOp dense_op(int k, const int *bits, int nctrl, const int *cbits, const double *m) {
+    QsvOp op;
+    op.kind = QSV_OP_DENSE;
+    op.k = k;
+    for (int j = 0; j < k; ++j) op.bits[j] = bits[j];
+    op.nctrl = nctrl;
+    for (int i = 0; i < nctrl; ++i) op.cbits[i] = cbits[i];
+    std::memcpy(op.m, m, sizeof(double) * (2u << (2 * k)));
+    return op;
 }
 
-int diag_2q_bits(qsv_state *st, int b0, int b1, const double d[8]) {
+QsvOp diag_op(int k, const int *bits, int nctrl, const int *cbits, const double *d) {
+    QsvOp op;
+    op.kind = QSV_OP_DIAG;
+    op.k = k;
+    for (int j = 0; j < k; ++j) op.bits[j] = bits[j];
+    op.nctrl = nctrl;
+    for (int i = 0; i < nctrl; ++i) op.cbits[i] = cbits[i];
+    std::memcpy(op.m, d, sizeof(double) * (2u << k));
+    return op;
+}
+
+QsvOp phase_op(int nctrl, const int *cbits, double re, double im) {
+    QsvOp op;
+    op.kind = QSV_OP_PHASE;
+    op.nctrl = nctrl;
+    for (int i = 0; i < nctrl; ++i) op.cbits[i] = cbits[i];
+    op.m[0] = re;
+    op.m[1] = im;
+    return op;
+}
+
+QsvOp none_op() {
+    QsvOp op;
+    op.kind = OP_NONE;
+    return op;
+}
+
+// 1-qubit diagonal with the traffic-saving special cases: d0 == 1 touches only the bit = 1 half.
+QsvOp diag_1q_bits(qsv_state *st, int bit, const double d[4]) {
+    if (st->specialize && is_one(d[0], d[1])) {
+        if (is_one(d[2], d[3])) return none_op();  // identity
+        if (bit >= QSV_MIN_CTRL_BIT) return phase_op(1, &bit, d[2], d[3]);
+    }
+    return diag_op(1, &bit, 0, nullptr, d);
+}
+
+QsvOp diag_2q_bits(qsv_state *st, int b0, int b1, const double d[8]) {
     if (st->specialize) {
         const bool one0 = is_one(d[0], d[1]), one1 = is_one(d[2], d[3]), one2 = is_one(d[4], d[5]);
         const bool c0 = b0 >= QSV_MIN_CTRL_BIT, c1 = b1 >= QSV_MIN_CTRL_BIT;
         if (one0 && one1 && one2) {  // controlled phase: CZ touches a quarter of the register
-            if (is_one(d[6], d[7])) return QSV_OK;
+            if (is_one(d[6], d[7])) return none_op();
             const double dd[4] = {1.0, 0.0, d[6], d[7]};
             if (c0 && c1) {
                 const int both[2] = {b0, b1};
-                return qsvk_phase(st, 2, both, d[6], d[7]);
+                return phase_op(2, both, d[6], d[7]);
             }
-            if (c0) return qsvk_diag(st, 1, &b1, 1, &b0, dd);  // half traffic: control on the wide bit
-            if (c1) return qsvk_diag(st, 1, &b0, 1, &b1, dd);
+            if (c0) return diag_op(1, &b1, 1, &b0, dd);  // half traffic: control on the wide bit
+            if (c1) return diag_op(1, &b0, 1, &b1, dd);
         } else if (one0 && one1 && c0) {
-            return qsvk_diag(st, 1, &b1, 1, &b0, d + 4);  // control on leg 0
+            return diag_op(1, &b1, 1, &b0, d + 4);  // control on leg 0
         } else if (one0 && one2 && d[2] == d[6] && d[3] == d[7]) {
             const double dd[4] = {1.0, 0.0, d[2], d[3]};  // acts on leg 1 only
             return diag_1q_bits(st, b1, dd);
         }
     }
     const int bits[2] = {b0, b1};
-    return qsvk_diag(st, 2, bits, 0, nullptr, d);
+    return diag_op(2, bits, 0, nullptr, d);
 }
 
 // Controlled 2x2 gate; one narrow control (bit < 3) is folded into a 4x4 matrix (see QSV_MIN_CTRL_BIT).
-int controlled_1q_bits(qsv_state *st, int nctrl, const int *cbits, int tbit, const double u[8]) {
+QsvOp controlled_1q_bits(qsv_state *st, int nctrl, const int *cbits, int tbit, const double u[8]) {
     int fold = -1;
     for (int i = 0; i < nctrl && st->n >= QSV_LANE_BITS; ++i)
         if (cbits[i] < QSV_MIN_CTRL_BIT) fold = i;
-    if (fold < 0) return qsvk_dense(st, 1, &tbit, nctrl, cbits, u);
+    if (fold < 0) return dense_op(1, &tbit, nctrl, cbits, u);
     double m[32] = {0};
     m[0] = 1.0;            // |00><00|
     m[2 * (1 * 4 + 1)] = 1.0;  // |01><01|
@@ -166,8 +207,124 @@ int controlled_1q_bits(qsv_state *st, int nctrl, const int *cbits, int tbit, con
     for (int i = 0; i < nctrl; ++i)
         if (i != fold) rest.push_back(cbits[i]);
     const int bits[2] = {cbits[fold], tbit};
-    return qsvk_dense(st, 2, bits, static_cast<int>(rest.size()), rest.data(), m);
+    return dense_op(2, bits, static_cast<int>(rest.size()), rest.data(), m);
 }
+
+QsvOp swap_bits(qsv_state *st, int b0, int b1) {
+    if (b0 >= QSV_LANE_BITS && b1 >= QSV_LANE_BITS && st->n >= QSV_LANE_BITS) {
+        QsvOp op;
+        op.kind = QSV_OP_PAIR;
+        op.k = 2;
+        op.bits[0] = b0;
+        op.bits[1] = b1;
+        return op;
+    }
+    static const double SW[32] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0,
+                                  0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0};
+    const int bits[2] = {b0, b1};
+    return dense_op(2, bits, 0, nullptr, SW);
+}
+
+// ---- deferred gates (QSV_OPT_DEFER) --------------------------------------------------------------------------------
+// 1- and 2-qubit gates on a register the library allocated wait in st->queue; qsv_plan.h groups them into passes that
+// k_pass_tile applies in one round trip over HBM each.  Every other entry point that takes the register flushes it first.
+constexpr uint64_t DEFER_MIN_AMPS = 1ull << 22;   // auto: registers of 64 MiB and more (the low end of where per-gate
+                                                  // passes start to spill the 256 MiB Infinity Cache; not yet swept)
+constexpr size_t DEFER_WINDOW = 64;               // queued gates that the planner looks through before it launches a pass
+
+int defer_mode(const qsv_state *st) {
+    static const int from_env = [] {
+        const char *e = getenv("QSV_DEFER");
+        return e && *e ? atoi(e) : 1;
+    }();
+    return st->defer >= 0 ? st->defer : from_env;
+}
+
+bool defer_active(const qsv_state *st) {
+    const int mode = defer_mode(st);
+    if (mode <= 0 || st->kind != 0 || !st->owns_data || st->ptr_exposed || st->n < qsv_plan::TILE_BITS) return false;
+    // the options that send 1- and 2-qubit gates to k_dense instead of the tile form: stay on the per-gate kernels
+    if (st->unroll != 0 || st->kq_variant == 1 || st->kq_variant == 2) return false;
+    return mode >= 2 || st->amps >= DEFER_MIN_AMPS;
+}
+
+// per-gate launch cost in full passes (k_dense_tile12<1> at n = 28: 1.31 ms; CX 0.69, CZ on two wide bits 0.36, SWAP as a
+// pair exchange 0.69): every control on bit >= 3 halves the amplitudes a kernel moves
+qsv_plan::Gate plan_gate(const QsvOp &op) {
+    qsv_plan::Gate g;
+    for (int j = 0; j < op.k; ++j) g.need |= 1ull << op.bits[j];
+    float cost = op.kind == QSV_OP_PAIR ? 0.53f : 1.0f;
+    for (int i = 0; i < op.nctrl; ++i) {
+        g.ctrl |= 1ull << op.cbits[i];
+        if (op.cbits[i] >= QSV_MIN_CTRL_BIT) cost *= 0.53f;
+    }
+    g.cost = cost < 0.2f ? 0.2f : cost;
+    g.exact = qsvk_op_exact(op);
+    return g;
+}
+
+// Plan the queue and launch its first pass (or its first gate alone, where a pass would not pay).
+int defer_launch_first(qsv_state *st) {
+    std::vector<qsv_plan::Gate> q;
+    q.reserve(st->queue.size());
+    for (const QsvOp &op : st->queue) q.push_back(plan_gate(op));
+    const qsv_plan::Pass p = qsv_plan::plan_first(q, st->n);
+    int rc;
+    if (p.fused) {
+        std::vector<const QsvOp *> ops;
+        for (int i : p.gates) ops.push_back(&st->queue[i]);
+        rc = qsvk_pass(st, ops.data(), static_cast<int>(ops.size()), p.tile);
+    } else {
+        rc = qsvk_run_op(st, st->queue[p.gates[0]]);
+    }
+    ++st->defer_launches;
+    if (rc) {
+        st->queue.clear();   // the stream is in an unknown state: what was pending is dropped, the error goes to the caller
+        return rc;
+    }
+    std::vector<bool> taken(st->queue.size(), false);
+    for (int i : p.gates) taken[i] = true;
+    size_t w = 0;
+    for (size_t i = 0; i < st->queue.size(); ++i)
+        if (!taken[i]) st->queue[w++] = st->queue[i];
+    st->queue.resize(w);
+    return QSV_OK;
+}
+
+int defer_flush(qsv_state *st) {
+    if (!st || st->queue.empty()) return QSV_OK;
+    const hipError_t e = hipSetDevice(st->device);
+    if (e != hipSuccess) {
+        st->queue.clear();
+        return qsv_fail(QSV_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    }
+    while (!st->queue.empty()) {
+        const int rc = defer_launch_first(st);
+        if (rc) return rc;
+    }
+    return QSV_OK;
+}
+
+// A classified gate: queued on a deferring register, launched at once on any other.
+int submit(qsv_state *st, const QsvOp &op) {
+    if (op.kind == OP_NONE) return QSV_OK;
+    if (!defer_active(st)) {
+        const int rc = defer_flush(st);
+        if (rc) return rc;
+        return qsvk_run_op(st, op);
+    }
+    st->queue.push_back(op);
+    ++st->defer_gates;
+    // a full window: launch the pass at its front while the host goes on queuing
+    if (st->queue.size() >= DEFER_WINDOW) return defer_launch_first(st);
+    return QSV_OK;
+}
+
+#define QSV_FLUSH(st)                           \
+    do {                                        \
+        const int _frc = defer_flush(st);       \
+        if (_frc) return _frc;                  \
+    } while (0)
 
 }  // namespace
 
@@ -243,6 +400,7 @@ int qsv_destroy(qsv_state *st) {
 
 int qsv_set_stream(qsv_state *st, void *hip_stream) {
     if (!valid(st)) return qsv_fail(QSV_EINVAL, "null state");
+    QSV_FLUSH(st);
     QSV_HIP(hipStreamSynchronize(st->stream));
     st->stream = static_cast<hipStream_t>(hip_stream);
     return QSV_OK;
@@ -250,7 +408,12 @@ int qsv_set_stream(qsv_state *st, void *hip_stream) {
 
 int qsv_set_option(qsv_state *st, int option, int64_t value) {
     if (!valid(st)) return qsv_fail(QSV_EINVAL, "null state");
+    QSV_FLUSH(st);
     switch (option) {
+        case QSV_OPT_DEFER:
+            if (value < -1 || value > 2) return qsv_fail(QSV_EINVAL, "defer must be -1, 0, 1 or 2");
+            st->defer = static_cast<int>(value);
+            return QSV_OK;
         case QSV_OPT_SPECIALIZE: st->specialize = value != 0; return QSV_OK;
         case QSV_OPT_UNROLL:
             if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8)
@@ -310,12 +473,15 @@ int qsv_num_amps(const qsv_state *st, uint64_t *n_amps) {
 
 int qsv_device_ptr(qsv_state *st, void **dev_amps) {
     if (!valid(st) || !dev_amps) return qsv_fail(QSV_EINVAL, "null pointer");
+    QSV_FLUSH(st);
+    st->ptr_exposed = true;   // the caller may now touch the amplitudes behind the library's back: no more deferral
     *dev_amps = st->data;
     return QSV_OK;
 }
 
 int qsv_sync(qsv_state *st) {
     if (!valid(st)) return qsv_fail(QSV_EINVAL, "null state");
+    QSV_FLUSH(st);
     QSV_HIP(hipSetDevice(st->device));
     QSV_HIP(hipStreamSynchronize(st->stream));
     return QSV_OK;
@@ -324,6 +490,7 @@ int qsv_sync(qsv_state *st) {
 int qsv_set_basis(qsv_state *st, uint64_t index) {
     if (!valid(st)) return qsv_fail(QSV_EINVAL, "null state");
     if (index >= st->amps) return qsv_fail(QSV_EINVAL, "basis index out of range");
+    QSV_FLUSH(st);
     QSV_HIP(hipSetDevice(st->device));
     return qsvk_set_basis(st, index);
 }
@@ -331,6 +498,7 @@ int qsv_set_basis(qsv_state *st, uint64_t index) {
 int qsv_upload(qsv_state *st, const double *host, uint64_t offset, uint64_t count) {
     if (!valid(st) || (!host && count)) return qsv_fail(QSV_EINVAL, "null pointer");
     if (offset > st->amps || count > st->amps - offset) return qsv_fail(QSV_EINVAL, "upload range out of bounds");
+    QSV_FLUSH(st);
     QSV_HIP(hipSetDevice(st->device));
     QSV_HIP(hipMemcpyAsync(st->data + offset, host, sizeof(amp_t) * count, hipMemcpyHostToDevice, st->stream));
     QSV_HIP(hipStreamSynchronize(st->stream));
@@ -375,6 +543,7 @@ static void prefault(char *p, size_t bytes, int threads) noexcept {
 int qsv_download(qsv_state *st, double *host, uint64_t offset, uint64_t count) {
     if (!valid(st) || (!host && count)) return qsv_fail(QSV_EINVAL, "null pointer");
     if (offset > st->amps || count > st->amps - offset) return qsv_fail(QSV_EINVAL, "download range out of bounds");
+    QSV_FLUSH(st);
     QSV_HIP(hipSetDevice(st->device));
     const size_t bytes = sizeof(amp_t) * count, piece = 256ull << 20;
     if (bytes < piece) {
@@ -411,6 +580,8 @@ int qsv_copy(qsv_state *dst, const qsv_state *src) {
     if (!valid(dst) || !valid(src)) return qsv_fail(QSV_EINVAL, "null state");
     if (dst->kind != src->kind || dst->d != src->d) return qsv_fail(QSV_ESTATE, "registers of different kinds");
     if (src->amps > dst->capacity) return qsv_fail(QSV_ENOMEM, "destination register too small");
+    QSV_FLUSH(dst);
+    QSV_FLUSH(const_cast<qsv_state *>(src));
     QSV_HIP(hipSetDevice(dst->device));
     QSV_HIP(hipStreamSynchronize(src->stream));
     if (dst->device == src->device) {
@@ -427,12 +598,14 @@ int qsv_copy(qsv_state *dst, const qsv_state *src) {
 
 int qsv_fill_random(qsv_state *st, uint64_t seed, uint64_t index_offset, double *norm2) {
     if (!valid(st)) return qsv_fail(QSV_EINVAL, "null state");
+    QSV_FLUSH(st);
     QSV_HIP(hipSetDevice(st->device));
     return qsvk_fill_random(st, seed, index_offset, norm2);
 }
 
 int qsv_scale(qsv_state *st, double re, double im) {
     if (!valid(st)) return qsv_fail(QSV_EINVAL, "null state");
+    QSV_FLUSH(st);
     QSV_HIP(hipSetDevice(st->device));
     return qsvk_scale(st, re, im);
 }
@@ -447,9 +620,9 @@ int qsv_apply_1q(qsv_state *st, int q, const double m[8]) {
     const int bit = bit_of(st, q);
     if (st->specialize && matrix_is_diagonal(2, m)) {
         const double d[4] = {m[0], m[1], m[6], m[7]};
-        return diag_1q_bits(st, bit, d);
+        return submit(st, diag_1q_bits(st, bit, d));
     }
-    return qsvk_dense(st, 1, &bit, 0, nullptr, m);
+    return submit(st, dense_op(1, &bit, 0, nullptr, m));
 }
 
 int qsv_apply_2q(qsv_state *st, int q0, int q1, const double m[32]) {
@@ -462,7 +635,7 @@ int qsv_apply_2q(qsv_state *st, int q0, int q1, const double m[32]) {
     if (st->specialize) {
         if (matrix_is_diagonal(4, m)) {
             const double d[8] = {m[0], m[1], m[10], m[11], m[20], m[21], m[30], m[31]};
-            return diag_2q_bits(st, bits[0], bits[1], d);
+            return submit(st, diag_2q_bits(st, bits[0], bits[1], d));
         }
         static const double CX[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 1, 0};
         static const double XC[16] = {1, 0, 0, 0, 0, 0, 0, 1, 0, 0, 1, 0, 0, 1, 0, 0};  // control = leg 1
@@ -483,10 +656,10 @@ int qsv_apply_2q(qsv_state *st, int q0, int q1, const double m[32]) {
             }
         if (ctl0) {
             const double u[8] = {m[20], m[21], m[22], m[23], m[28], m[29], m[30], m[31]};
-            if (bits[0] >= QSV_MIN_CTRL_BIT) return qsvk_dense(st, 1, &bits[1], 1, &bits[0], u);
+            if (bits[0] >= QSV_MIN_CTRL_BIT) return submit(st, dense_op(1, &bits[1], 1, &bits[0], u));
         }
     }
-    return qsvk_dense(st, 2, bits, 0, nullptr, m);
+    return submit(st, dense_op(2, bits, 0, nullptr, m));
 }
 
 int qsv_apply_diag_1q(qsv_state *st, int q, const double d[4]) {
@@ -494,7 +667,7 @@ int qsv_apply_diag_1q(qsv_state *st, int q, const double d[4]) {
     int rc = check_qubits(st, 1, &q);
     if (rc) return rc;
     QSV_HIP(hipSetDevice(st->device));
-    return diag_1q_bits(st, bit_of(st, q), d);
+    return submit(st, diag_1q_bits(st, bit_of(st, q), d));
 }
 
 int qsv_apply_diag_2q(qsv_state *st, int q0, int q1, const double d[8]) {
@@ -503,7 +676,7 @@ int qsv_apply_diag_2q(qsv_state *st, int q0, int q1, const double d[8]) {
     int rc = check_qubits(st, 2, qs);
     if (rc) return rc;
     QSV_HIP(hipSetDevice(st->device));
-    return diag_2q_bits(st, bit_of(st, q0), bit_of(st, q1), d);
+    return submit(st, diag_2q_bits(st, bit_of(st, q0), bit_of(st, q1), d));
 }
 
 int qsv_apply_cx(qsv_state *st, int control, int target) {
@@ -514,7 +687,7 @@ int qsv_apply_cx(qsv_state *st, int control, int target) {
     QSV_HIP(hipSetDevice(st->device));
     const int cbit = bit_of(st, control), tbit = bit_of(st, target);
     static const double X[8] = {0, 0, 1, 0, 1, 0, 0, 0};
-    return controlled_1q_bits(st, 1, &cbit, tbit, X);
+    return submit(st, controlled_1q_bits(st, 1, &cbit, tbit, X));
 }
 
 int qsv_apply_swap(qsv_state *st, int q0, int q1) {
@@ -523,12 +696,7 @@ int qsv_apply_swap(qsv_state *st, int q0, int q1) {
     int rc = check_qubits(st, 2, qs);
     if (rc) return rc;
     QSV_HIP(hipSetDevice(st->device));
-    const int b0 = bit_of(st, q0), b1 = bit_of(st, q1);
-    if (b0 >= QSV_LANE_BITS && b1 >= QSV_LANE_BITS && st->n >= QSV_LANE_BITS) return qsvk_pair_exchange(st, b0, b1);
-    static const double SW[32] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0,
-                                  0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0};
-    const int bits[2] = {b0, b1};
-    return qsvk_dense(st, 2, bits, 0, nullptr, SW);
+    return submit(st, swap_bits(st, bit_of(st, q0), bit_of(st, q1)));
 }
 
 int qsv_apply_controlled_1q(qsv_state *st, int n_controls, const int *controls, int target, const double m[8]) {
@@ -544,7 +712,7 @@ int qsv_apply_controlled_1q(qsv_state *st, int n_controls, const int *controls, 
     const int tbit = bit_of(st, target);
     if (st->n < QSV_LANE_BITS && n_controls + 1 > QSV_MAX_K)
         return qsv_fail(QSV_EINVAL, "too many controls for a tiny register");
-    return controlled_1q_bits(st, n_controls, cbits.data(), tbit, m);
+    return submit(st, controlled_1q_bits(st, n_controls, cbits.data(), tbit, m));
 }
 
 int qsv_apply_mcphase(qsv_state *st, int n_qubits, const int *qubits, double re, double im) {
@@ -552,6 +720,7 @@ int qsv_apply_mcphase(qsv_state *st, int n_qubits, const int *qubits, double re,
     if (n_qubits < 0 || n_qubits > 64) return qsv_fail(QSV_EINVAL, "bad qubit count");
     int rc = check_qubits(st, n_qubits, qubits);
     if (rc) return rc;
+    QSV_FLUSH(st);
     QSV_HIP(hipSetDevice(st->device));
     std::vector<int> cbits(n_qubits);
     for (int i = 0; i < n_qubits; ++i) cbits[i] = bit_of(st, qubits[i]);
@@ -575,6 +744,7 @@ int qsv_apply_kq(qsv_state *st, int k, const int *qubits, const double *m) {
     if (k < 1 || k > QSV_MAX_K) return qsv_fail(QSV_EINVAL, "k must be in 1..6");
     int rc = check_qubits(st, k, qubits);
     if (rc) return rc;
+    QSV_FLUSH(st);
     if (k == 1) return qsv_apply_1q(st, qubits[0], m);
     if (k == 2) return qsv_apply_2q(st, qubits[0], qubits[1], m);
     QSV_HIP(hipSetDevice(st->device));
@@ -605,6 +775,7 @@ int qsv_apply_sequence(qsv_state *st, int k, const int *qubits, int n_gates, con
     if (n_gates < 1) return qsv_fail(QSV_EINVAL, "a gate sequence needs at least one gate");
     for (int g = 0; g < n_gates; ++g)
         if (arity[g] < 1 || arity[g] > k) return qsv_fail(QSV_EINVAL, "gate sequence: arity outside 1..k");
+    QSV_FLUSH(st);
     QSV_HIP(hipSetDevice(st->device));
     int bits[QSV_MAX_K];
     for (int j = 0; j < k; ++j) bits[j] = bit_of(st, qubits[j]);
@@ -641,6 +812,7 @@ int qsv_permute(qsv_state *st, const int *new_ordering) {
         if (new_ordering[j] < 0 || new_ordering[j] >= n || seen[new_ordering[j]]++)
             return qsv_fail(QSV_EINVAL, "new_ordering must be a permutation of all qubits");
     }
+    QSV_FLUSH(st);
     QSV_HIP(hipSetDevice(st->device));
     // qubit at position j moves to position new_ordering[j]:
     // destination bit (n-1-new_ordering[j]) takes source bit (n-1-j)
@@ -655,6 +827,7 @@ int qsv_measure_probs(qsv_state *st, int q, const double eig0[4], const double e
     if (!valid(st) || !eig0 || !eig1 || !p0 || !p1) return qsv_fail(QSV_EINVAL, "null pointer");
     int rc = check_qubits(st, 1, &q);
     if (rc) return rc;
+    QSV_FLUSH(st);
     QSV_HIP(hipSetDevice(st->device));
     return qsvk_measure_probs(st, bit_of(st, q), eig0, eig1, p0, p1);
 }
@@ -663,6 +836,7 @@ int qsv_collapse(qsv_state *st, int q, const double eig[4], double scale) {
     if (!valid(st) || !eig) return qsv_fail(QSV_EINVAL, "null pointer");
     int rc = check_qubits(st, 1, &q);
     if (rc) return rc;
+    QSV_FLUSH(st);
     QSV_HIP(hipSetDevice(st->device));
     return qsvk_collapse(st, bit_of(st, q), eig, scale);
 }
@@ -693,6 +867,7 @@ int qsv_insert(qsv_state *st, int q, const double amp[4]) {
     if (st->kind != 0) return qsv_fail(QSV_ESTATE, "this call needs a qubit register");
     if (q < 0 || q > st->n) return qsv_fail(QSV_EINVAL, "new_ordering must be a permutation of all qubits");
     if (st->n + 1 > 40) return qsv_fail(QSV_EINVAL, "register too large");
+    QSV_FLUSH(st);
     QSV_HIP(hipSetDevice(st->device));
     // after insertion the register has n+1 qubits and the new one is qubit q: bit (n+1)-1-q
     return qsvk_insert(st, st->n - q, amp);
@@ -702,6 +877,7 @@ int qsv_insert(qsv_state *st, int q, const double amp[4]) {
 
 int qsv_norm2(qsv_state *st, double *out) {
     if (!valid(st) || !out) return qsv_fail(QSV_EINVAL, "null pointer");
+    QSV_FLUSH(st);
     QSV_HIP(hipSetDevice(st->device));
     return qsvk_norm2(st, out);
 }
@@ -710,6 +886,7 @@ int qsv_probabilities(qsv_state *st, const uint64_t *indices, int count, double 
     if (!valid(st) || (count > 0 && (!indices || !out))) return qsv_fail(QSV_EINVAL, "null pointer");
     for (int i = 0; i < count; ++i)
         if (indices[i] >= st->amps) return qsv_fail(QSV_EINVAL, "amplitude index out of range");
+    QSV_FLUSH(st);
     QSV_HIP(hipSetDevice(st->device));
     return qsvk_probabilities(st, indices, count, out);
 }
@@ -731,6 +908,7 @@ int qsv_expect_pauli(qsv_state *st, int k, const int *qubits, const char *paulis
             default: return qsv_fail(QSV_EINVAL, "Pauli letters must be I, X, Y or Z");
         }
     }
+    QSV_FLUSH(st);
     QSV_HIP(hipSetDevice(st->device));
     return qsvk_expect_pauli(st, xmask, zmask, n_y, re, im);
 }
@@ -739,6 +917,7 @@ int qsv_sample(qsv_state *st, int shots, const double *u, uint64_t *out) {
     if (!valid(st) || (shots > 0 && (!u || !out))) return qsv_fail(QSV_EINVAL, "null pointer");
     if (shots < 0 || shots > (1 << 24)) return qsv_fail(QSV_EINVAL, "shots must be in 0..2^24");
     if (shots == 0) return QSV_OK;
+    QSV_FLUSH(st);
     QSV_HIP(hipSetDevice(st->device));
     return qsvk_sample(st, shots, u, out);
 }
@@ -747,6 +926,8 @@ int qsv_inner(qsv_state *a, qsv_state *b, double *re, double *im) {
     if (!valid(a) || !valid(b) || !re || !im) return qsv_fail(QSV_EINVAL, "null pointer");
     if (a->amps != b->amps) return qsv_fail(QSV_EINVAL, "registers of different sizes");
     if (a->device != b->device) return qsv_fail(QSV_EINVAL, "registers on different devices");
+    QSV_FLUSH(a);
+    QSV_FLUSH(b);
     QSV_HIP(hipSetDevice(a->device));
     return qsvk_inner(a, b, re, im);
 }
@@ -757,6 +938,7 @@ int qsv_reduced_density(qsv_state *st, int k, const int *qubits, double *rho) {
     if (k < 1 || k > QSV_MAX_K) return qsv_fail(QSV_EINVAL, "keep between 1 and 6 qubits");
     int rc = check_qubits(st, k, qubits);
     if (rc) return rc;
+    QSV_FLUSH(st);
     QSV_HIP(hipSetDevice(st->device));
     std::vector<int> bits(k);
     for (int j = 0; j < k; ++j) bits[j] = bit_of(st, qubits[j]);
@@ -768,6 +950,8 @@ int qsv_expect_density(qsv_state *ket, qsv_state *rho, double *re, double *im) {
     if (ket->kind != 0 || rho->kind != 0) return qsv_fail(QSV_ESTATE, "this call needs qubit registers");
     if (rho->n != 2 * ket->n) return qsv_fail(QSV_EINVAL, "the density register must have twice the ket's qubits");
     if (ket->device != rho->device) return qsv_fail(QSV_EINVAL, "registers on different devices");
+    QSV_FLUSH(ket);
+    QSV_FLUSH(rho);
     QSV_HIP(hipSetDevice(rho->device));
     return qsvk_expect_density(ket, rho, re, im);
 }
@@ -1045,6 +1229,7 @@ int qsv_tensor_axis_overlap(int device, void *hip_stream, const void *dev_z, con
 
 int qsv_timer_start(qsv_state *st) {
     if (!valid(st)) return qsv_fail(QSV_EINVAL, "null state");
+    QSV_FLUSH(st);
     QSV_HIP(hipSetDevice(st->device));
     QSV_HIP(hipEventRecord(st->ev_start, st->stream));
     return QSV_OK;
@@ -1052,6 +1237,7 @@ int qsv_timer_start(qsv_state *st) {
 
 int qsv_timer_stop(qsv_state *st, float *elapsed_ms) {
     if (!valid(st) || !elapsed_ms) return qsv_fail(QSV_EINVAL, "null pointer");
+    QSV_FLUSH(st);
     QSV_HIP(hipSetDevice(st->device));
     QSV_HIP(hipEventRecord(st->ev_stop, st->stream));
     QSV_HIP(hipEventSynchronize(st->ev_stop));
@@ -1061,6 +1247,7 @@ int qsv_timer_stop(qsv_state *st, float *elapsed_ms) {
 
 int qsv_last_kernel(const qsv_state *st, char *buf, size_t buf_len) {
     if (!valid(st) || !buf || buf_len == 0) return qsv_fail(QSV_EINVAL, "null pointer");
+    QSV_FLUSH(const_cast<qsv_state *>(st));
     std::strncpy(buf, st->last_kernel, buf_len - 1);
     buf[buf_len - 1] = '\0';
     return QSV_OK;
@@ -1069,10 +1256,23 @@ int qsv_last_kernel(const qsv_state *st, char *buf, size_t buf_len) {
 int qsv_event_record(qsv_state *st, int slot) {
     if (!valid(st)) return qsv_fail(QSV_EINVAL, "null state");
     if (slot < 0 || slot >= 16384) return qsv_fail(QSV_EINVAL, "event slot out of range");
+    QSV_FLUSH(st);
     QSV_HIP(hipSetDevice(st->device));
     if (st->marks.size() <= static_cast<size_t>(slot)) st->marks.resize(slot + 1, nullptr);
     if (!st->marks[slot]) QSV_HIP(hipEventCreate(&st->marks[slot]));
     QSV_HIP(hipEventRecord(st->marks[slot], st->stream));
+    return QSV_OK;
+}
+
+int qsv_flush(qsv_state *st) {
+    if (!valid(st)) return qsv_fail(QSV_EINVAL, "null state");
+    return defer_flush(st);
+}
+
+int qsv_defer_stats(const qsv_state *st, uint64_t *gates_queued, uint64_t *launches) {
+    if (!valid(st) || !gates_queued || !launches) return qsv_fail(QSV_EINVAL, "null pointer");
+    *gates_queued = st->defer_gates;
+    *launches = st->defer_launches;
     return QSV_OK;
 }
 
@@ -1082,6 +1282,7 @@ int qsv_event_elapsed_ms(qsv_state *st, int slot_a, int slot_b, float *elapsed_m
     if (slot_a < 0 || slot_b < 0 || static_cast<size_t>(hi) >= st->marks.size() || !st->marks[slot_a] ||
         !st->marks[slot_b])
         return qsv_fail(QSV_EINVAL, "event slot was never recorded");
+    QSV_FLUSH(st);
     QSV_HIP(hipSetDevice(st->device));
     QSV_HIP(hipEventSynchronize(st->marks[slot_b]));
     QSV_HIP(hipEventElapsedTime(elapsed_ms, st->marks[slot_a], st->marks[slot_b]));

@@ -51,6 +51,19 @@ struct DiagArgs {
     double d[8];
 };
 
+// One 1- or 2-qubit gate as the per-gate launcher runs it (qsvk_run_op): the classification of qsv_apply_* (diagonal,
+// phase, CX / controlled-U, SWAP as a pair exchange, dense) with everything held by value, so that it can wait in a queue.
+enum { QSV_OP_DENSE = 0, QSV_OP_PAIR = 1, QSV_OP_DIAG = 2, QSV_OP_PHASE = 3 };
+constexpr int QSV_OP_MAX_CTRL = 40;
+struct QsvOp {
+    int kind = QSV_OP_DENSE;
+    int k = 0;                        // target legs (dense, diag: 1 or 2; pair: 2; phase: 0)
+    int bits[2] = {-1, -1};           // target bits, leg 0 first (leg 0 = most significant matrix index bit)
+    int nctrl = 0;
+    int cbits[QSV_OP_MAX_CTRL] = {};  // control bits (phase: the bits that must all be 1)
+    double m[32] = {};                // dense: 2^k x 2^k row-major complex; diag: 2^k complex; phase: (re, im)
+};
+
 struct qsv_state {
     int device = 0;
     int kind = 0;            // 0 = qubits, 1 = qudits
@@ -95,6 +108,12 @@ struct qsv_state {
     int plane_kernel = 1;             // block-diagonal two-mode operators on the last two modes: 1 = workgroup-per-plane
                                       // form (k_mode2_plane), 0 = plane-per-thread form (k_mode2_blocks<64>)
     char last_kernel[96] = "";        // name of the most recent gate kernel launched (qsv_last_kernel)
+    // deferred gates (QSV_OPT_DEFER): 1- and 2-qubit gates wait here and are applied in shared passes (k_pass_tile)
+    int defer = -1;                   // -1 = $QSV_DEFER or 1 (auto), 0 = off, 1 = auto, 2 = always
+    bool ptr_exposed = false;         // qsv_device_ptr handed out the register's address: never defer again
+    std::vector<QsvOp> queue;         // pending gates, in call order
+    uint64_t defer_gates = 0;         // gates that went through the queue
+    uint64_t defer_launches = 0;      // launches that applied them (passes + single gates)
 };
 
 constexpr int QSV_REDUCE_BLOCKS = 1024;
@@ -127,6 +146,9 @@ int qsvk_diag(qsv_state *st, int k, const int *bits, int nctrl, const int *cbits
 int qsvk_phase(qsv_state *st, int nctrl, const int *cbits, double re, double im);
 int qsvk_generic(qsv_state *st, int k, const int *bits, const double *m_user);
 int qsvk_sequence5(qsv_state *st, const int *bits, int n_gates, const int *arity, const int *legs, const double *mats);
+int qsvk_run_op(qsv_state *st, const QsvOp &op);                     // the gate on its own kernel, as without deferral
+int qsvk_pass(qsv_state *st, const QsvOp *const *ops, int count, uint64_t tile_high);   // one k_pass_tile launch
+bool qsvk_op_exact(const QsvOp &op);                                 // a signed permutation (entries 0 / +-1 only)
 int qsvk_sequence_tile(qsv_state *st, int k, const int *bits, int n_gates, const int *arity, const int *legs, const double *mats);
 constexpr int QSV_UNHANDLED_KQ = 1 << 20;  // internal: "not this kernel's case"
 int qsvk_measure_probs(qsv_state *st, int bit, const double eig0[4], const double eig1[4], double *p0, double *p1);

@@ -14,6 +14,7 @@
 // (simulators/dv_simulator/gates.py:44-54, numpy_quantum.py:243-247).
 
 #include "qsv_internal.h"
+#include "qsv_plan.h"
 
 #include <algorithm>
 #include <array>
@@ -32,6 +33,16 @@ __device__ __forceinline__ amp_t cmul(cplx m, amp_t a) {
     amp_t r;
     r.x = m.re * a.x - m.im * a.y;
     r.y = m.re * a.y + m.im * a.x;
+    return r;
+}
+
+// d * a for the diagonal kernels (k_diag, and k_pass_tile's diagonal gates), with the two fused multiply-adds spelled
+// out: left to the compiler, `re * a.y + im * a.x` is contracted one way or the other depending on the surrounding code,
+// and a deferred gate must round exactly as its per-gate launch does.  This is the form k_diag was compiled to.
+__device__ __forceinline__ amp_t cmul_diag(cplx d, amp_t a) {
+    amp_t r;
+    r.x = fma(a.x, d.re, -(a.y * d.im));
+    r.y = fma(a.x, d.im, a.y * d.re);
     return r;
 }
 
@@ -212,7 +223,7 @@ __global__ __launch_bounds__(QSV_BLOCK) void k_diag(amp_t *__restrict__ a, const
                 const int s1 = static_cast<int>((idx[u] >> g.b1) & 1ull);
                 d = s0 ? (s1 ? d3 : d2) : (s1 ? d1 : d0);
             }
-            st<NT>(a + idx[u], cmul(d, v[u]));
+            st<NT>(a + idx[u], cmul_diag(d, v[u]));
         }
     }
 }
@@ -2407,15 +2418,22 @@ static int launch_tile12_kernels(qsv_state *st, int k, bool sub, BigArgs g, cons
     return QSV_OK;
 }
 
-static int launch_tile12(qsv_state *st, int k, const int *bits, int nctrl, const int *cbits, const double *m_user) {
-    const int D = 1 << k;
-    if (k + nctrl > 2 * QSV_MAX_K || (nctrl && k != 1)) return QSV_UNHANDLED_KQ;   // controlled 4 x 4 gates only arise with a folded narrow control
+// Does a dense 1- / 2-qubit gate take the tile form (k_dense_tile12*)?  Otherwise it runs on k_dense / k_dense_ctrl.  The
+// pass kernel (k_pass_tile) asks too: it sums each gate's products in the order of the kernel the gate would have run on.
+static bool tile12_takes(const qsv_state *st, int k, const int *bits, int nctrl, const int *cbits) {
+    if (k + nctrl > 2 * QSV_MAX_K || (nctrl && k != 1)) return false;   // controlled 4 x 4 gates only arise with a folded narrow control
     for (int i = 0; i < nctrl; ++i)
-        if (cbits[i] < 3) return QSV_UNHANDLED_KQ;   // a control inside a 128-byte line cannot be skipped
+        if (cbits[i] < 3) return false;   // a control inside a 128-byte line cannot be skipped
     const uint64_t W = st->amps >> (k + nctrl);
     const int lowest = k == 1 ? bits[0] : std::min(bits[0], bits[1]);
     // 2-qubit gates with a target inside a wavefront (bits 3..5) are better off with k_dense<1, 1> (1.29-1.37 ms)
-    if (lowest < (k == 1 ? 3 : QSV_LANE_BITS) || W < 64 || W % 64) return QSV_UNHANDLED_KQ;
+    return !(lowest < (k == 1 ? 3 : QSV_LANE_BITS) || W < 64 || W % 64);
+}
+
+static int launch_tile12(qsv_state *st, int k, const int *bits, int nctrl, const int *cbits, const double *m_user) {
+    const int D = 1 << k;
+    if (!tile12_takes(st, k, bits, nctrl, cbits)) return QSV_UNHANDLED_KQ;
+    const uint64_t W = st->amps >> (k + nctrl);
     SmallGate sg;
     std::memset(&sg, 0, sizeof(sg));
     int ui[4];
@@ -2970,6 +2988,280 @@ int qsvk_sequence_tile(qsv_state *st, int k, const int *bits, int n_gates, const
         const dim3 gd(static_cast<unsigned>(tiles)), bd(TILE_SEQ_THREADS);
         if (nt) hipLaunchKernelGGL(k_seq_tile<true>, gd, bd, lds, st->stream, st->data, ta, dev_g, dev_p, static_cast<int>(passes.size()), dev_off);
         else hipLaunchKernelGGL(k_seq_tile<false>, gd, bd, lds, st->stream, st->data, ta, dev_g, dev_p, static_cast<int>(passes.size()), dev_off);
+        rc = check_launch();
+        if (rc) return rc;
+    }
+    return qsvk_stage_done(st, staged);
+}
+
+// ---- deferred gates: one PASS of queued 1- and 2-qubit gates over LDS-resident tiles ----------------------------------
+// The queue of a deferring register (qsv_api.hip) is cut into passes by qsv_plan.h.  A workgroup brings one 4096-amplitude
+// tile into LDS -- bits 0..5 plus the pass's six further tile bits, so every tile row is one 1 KiB run of HBM, straight
+// into LDS on the way in -- applies the pass's gates to it one after the other (a barrier between gates) and stores it back:
+// one round trip over HBM for the whole list.  A gate's control bits outside the tile are the same for every amplitude of
+// a tile: they decide per workgroup whether the gate acts (omask), and a tile on which no gate of the pass acts is neither
+// loaded nor stored.  Each gate is computed with the expression and the summation order of the per-gate kernel it would
+// have run on (tile12_body: products summed from zero in kernel-index order; dense_body: low-lane combinations outer,
+// high rows inner; k_diag: one complex product), so the amplitudes are bit for bit those of the per-gate path.
+enum { PASS_D2 = 0, PASS_D2X = 1, PASS_D4 = 2, PASS_D4X = 3, PASS_D4HL = 4, PASS_DIAG = 5 };
+struct PassGate {
+    int32_t form;        // PASS_*: dense on 2 / 4 amplitudes in one of dense_body's / tile12_body's orders, or diagonal
+    int32_t z0, z1;      // dense: tile bits that are 0 in a group's base, ascending (z1 < 0: one); diagonal: the bits
+                         // that select d (d[(s0 << 1) | s1]; z1 < 0: d[s0])
+    uint32_t cmask;      // tile bits that must be 1 (controls inside the tile)
+    uint32_t off[4];     // dense: tile offset of kernel index c
+    uint64_t omask;      // register bits outside the tile that must be 1 (the same for every amplitude of a tile)
+    uint64_t pad;
+    double m[32];        // dense: D x D kernel-order matrix, (re, im) interleaved; diagonal: d[0..3]
+};
+constexpr int PASS_TILE = 1 << qsv_plan::TILE_BITS, PASS_ROWS = PASS_TILE / 64, PASS_THREADS = 256;
+constexpr int PASS_ROWS_PER_WAVE = PASS_ROWS / (PASS_THREADS / 64);
+
+struct PassArgs {
+    BigArgs g;                     // pos[] = the 12 tile bits: the tile number is deposited around them
+    uint64_t row_off[PASS_ROWS];   // register offset of tile row r (tile bits 6..11)
+};
+
+// Kernel index of the j-th product summed into output row r.  NAT: tile12_body and dense_body without low targets;
+// XOR: dense_body with every target a lane bit (x = j over the low combinations); HL: dense_body with one high and one low
+// target (x = j >> 1 outer, hp = j & 1 inner, column (hp, l ^ x)).
+template <int FORM>
+__device__ __forceinline__ constexpr int pass_col(int r, int j) {
+    return FORM == 0 ? j : FORM == 1 ? (j ^ r) : (((j & 1) << 1) | ((r & 1) ^ (j >> 1)));
+}
+
+template <int D, int FORM>
+__device__ __forceinline__ void pass_dense(amp_t *__restrict__ tile, const PassGate &pg) {
+    const int count = PASS_TILE >> (pg.z1 >= 0 ? 2 : 1);
+    for (int grp = threadIdx.x; grp < count; grp += PASS_THREADS) {
+        uint32_t g0 = static_cast<uint32_t>(insert_zero(static_cast<uint64_t>(grp), pg.z0));
+        if (pg.z1 >= 0) g0 = static_cast<uint32_t>(insert_zero(g0, pg.z1));
+        if ((g0 & pg.cmask) != pg.cmask) continue;
+        amp_t x[D], y[D];
+#pragma unroll
+        for (int c = 0; c < D; ++c) x[c] = tile[g0 | pg.off[c]];
+#pragma unroll
+        for (int r = 0; r < D; ++r) {
+            amp_t acc = {0.0, 0.0};
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                const int c = pass_col<FORM>(r, j);
+                acc = cfma(cplx{pg.m[2 * (r * D + c)], pg.m[2 * (r * D + c) + 1]}, x[c], acc);
+            }
+            y[r] = acc;
+        }
+#pragma unroll
+        for (int r = 0; r < D; ++r) tile[g0 | pg.off[r]] = y[r];
+    }
+}
+
+__device__ __forceinline__ void pass_diag(amp_t *__restrict__ tile, const PassGate &pg) {
+    const cplx d0 = {pg.m[0], pg.m[1]}, d1 = {pg.m[2], pg.m[3]}, d2 = {pg.m[4], pg.m[5]}, d3 = {pg.m[6], pg.m[7]};
+    for (int i = threadIdx.x; i < PASS_TILE; i += PASS_THREADS) {
+        if ((static_cast<uint32_t>(i) & pg.cmask) != pg.cmask) continue;
+        const int s0 = (i >> pg.z0) & 1;
+        cplx d;
+        if (pg.z1 < 0) {
+            d = s0 ? d1 : d0;
+        } else {
+            const int s1 = (i >> pg.z1) & 1;
+            d = s0 ? (s1 ? d3 : d2) : (s1 ? d1 : d0);
+        }
+        tile[i] = cmul_diag(d, tile[i]);
+    }
+}
+
+template <bool NT>
+__global__ __launch_bounds__(PASS_THREADS) void k_pass_tile(amp_t *__restrict__ a, const PassArgs pa,
+                                                            const PassGate *__restrict__ gates, int n_gates) {
+    __shared__ amp_t tile[PASS_TILE];      // [row][64 lanes]: LDS index = tile index (bits 0..5 lane, 6..11 row)
+    const BigArgs &g = pa.g;
+    const int lane = threadIdx.x & 63;
+    const int q = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    constexpr int RPW = PASS_ROWS_PER_WAVE;
+    const uint64_t tile_id = (g.regions > 1 && gridDim.x % g.regions == 0)
+                                 ? (blockIdx.x % g.regions) * (gridDim.x / g.regions) + blockIdx.x / g.regions
+                                 : blockIdx.x;
+    const uint64_t base = deposit(g.w0 + tile_id, g);
+    uint64_t active = 0;                   // wave-uniform: bit i = gate i acts on this tile
+    for (int i = 0; i < n_gates; ++i)
+        if ((base & gates[i].omask) == gates[i].omask) active |= 1ull << i;
+    if (!active) return;
+#if defined(__HIP_DEVICE_COMPILE__)   // the builtin exists in the device pass only
+#pragma unroll
+    for (int i = 0; i < RPW; ++i)
+        __builtin_amdgcn_global_load_lds(a + base + pa.row_off[q * RPW + i] + lane, tile + (q * RPW + i) * 64, 16, 0, NT ? 2 : 0);
+#endif
+    __syncthreads();
+#pragma unroll 1
+    for (int i = 0; i < n_gates; ++i) {
+        if (!((active >> i) & 1)) continue;
+        const PassGate &pg = gates[i];
+        switch (pg.form) {     // wave-uniform (scalar loads)
+            case PASS_D2: pass_dense<2, 0>(tile, pg); break;
+            case PASS_D2X: pass_dense<2, 1>(tile, pg); break;
+            case PASS_D4: pass_dense<4, 0>(tile, pg); break;
+            case PASS_D4X: pass_dense<4, 1>(tile, pg); break;
+            case PASS_D4HL: pass_dense<4, 2>(tile, pg); break;
+            default: pass_diag(tile, pg); break;
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < RPW; ++i) st<NT>(a + base + pa.row_off[q * RPW + i] + lane, tile[(q * RPW + i) * 64 + lane]);
+}
+
+bool qsvk_op_exact(const QsvOp &op) {
+    if (op.kind == QSV_OP_PAIR) return true;
+    auto unit = [](double re, double im) { return im == 0.0 && (re == 1.0 || re == -1.0); };
+    if (op.kind == QSV_OP_PHASE) return unit(op.m[0], op.m[1]);
+    if (op.kind == QSV_OP_DIAG) {
+        for (int i = 0; i < (1 << op.k); ++i)
+            if (!unit(op.m[2 * i], op.m[2 * i + 1])) return false;
+        return true;
+    }
+    // dense: one +-1 per row and per column, zeros elsewhere (every output is one input, negated or not)
+    const int D = 1 << op.k;
+    int per_col[4] = {0, 0, 0, 0};
+    for (int r = 0; r < D; ++r) {
+        int nz = 0;
+        for (int c = 0; c < D; ++c) {
+            const double re = op.m[2 * (r * D + c)], im = op.m[2 * (r * D + c) + 1];
+            if (re == 0.0 && im == 0.0) continue;
+            if (!unit(re, im)) return false;
+            ++nz;
+            ++per_col[c];
+        }
+        if (nz != 1) return false;
+    }
+    for (int c = 0; c < D; ++c)
+        if (per_col[c] != 1) return false;
+    return true;
+}
+
+int qsvk_run_op(qsv_state *st, const QsvOp &op) {
+    switch (op.kind) {
+        case QSV_OP_DENSE: return qsvk_dense(st, op.k, op.bits, op.nctrl, op.cbits, op.m);
+        case QSV_OP_PAIR: return qsvk_pair_exchange(st, op.bits[0], op.bits[1]);
+        case QSV_OP_DIAG: return qsvk_diag(st, op.k, op.bits, op.nctrl, op.cbits, op.m);
+        case QSV_OP_PHASE: return qsvk_phase(st, op.nctrl, op.cbits, op.m[0], op.m[1]);
+        default: return qsv_fail(QSV_EINVAL, "internal: unknown queued gate kind");
+    }
+}
+
+// One k_pass_tile launch for `count` queued gates (in application order) on the tiles spanned by bits 0..5 and tile_high.
+int qsvk_pass(qsv_state *st, const QsvOp *const *ops, int count, uint64_t tile_high) {
+    const uint64_t low = (1ull << QSV_LANE_BITS) - 1;
+    if (count < 1 || count > qsv_plan::MAX_PASS_GATES || st->n < qsv_plan::TILE_BITS || (tile_high & low) ||
+        __builtin_popcountll(tile_high) != qsv_plan::HIGH_BITS || (tile_high >> st->n))
+        return qsv_fail(QSV_EINVAL, "internal: malformed gate pass");
+    int tile_bits[qsv_plan::TILE_BITS];
+    int local_of[64];
+    for (int b = 0; b < 64; ++b) {
+        local_of[b] = qsv_plan::tile_index(b, tile_high);
+        if (local_of[b] >= 0) tile_bits[local_of[b]] = b;
+    }
+    std::vector<PassGate> rec(count);
+    for (int i = 0; i < count; ++i) {
+        const QsvOp &op = *ops[i];
+        PassGate &pg = rec[i];
+        std::memset(&pg, 0, sizeof(pg));
+        pg.z1 = -1;
+        uint64_t ctrl = 0;
+        for (int c = 0; c < op.nctrl; ++c) ctrl |= 1ull << op.cbits[c];
+        const qsv_plan::ControlMasks cm = qsv_plan::control_masks(ctrl, tile_high);
+        pg.cmask = cm.inside;
+        pg.omask = cm.outside;
+        for (int j = 0; j < op.k; ++j)
+            if (local_of[op.bits[j]] < 0) return qsv_fail(QSV_EINVAL, "internal: gate target outside its pass's tile");
+        if (op.kind == QSV_OP_DIAG || op.kind == QSV_OP_PHASE) {
+            pg.form = PASS_DIAG;
+            if (op.kind == QSV_OP_PHASE) {           // k_diag with b0 = 0 and d0 = d1 = the phase (qsvk_phase)
+                pg.z0 = 0;
+                pg.m[0] = pg.m[2] = op.m[0];
+                pg.m[1] = pg.m[3] = op.m[1];
+            } else {
+                pg.z0 = local_of[op.bits[0]];
+                if (op.k == 2) pg.z1 = local_of[op.bits[1]];
+                std::memcpy(pg.m, op.m, sizeof(double) * (2u << op.k));
+            }
+            continue;
+        }
+        if (op.kind == QSV_OP_PAIR) {               // qsvk_pair_exchange: X between (a, b) = (1, 0) and (0, 1)
+            const int la = local_of[op.bits[0]], lb = local_of[op.bits[1]];
+            pg.form = PASS_D2;
+            pg.z0 = std::min(la, lb);
+            pg.z1 = std::max(la, lb);
+            pg.off[0] = 1u << la;
+            pg.off[1] = 1u << lb;
+            pg.m[2] = 1.0;
+            pg.m[4] = 1.0;
+            continue;
+        }
+        // dense: kernel index bit i <-> register bit kb[i], matrix re-indexed as the per-gate launcher does
+        const int k = op.k, D = 1 << k;
+        int kb[2] = {op.bits[0], op.bits[1]};
+        int form;
+        if (tile12_takes(st, k, op.bits, op.nctrl, op.cbits)) {      // launch_tile12: kernel bit leg <-> bits[leg]
+            form = k == 1 ? PASS_D2 : PASS_D4;
+        } else {                                                     // qsvk_dense: low targets first, then high ones
+            int low_b[2], high_b[2], nl = 0, nh = 0;
+            for (int j = 0; j < k; ++j) {
+                if (op.bits[j] >= QSV_LANE_BITS) high_b[nh++] = op.bits[j];
+                else low_b[nl++] = op.bits[j];
+            }
+            for (int j = 0; j < nl; ++j) kb[j] = low_b[j];
+            for (int j = 0; j < nh; ++j) kb[nl + j] = high_b[j];
+            form = nl == 0 ? (k == 1 ? PASS_D2 : PASS_D4) : nh == 0 ? (k == 1 ? PASS_D2X : PASS_D4X) : PASS_D4HL;
+        }
+        pg.form = form;
+        auto user_index = [&](int kidx) {        // matrix index of kernel index kidx (leg 0 = most significant)
+            int u = 0;
+            for (int i2 = 0; i2 < k; ++i2) {
+                const int bitval = (kidx >> i2) & 1;
+                for (int j = 0; j < k; ++j)
+                    if (op.bits[j] == kb[i2]) u |= bitval << (k - 1 - j);
+            }
+            return u;
+        };
+        for (int r = 0; r < D; ++r)
+            for (int c = 0; c < D; ++c) {
+                const int ur = user_index(r), uc = user_index(c);
+                pg.m[2 * (r * D + c)] = op.m[2 * (ur * D + uc)];
+                pg.m[2 * (r * D + c) + 1] = op.m[2 * (ur * D + uc) + 1];
+            }
+        for (int c = 0; c < D; ++c)
+            for (int i2 = 0; i2 < k; ++i2)
+                if ((c >> i2) & 1) pg.off[c] |= 1u << local_of[kb[i2]];
+        const int l0 = local_of[kb[0]];
+        pg.z0 = l0;
+        if (k == 2) {
+            const int l1 = local_of[kb[1]];
+            pg.z0 = std::min(l0, l1);
+            pg.z1 = std::max(l0, l1);
+        }
+    }
+    StageRef staged;
+    int rc = qsvk_stage(st, rec.data(), sizeof(PassGate) * rec.size(), nullptr, 0, &staged);
+    if (rc) return rc;
+    const PassGate *dev_g = reinterpret_cast<const PassGate *>(staged.dev);
+    PassArgs pa;
+    std::memset(&pa, 0, sizeof(pa));
+    BigArgs &g = pa.g;
+    g.W = st->amps >> qsv_plan::TILE_BITS;      // tiles: the index with every tile bit taken out
+    g.nins = qsv_plan::TILE_BITS;
+    for (int j = 0; j < qsv_plan::TILE_BITS; ++j) g.pos[j] = static_cast<uint32_t>(tile_bits[j]);
+    for (int row = 0; row < PASS_ROWS; ++row)
+        for (int j = 0; j < qsv_plan::HIGH_BITS; ++j)
+            if ((row >> j) & 1) pa.row_off[row] |= 1ull << tile_bits[QSV_LANE_BITS + j];
+    g.regions = st->remap >= 0 ? static_cast<uint32_t>(st->remap) : 8;
+    const bool nt = st->nontemporal != 0;
+    snprintf(st->last_kernel, sizeof(st->last_kernel), "k_pass_tile<%s>", nt ? "true" : "false");
+    const uint64_t per_launch = 1ull << 23;       // tiles per dispatch (a power of two: the tile order stays whole)
+    for (g.w0 = 0; g.w0 < g.W; g.w0 += per_launch) {
+        const dim3 gd(static_cast<unsigned>(std::min(per_launch, g.W - g.w0))), bd(PASS_THREADS);
+        if (nt) hipLaunchKernelGGL(k_pass_tile<true>, gd, bd, 0, st->stream, st->data, pa, dev_g, count);
+        else hipLaunchKernelGGL(k_pass_tile<false>, gd, bd, 0, st->stream, st->data, pa, dev_g, count);
         rc = check_launch();
         if (rc) return rc;
     }

@@ -348,6 +348,16 @@ class DeviceState:
         return ms.value
 
 
+    def flush(self) -> None:
+        """Apply the gates the register has queued (QSV_OPT_DEFER); every read-out does this by itself."""
+        _lib.call("qsv_flush", self._h)
+
+    def defer_stats(self) -> tuple[int, int]:
+        """(gates that went through the deferred queue, launches that applied them)."""
+        g, n = C.c_uint64(), C.c_uint64()
+        _lib.call("qsv_defer_stats", self._h, C.byref(g), C.byref(n))
+        return g.value, n.value
+
     def last_kernel(self) -> str:
         """Name of the gate kernel the most recent apply launched, as rocprofv3 spells it."""
         buf = C.create_string_buffer(128)

@@ -261,7 +261,16 @@ int qsv_tensor_apply_axis_dev(int device, void *hip_stream, const void *dev_in, 
  * (cv_simulator/gates.py:48-84,151-192).  These entry points are that update on raw device tensors: every pointer
  * is device memory (row-major complex128 unless noted), every call runs on `hip_stream` of `device`; calls that
  * return data to the host synchronise the stream.  GEMM and SVD come from rocBLAS / rocSOLVER (bound by dlopen);
- * without them these calls return QSV_EHIP. */
+ * without them these calls return QSV_EHIP.
+ *
+ * Threading.  Every (device, stream) pair has a context of its own inside the library: a rocBLAS handle bound to that
+ * stream, a grow-only scratch pool and the state of the QSV_RANK_NEEDS_OMEGA protocol.  Calls on distinct streams may
+ * run concurrently from distinct threads; calls on one stream must come from one thread at a time.  No lock is held
+ * across a kernel launch, a library call or a stream synchronisation.  A call waits for its own stream and frees no
+ * device memory: a pool that grows keeps its old block until the context is released, and so does the shared cache of
+ * the fixed probe matrices of the splits' low-rank route when it evicts one.  Only the two release calls below free
+ * memory, and hipFree waits for the whole device: call them between batches, not while other streams work.  Run independent MPS
+ * simulations side by side by giving each its own stream (quantum_computations_amd.concurrent.map_on_streams). */
 /* C (m x n) = op(A) . op(B); op: 0 = as stored, 1 = transpose, 2 = conjugate transpose; A is (m x k) or, with an
  * op, (k x m); likewise B.  np.tensordot(m1, m2, (2, 0)) (gates.py:68) and the environment recursions of
  * MPS.norm / partial_density_mps (mps.py:166-190). */
@@ -298,8 +307,17 @@ int qsv_tensor_rsvd_split(int device, void *hip_stream, const void *dev_theta, u
 int qsv_tensor_skinny_gemm(int device, void *hip_stream, int op, uint64_t n, uint64_t m, int l, const void *dev_a,
                            const void *dev_q, void *dev_y);
 /* The splits keep their scratch memory (a copy-free pass needs panels only, the exact SVD its factors) in a grow-only
- * pool per device; this returns the pool of `device` to the driver.  It is re-grown on demand. */
+ * pool per (device, stream) context.  qsv_tensor_release_workspace frees the pools of every context of `device` (the
+ * contexts and their rocBLAS handles stay) and the evicted probe matrices, after waiting for the whole device: it must
+ * not be called while other streams of the device are working in the library.  Pools are re-grown on demand. */
 int qsv_tensor_release_workspace(int device);
+/* Free the context of one stream -- its rocBLAS handle and its pools -- after waiting for that stream.  The frees
+ * themselves wait for the whole device.  A stream the library has not seen is no error.  Call it before destroying a
+ * stream that ran tensor calls. */
+int qsv_tensor_release_stream_workspace(int device, void *hip_stream);
+/* Grow the pool of the stream's context to at least `bytes` now (a no-op when it is that large), so that the calls of
+ * a batch never grow pools -- an allocation -- mid-flight. */
+int qsv_tensor_reserve_workspace(int device, void *hip_stream, uint64_t bytes);
 /* t[l, j, r] *= diag[j] in place: Z and P on a site (gates.py:223,245). */
 int qsv_tensor_scale_axis(int device, void *hip_stream, void *dev_t, uint64_t L, uint64_t d, uint64_t R,
                           const void *dev_diag /* d */);

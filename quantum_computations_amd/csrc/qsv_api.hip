@@ -1151,6 +1151,14 @@ int qsv_tensor_skinny_gemm(int device, void *hip_stream, int op, uint64_t n, uin
 
 int qsv_tensor_release_workspace(int device) { return qsvg_release_workspace(device); }
 
+int qsv_tensor_release_stream_workspace(int device, void *hip_stream) {
+    return qsvg_release_stream_workspace(device, as_stream(hip_stream));
+}
+
+int qsv_tensor_reserve_workspace(int device, void *hip_stream, uint64_t bytes) {
+    return qsvg_reserve_workspace(device, as_stream(hip_stream), bytes);
+}
+
 int qsv_tensor_scale_axis(int device, void *hip_stream, void *dev_t, uint64_t L, uint64_t d, uint64_t R,
                           const void *dev_diag) {
     if (!dev_t || !dev_diag) return qsv_fail(QSV_EINVAL, "null pointer");

@@ -7,6 +7,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <memory>
+#include <mutex>
 #include <vector>
 
 #include "qsv_linalg.h"
@@ -847,9 +849,9 @@ uint64_t kept_rank(const std::vector<double> &sv, int64_t max_bond_dim, double a
 
 constexpr int QSV_UNDECIDED = 2;
 bool fused_panels_enabled();
-int try_verified_low_rank(RocblasApi &a, rocblas_handle h, int device, hipStream_t stream, const amp_t *theta,
-                          uint64_t rows, uint64_t cols, int64_t max_bond_dim, double abs_err, double rel_err, amp_t *m1,
-                          amp_t *m2, uint64_t capacity, uint64_t *rank_out, std::vector<double> *values,
+int try_verified_low_rank(RocblasApi &a, rocblas_handle h, StreamContext &ctx, const amp_t *theta, uint64_t rows,
+                          uint64_t cols, int64_t max_bond_dim, double abs_err, double rel_err, amp_t *m1, amp_t *m2,
+                          uint64_t capacity, uint64_t *rank_out, std::vector<double> *values,
                           double *frobenius_squared_out = nullptr);
 
 // The exact split by one-sided Jacobi sweeps over the whole matrix (k_jacobi_pair): theta is left untouched;
@@ -998,9 +1000,10 @@ int qsvg_svd_split(int device, hipStream_t stream, amp_t *theta, uint64_t rows, 
     const uint64_t lim = 0x7fffffffull;
     if (rows > lim || cols > lim) return qsv_fail(QSV_EINVAL, "matrix dimension exceeds 2^31 - 1");
     RocblasApi &a = api();
-    std::lock_guard<std::mutex> guard(a.lock);
     int rc;
-    rocblas_handle h = handle_for(a, device, stream, &rc);
+    StreamContext *ctx = context_for(device, stream, &rc);
+    if (!ctx) return rc;
+    rocblas_handle h = handle_of(*ctx, &rc);
     if (!h) return rc;
     if (!a.zgesvd) return qsv_fail(QSV_EHIP, "rocSOLVER could not be loaded (librocsolver.so.0): no SVD available");
     const uint64_t k = rows < cols ? rows : cols;
@@ -1011,8 +1014,8 @@ int qsvg_svd_split(int device, hipStream_t stream, amp_t *theta, uint64_t rows, 
     double frobenius_squared = -1.0;      // filled in by the verified route when it gets far enough to measure it
     if (shortcuts_enabled && fused_panels_enabled()) {     // any tolerance: the route verifies itself (or declines)
         std::vector<double> values;
-        const int fast = try_verified_low_rank(a, h, device, stream, theta, rows, cols, max_bond_dim, abs_err, rel_err, m1, m2,
-                                               capacity, rank_out, s_host ? &values : nullptr, &frobenius_squared);
+        const int fast = try_verified_low_rank(a, h, *ctx, theta, rows, cols, max_bond_dim, abs_err, rel_err, m1, m2, capacity,
+                                               rank_out, s_host ? &values : nullptr, &frobenius_squared);
         if (fast == QSV_OK) {
             if (s_host)
                 for (uint64_t i = 0; i < k; ++i) s_host[i] = values[i];
@@ -1021,7 +1024,7 @@ int qsvg_svd_split(int device, hipStream_t stream, amp_t *theta, uint64_t rows, 
         if (fast != QSV_UNDECIDED) return fast;
     }
     DeviceBuffers buf;
-    buf.reserve(device, sizeof(amp_t) * (cols * k + k * rows + 2 * rows * cols + k * k) + 32 * k + 16384);   // + the Jacobi route's copy
+    buf.reserve(*ctx, sizeof(amp_t) * (cols * k + k * rows + 2 * rows * cols + k * k) + 32 * k + 16384);   // + the Jacobi route's copy
     double *dS = nullptr, *dE = nullptr;
     amp_t *dU = nullptr, *dV = nullptr;
     rocblas_int *dinfo = nullptr;
@@ -1423,19 +1426,26 @@ bool skinny_gemm(hipStream_t stream, bool transpose, bool conjugate, const amp_t
 int panel_orthonormalise(hipStream_t stream, amp_t *Y, uint64_t n, int l, amp_t *partials, amp_t *r_factor,
                          amp_t *r_total, int *flags = nullptr, int rounds = 3) {
     const size_t lds = sizeof(amp_t) * l * PANEL_PITCH;
-    static bool raised = false;
-    if (lds > 64 * 1024 && !raised) {
-        QSV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_panel_gram<1>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(LMAX * PANEL_PITCH * sizeof(amp_t))));
-        QSV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_panel_gram<4>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(LMAX * PANEL_PITCH * sizeof(amp_t))));
-        raised = true;
+    static std::once_flag raised, raised_solve;     // attributes are process-wide: set once, whichever thread comes first
+    static hipError_t raised_status = hipSuccess, raised_solve_status = hipSuccess;
+    if (lds > 64 * 1024) {
+        std::call_once(raised, [] {
+            const int bytes = static_cast<int>(LMAX * PANEL_PITCH * sizeof(amp_t));
+            raised_status = hipFuncSetAttribute(reinterpret_cast<const void *>(k_panel_gram<1>),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+            if (raised_status == hipSuccess)
+                raised_status = hipFuncSetAttribute(reinterpret_cast<const void *>(k_panel_gram<4>),
+                                                    hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        });
+        QSV_HIP(raised_status);
     }
-    static bool raised_solve = false;
-    if (lds + sizeof(amp_t) * l * l > 64 * 1024 && !raised_solve) {
-        QSV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_panel_solve), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    static_cast<int>((LMAX * PANEL_PITCH + LMAX * LMAX) * sizeof(amp_t))));
-        raised_solve = true;
+    if (lds + sizeof(amp_t) * l * l > 64 * 1024) {
+        std::call_once(raised_solve, [] {
+            raised_solve_status = hipFuncSetAttribute(reinterpret_cast<const void *>(k_panel_solve),
+                                                      hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                      static_cast<int>((LMAX * PANEL_PITCH + LMAX * LMAX) * sizeof(amp_t)));
+        });
+        QSV_HIP(raised_solve_status);
     }
     const uint64_t tiles = (n + PANEL_ROWS - 1) / PANEL_ROWS;
     const int gram_blocks = static_cast<int>(tiles < GRAM_BLOCKS ? tiles : GRAM_BLOCKS);
@@ -1562,14 +1572,18 @@ __global__ __launch_bounds__(256) void k_place_block(amp_t *__restrict__ out, in
 int wide_panel_orthonormalise(hipStream_t stream, amp_t *Y, uint64_t n, int l, amp_t *partials, amp_t *scratch,
                               amp_t *r_total, int *flags, int rounds = 3) {
     if (l <= LMAX) return panel_orthonormalise(stream, Y, n, l, partials, scratch, r_total, flags, rounds);
-    static bool raised = false;
-    if (!raised) {
+    static std::once_flag raised;
+    static hipError_t raised_status = hipSuccess;
+    std::call_once(raised, [] {
         const int big = static_cast<int>((2 * LMAX * PANEL_PITCH) * sizeof(amp_t));
-        QSV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_panel_cross), hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        QSV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_panel_update), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    static_cast<int>((LMAX * PANEL_PITCH + LMAX * LMAX) * sizeof(amp_t))));
-        raised = true;
-    }
+        raised_status = hipFuncSetAttribute(reinterpret_cast<const void *>(k_panel_cross),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, big);
+        if (raised_status == hipSuccess)
+            raised_status = hipFuncSetAttribute(reinterpret_cast<const void *>(k_panel_update),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                static_cast<int>((LMAX * PANEL_PITCH + LMAX * LMAX) * sizeof(amp_t)));
+    });
+    QSV_HIP(raised_status);
     amp_t *block_factor = scratch, *cross = scratch + LMAX * LMAX;
     const uint64_t tiles = (n + PANEL_ROWS - 1) / PANEL_ROWS;
     const int red_blocks = static_cast<int>(tiles < GRAM_BLOCKS ? tiles : GRAM_BLOCKS);
@@ -1689,10 +1703,10 @@ struct LowRankCheck {
     std::vector<double> *values;   // out: the kept spectrum padded with zeros to full_rank
 };
 
-int rsvd_split_fused(RocblasApi &a, rocblas_handle h, int device, hipStream_t stream, const amp_t *theta, uint64_t rows,
-                     uint64_t cols, int64_t k_keep, int l, int q, const amp_t *omega, double abs_err, double rel_err,
-                     amp_t *m1, amp_t *m2, uint64_t capacity, uint64_t *rank_out, double *s_host,
-                     const LowRankCheck *verify = nullptr) {
+int rsvd_split_fused(RocblasApi &a, rocblas_handle h, StreamContext &ctx, const amp_t *theta, uint64_t rows, uint64_t cols,
+                     int64_t k_keep, int l, int q, const amp_t *omega, double abs_err, double rel_err, amp_t *m1, amp_t *m2,
+                     uint64_t capacity, uint64_t *rank_out, double *s_host, const LowRankCheck *verify = nullptr) {
+    hipStream_t stream = ctx.stream;
     const bool wide = rows < cols;
     const uint64_t n = wide ? cols : rows, m = wide ? rows : cols;
     const uint64_t L = static_cast<uint64_t>(l);
@@ -1700,7 +1714,7 @@ int rsvd_split_fused(RocblasApi &a, rocblas_handle h, int device, hipStream_t st
     const uint64_t block = L < LMAX ? L : LMAX, scratch_amps = 2 * LMAX * LMAX;
     // the k-range shares of the skinny products: only matrices with few 64-row blocks use them (see skinny_gemm)
     const uint64_t share_amps = n < 256 * 64 ? SKINNY_MAX_SHARES * n * (L < 64 ? L : 64) : 0;
-    buf.reserve(device, sizeof(amp_t) * ((n + m) * (L + static_cast<uint64_t>(k_keep)) + (verify ? n * L : 0) + share_amps +
+    buf.reserve(ctx, sizeof(amp_t) * ((n + m) * (L + static_cast<uint64_t>(k_keep)) + (verify ? n * L : 0) + share_amps +
                                          GRAM_BLOCKS * block * block + scratch_amps + 5 * L * L) + 32 * L + 16384 + 8 * 1024);
     amp_t *Qn = nullptr, *Qm = nullptr, *partials = nullptr, *small = nullptr, *UA = nullptr, *VA = nullptr, *shares = nullptr;
     double *dS = nullptr;
@@ -1883,37 +1897,131 @@ __global__ __launch_bounds__(256) void k_sum_squares(const amp_t *__restrict__ x
     if (threadIdx.x == 0) partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
+// The probe matrices of the verified low-rank route, per device, width and matrix size: they depend only on those (a
+// fixed random stream), so every stream shares them.  (Several sizes per width: the thetas of one MPS alternate between a
+// few shapes -- 1000, 2000, 4000 on the short side in the GKP runs -- and with ONE entry per width every change of shape
+// cost a Box-Muller pass over 10^5 deviates on the host, an allocation and an upload.)  Entries are handed out
+// reference-counted, and an evicted entry is kept in `retired` until qsv_tensor_release_workspace: a split on another
+// stream may still read it, and hipFree would wait for the whole device.
+struct ProbeMatrix {
+    amp_t *omega = nullptr;
+    uint64_t count = 0;
+    ~ProbeMatrix() {
+        if (omega) (void)hipFree(omega);
+    }
+};
+
+struct ProbeCache {
+    static constexpr int SIZES = 8;
+    struct Slot {
+        std::shared_ptr<ProbeMatrix> probes;
+        uint64_t last_use = 0;
+    };
+    std::mutex lock;          // held for lookup and insertion only
+    Slot slots[16][3][SIZES];
+    std::vector<std::shared_ptr<ProbeMatrix>> retired[16];
+    uint64_t use_clock = 0;
+};
+
+ProbeCache &probe_cache() {
+    static ProbeCache *c = new ProbeCache;     // never destroyed: no hipFree after the runtime has gone at exit
+    return *c;
+}
+
+// The (full x l) probe matrix of width index `w` on the context's device, generated and uploaded on the context's stream
+// when no stream has it yet; null when the device memory is not there.
+std::shared_ptr<ProbeMatrix> probes_for(StreamContext &ctx, int w, uint64_t full, int l) {
+    ProbeCache &cache = probe_cache();
+    ProbeCache::Slot *row = cache.slots[ctx.device][w];
+    const uint64_t count = full * static_cast<uint64_t>(l);
+    {
+        std::lock_guard<std::mutex> guard(cache.lock);
+        for (int i = 0; i < ProbeCache::SIZES; ++i)
+            if (row[i].probes && row[i].probes->count == count) {
+                row[i].last_use = ++cache.use_clock;
+                return row[i].probes;
+            }
+    }
+    auto fresh = std::make_shared<ProbeMatrix>();
+    if (hipMalloc(reinterpret_cast<void **>(&fresh->omega), sizeof(amp_t) * count) != hipSuccess) {
+        fresh->omega = nullptr;
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    std::vector<double> host(2 * count, 0.0);
+    uint64_t state = 0x9e3779b97f4a7c15ull + static_cast<uint64_t>(w);   // splitmix64 + Box-Muller: fixed probe matrices
+    auto next = [&]() {
+        state += 0x9e3779b97f4a7c15ull;
+        uint64_t z = state;
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+        return ((z ^ (z >> 31)) >> 11) * (1.0 / 9007199254740992.0);
+    };
+    for (uint64_t i = 0; i < count; ++i) {
+        const double u1 = next() + 1e-300, u2 = next();
+        host[2 * i] = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+    }
+    // complete before it is published (a synchronous copy): other streams may use the entry as soon as it is in the cache
+    if (hipMemcpy(fresh->omega, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    fresh->count = count;
+    std::lock_guard<std::mutex> guard(cache.lock);
+    ProbeCache::Slot *slot = nullptr;
+    for (int i = 0; i < ProbeCache::SIZES; ++i)
+        if (row[i].probes && row[i].probes->count == count) slot = &row[i];      // another stream was quicker: use its copy
+    if (slot) {
+        slot->last_use = ++cache.use_clock;
+        cache.retired[ctx.device].push_back(std::move(fresh));    // never published; freed with the other retired ones
+        return slot->probes;
+    }
+    slot = &row[0];                          // a free entry, or the one that was used longest ago
+    for (int i = 0; i < ProbeCache::SIZES; ++i)
+        if (!row[i].probes) {
+            slot = &row[i];
+            break;
+        } else if (row[i].last_use < slot->last_use) {
+            slot = &row[i];
+        }
+    if (slot->probes) cache.retired[ctx.device].push_back(std::move(slot->probes));
+    slot->probes = fresh;
+    slot->last_use = ++cache.use_clock;
+    return fresh;
+}
+
+// Free the probe matrices evicted on `device` (qsv_tensor_release_workspace, after it has waited for the device).
+int release_retired_probes(int device) {
+    std::vector<std::shared_ptr<ProbeMatrix>> gone;
+    {
+        ProbeCache &cache = probe_cache();
+        std::lock_guard<std::mutex> guard(cache.lock);
+        gone.swap(cache.retired[device]);
+    }
+    gone.clear();
+    return QSV_OK;
+}
+
 // The exact split's shortcut for numerically low-rank theta under a loose tolerance (the regime of the reference's own
 // GKP runs: rel_err = 1e-2, bonds of 1-2 on d = 1000 grids, where LAPACK-style SVDs of 1000..2000-sized matrices are all
 // the time there is): a 64-probe range finder with its own fixed random stream -- the reference's exact branch draws no
 // random numbers, so the caller's generator must not be touched -- verified a posteriori by LowRankCheck.
-int try_verified_low_rank(RocblasApi &a, rocblas_handle h, int device, hipStream_t stream, const amp_t *theta,
-                          uint64_t rows, uint64_t cols, int64_t max_bond_dim, double abs_err, double rel_err, amp_t *m1,
-                          amp_t *m2, uint64_t capacity, uint64_t *rank_out, std::vector<double> *values,
+int try_verified_low_rank(RocblasApi &a, rocblas_handle h, StreamContext &ctx, const amp_t *theta, uint64_t rows,
+                          uint64_t cols, int64_t max_bond_dim, double abs_err, double rel_err, amp_t *m1, amp_t *m2,
+                          uint64_t capacity, uint64_t *rank_out, std::vector<double> *values,
                           double *frobenius_squared_out) {
     const uint64_t full = rows < cols ? rows : cols;
     if (full < 4 * static_cast<uint64_t>(LMAX)) return QSV_UNDECIDED;    // small matrices: the library SVD is cheap
-    // the probe matrices and the norm partials live outside the pool (which rsvd_split_fused carves for itself) and are
-    // kept per device, width and matrix size: the probes depend only on those, so they are generated and uploaded once.
-    // (Several sizes per width: the thetas of one MPS alternate between a few shapes -- 1000, 2000, 4000 on the short side in
-    // the GKP runs -- and with ONE entry per width every change of shape cost a Box-Muller pass over 10^5 deviates on the
-    // host, a synchronising hipFree / hipMalloc and an upload.)
-    struct Probes {
-        amp_t *omega = nullptr;
-        uint64_t count = 0;
-        uint64_t last_use = 0;
-    };
-    constexpr int PROBE_SIZES = 8;
-    static Probes cache_sizes[16][3][PROBE_SIZES];
-    static uint64_t use_clock = 0;
-    static double *norm_partials[16] = {nullptr};
-    if (device < 0 || device >= 16) return QSV_UNDECIDED;  // no probe cache for this ordinal: take the exact route
-    if (!norm_partials[device] &&
-        hipMalloc(reinterpret_cast<void **>(&norm_partials[device]), sizeof(double) * 256) != hipSuccess) {
-        norm_partials[device] = nullptr;
+    // the norm partials live outside the pool (which rsvd_split_fused carves for itself), in the stream's context; the
+    // probe matrices in the cache shared by every stream of the device (probes_for)
+    hipStream_t stream = ctx.stream;
+    if (!ctx.norm_partials &&
+        hipMalloc(reinterpret_cast<void **>(&ctx.norm_partials), sizeof(double) * 256) != hipSuccess) {
+        ctx.norm_partials = nullptr;
+        (void)hipGetLastError();
         return QSV_UNDECIDED;
     }
-    double *partials = norm_partials[device];
+    double *partials = ctx.norm_partials;
     hipLaunchKernelGGL(k_sum_squares, dim3(256), dim3(256), 0, stream, theta, rows * cols, partials);
     QSV_HIP(hipGetLastError());
     double sums[256];
@@ -1934,52 +2042,12 @@ int try_verified_low_rank(RocblasApi &a, rocblas_handle h, int device, hipStream
     for (int w = 0; w < 3; ++w) {
         const int l = widths[w], keep = l - 10;
         if (full < 4 * static_cast<uint64_t>(l)) break;
-        Probes *slot = nullptr;
-        for (Probes &cand : cache_sizes[device][w])
-            if (cand.omega && cand.count == full * l) slot = &cand;
-        if (!slot) {               // a free entry, or the one that was used longest ago
-            slot = &cache_sizes[device][w][0];
-            for (Probes &cand : cache_sizes[device][w])
-                if (!cand.omega) {
-                    slot = &cand;
-                    break;
-                } else if (cand.last_use < slot->last_use) {
-                    slot = &cand;
-                }
-        }
-        Probes &probes = *slot;
-        probes.last_use = ++use_clock;
-        if (probes.count != full * l || !probes.omega) {
-            if (probes.omega) {
-                (void)hipDeviceSynchronize();
-                (void)hipFree(probes.omega);
-                probes.omega = nullptr;
-                probes.count = 0;
-            }
-            if (hipMalloc(reinterpret_cast<void **>(&probes.omega), sizeof(amp_t) * full * l) != hipSuccess) {
-                probes.omega = nullptr;
-                return QSV_UNDECIDED;
-            }
-            std::vector<double> host(2 * full * l, 0.0);
-            uint64_t state = 0x9e3779b97f4a7c15ull + static_cast<uint64_t>(w);   // splitmix64 + Box-Muller: fixed probe matrices
-            auto next = [&]() {
-                state += 0x9e3779b97f4a7c15ull;
-                uint64_t z = state;
-                z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-                z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-                return ((z ^ (z >> 31)) >> 11) * (1.0 / 9007199254740992.0);
-            };
-            for (uint64_t i = 0; i < full * l; ++i) {
-                const double u1 = next() + 1e-300, u2 = next();
-                host[2 * i] = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
-            }
-            QSV_HIP(hipMemcpy(probes.omega, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice));
-            probes.count = full * l;
-        }
+        const std::shared_ptr<ProbeMatrix> probes = probes_for(ctx, w, full, l);
+        if (!probes) return QSV_UNDECIDED;
         // two power iterations: the route is accepted only when the kept values stand 10^2 rho above everything that was
         // missed, and the error of their subspace after q iterations is of order (missed / kept)^(2q+1)
-        const int rc = rsvd_split_fused(a, h, device, stream, theta, rows, cols, keep, l, 2, probes.omega, abs_err, rel_err, m1,
-                                        m2, capacity, rank_out, nullptr, &check);
+        const int rc = rsvd_split_fused(a, h, ctx, theta, rows, cols, keep, l, 2, probes->omega, abs_err, rel_err, m1, m2,
+                                        capacity, rank_out, nullptr, &check);
         if (rc == QSV_OK && values) *values = spectrum;
         if (rc != QSV_UNDECIDED) return rc;
     }
@@ -1997,9 +2065,10 @@ int qsvg_rsvd_split(int device, hipStream_t stream, const amp_t *theta, uint64_t
     const uint64_t lim = 0x7fffffffull;
     if (rows > lim || cols > lim) return qsv_fail(QSV_EINVAL, "matrix dimension exceeds 2^31 - 1");
     RocblasApi &a = api();
-    std::lock_guard<std::mutex> guard(a.lock);
     int rc;
-    rocblas_handle h = handle_for(a, device, stream, &rc);
+    StreamContext *ctx = context_for(device, stream, &rc);
+    if (!ctx) return rc;
+    rocblas_handle h = handle_of(*ctx, &rc);
     if (!h) return rc;
     if (!a.zgesvd || !a.zgeqrf || !a.zungqr)
         return qsv_fail(QSV_EHIP, "rocSOLVER could not be loaded (librocsolver.so.0): no SVD available");
@@ -2009,7 +2078,7 @@ int qsvg_rsvd_split(int device, hipStream_t stream, const amp_t *theta, uint64_t
     if (k_keep < 1 || L < static_cast<uint64_t>(k_keep) || L > m)
         return qsv_fail(QSV_EINVAL, "need 1 <= k <= l <= min(rows, cols)");
     if (omega && L <= LMAX && fused_panels_enabled())
-        return rsvd_split_fused(a, h, device, stream, theta, rows, cols, k_keep, l, q, omega, abs_err, rel_err, m1, m2, capacity,
+        return rsvd_split_fused(a, h, *ctx, theta, rows, cols, k_keep, l, q, omega, abs_err, rel_err, m1, m2, capacity,
                                 rank_out, s_host);
     // More probes than the fused kernels take (max_bond_dim > 54, e.g. the 100 of the reference's GKP runs).  Under a
     // loose tolerance the kept rank is far below that anyway: the verified low-rank route decides it with 64 probes of
@@ -2020,15 +2089,14 @@ int qsvg_rsvd_split(int device, hipStream_t stream, const amp_t *theta, uint64_t
         return !(v && std::string(v) == "exact");
     }();
     // A caller that came without its test matrix, was asked for it and is back with it (same theta, untouched in between)
-    // has had its verified attempts already: do not repeat them.
-    static const amp_t *asked_theta = nullptr;
-    static uint64_t asked_rows = 0, asked_cols = 0;
-    const bool back_with_omega = omega && asked_theta == theta && asked_rows == rows && asked_cols == cols;
-    asked_theta = nullptr;
+    // has had its verified attempts already: do not repeat them.  (The memo is the stream's: the second call comes on
+    // the stream of the first.)
+    const bool back_with_omega = omega && ctx->asked_theta == theta && ctx->asked_rows == rows && ctx->asked_cols == cols;
+    ctx->asked_theta = nullptr;
     if (!back_with_omega && L > LMAX && shortcuts_enabled && fused_panels_enabled() && (rel_err >= 1e-4 || abs_err > 0.0)) {
         std::vector<double> values;
-        const int fast = try_verified_low_rank(a, h, device, stream, theta, rows, cols, k_keep, abs_err, rel_err, m1, m2,
-                                               capacity, rank_out, s_host ? &values : nullptr);
+        const int fast = try_verified_low_rank(a, h, *ctx, theta, rows, cols, k_keep, abs_err, rel_err, m1, m2, capacity,
+                                               rank_out, s_host ? &values : nullptr);
         if (fast == QSV_OK) {
             if (s_host)
                 for (int64_t i = 0; i < k_keep; ++i) s_host[i] = values[static_cast<size_t>(i)];
@@ -2037,17 +2105,17 @@ int qsvg_rsvd_split(int device, hipStream_t stream, const amp_t *theta, uint64_t
         if (fast != QSV_UNDECIDED) return fast;
     }
     if (!omega) {      // the caller has not drawn the test matrix yet (it costs more than the route above): ask for it
-        asked_theta = theta;
-        asked_rows = rows;
-        asked_cols = cols;
+        ctx->asked_theta = theta;
+        ctx->asked_rows = rows;
+        ctx->asked_cols = cols;
         *rank_out = QSV_RANK_NEEDS_OMEGA;
         return QSV_OK;
     }
     if (L <= WIDE_MAX && fused_panels_enabled())      // 64-column blocks of probes, library SVD of the projected factor
-        return rsvd_split_fused(a, h, device, stream, theta, rows, cols, k_keep, l, q, omega, abs_err, rel_err, m1, m2, capacity,
+        return rsvd_split_fused(a, h, *ctx, theta, rows, cols, k_keep, l, q, omega, abs_err, rel_err, m1, m2, capacity,
                                 rank_out, s_host);
     DeviceBuffers buf;
-    buf.reserve(device, sizeof(amp_t) * ((n + m) * L + L + L * m + L * kk + kk * m + n * static_cast<uint64_t>(k_keep) +
+    buf.reserve(*ctx, sizeof(amp_t) * ((n + m) * L + L + L * m + L * kk + kk * m + n * static_cast<uint64_t>(k_keep) +
                                          (wide ? 0 : n * m)) + 16 * kk + 8192);
     amp_t *A = nullptr, *Qn = nullptr, *Qm = nullptr, *tau = nullptr, *B = nullptr, *UB = nullptr, *VB = nullptr;
     double *dS = nullptr, *dE = nullptr;

@@ -13,6 +13,8 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -26,22 +28,23 @@ RocblasApi &api() {
     return a;
 }
 
-bool load_locked(RocblasApi &a) {
-    if (a.tried) return a.ok;
-    a.tried = true;
+namespace {
+
+void load_libraries(RocblasApi &a) {
     const char *off = std::getenv("QSV_NO_ROCBLAS");
-    if (off && off[0] == '1') return false;
+    if (off && off[0] == '1') return;
     void *lib = nullptr;
     for (const char *name : {"librocblas.so.5", "librocblas.so", "/opt/rocm/lib/librocblas.so.5",
                              "/opt/rocm/lib/librocblas.so"}) {
         lib = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
         if (lib) break;
     }
-    if (!lib) return false;
+    if (!lib) return;
     a.create = reinterpret_cast<decltype(a.create)>(dlsym(lib, "rocblas_create_handle"));
+    a.destroy = reinterpret_cast<decltype(a.destroy)>(dlsym(lib, "rocblas_destroy_handle"));
     a.set_stream = reinterpret_cast<decltype(a.set_stream)>(dlsym(lib, "rocblas_set_stream"));
     a.zgemm = reinterpret_cast<decltype(a.zgemm)>(dlsym(lib, "rocblas_zgemm_strided_batched"));
-    a.ok = a.create && a.set_stream && a.zgemm;
+    a.ok = a.create && a.destroy && a.set_stream && a.zgemm;
     if (a.ok) {
         void *solver = nullptr;
         for (const char *name : {"librocsolver.so.0", "librocsolver.so", "/opt/rocm/lib/librocsolver.so.0",
@@ -56,40 +59,122 @@ bool load_locked(RocblasApi &a) {
             a.zungqr = reinterpret_cast<decltype(a.zungqr)>(dlsym(solver, "rocsolver_zungqr"));
         }
     }
+}
+
+// The contexts of every (device, stream) seen so far.  Allocated once and never destroyed: a static destructor would
+// free device memory after the HIP runtime has gone at process exit.
+struct ContextMap {
+    std::mutex lock;          // held for lookup, insertion and removal only -- never across HIP or library calls
+    std::map<std::pair<int, hipStream_t>, std::unique_ptr<StreamContext>> contexts;
+};
+
+ContextMap &context_map() {
+    static ContextMap *m = new ContextMap;
+    return *m;
+}
+
+// Give the context's device memory back (hipFree: waits for the whole device); every pointer is freed even after an
+// error, which is reported afterwards.  The caller has waited for the context's stream.
+int free_memory(StreamContext &ctx) {
+    hipError_t first = hipSuccess;
+    auto release = [&first](void *p) {
+        if (!p) return;
+        const hipError_t e = hipFree(p);
+        if (first == hipSuccess) first = e;
+    };
+    release(ctx.pool.base);
+    ctx.pool = Pool{};
+    for (char *p : ctx.retired) release(p);
+    ctx.retired.clear();
+    release(ctx.norm_partials);
+    ctx.norm_partials = nullptr;
+    QSV_HIP(first);
+    return QSV_OK;
+}
+
+// Wait for the context's stream, then give its handle and memory back.  The context is out of the map already, so
+// nothing is left behind on an error: everything is released and the first failure reported.
+int free_context(StreamContext &ctx) {
+    QSV_HIP(hipSetDevice(ctx.device));
+    const hipError_t waited = hipStreamSynchronize(ctx.stream);
+    if (ctx.handle) (void)api().destroy(ctx.handle);
+    ctx.handle = nullptr;
+    const int freed = free_memory(ctx);
+    QSV_HIP(waited);
+    return freed;
+}
+
+}  // namespace
+
+bool loaded(RocblasApi &a) {
+    std::call_once(a.once, [&a] { load_libraries(a); });
     return a.ok;
 }
 
-// Handle of `device` bound to `stream`, or null (and *rc set) when the libraries cannot be used.
-rocblas_handle handle_for(RocblasApi &a, int device, hipStream_t stream, int *rc) {
+StreamContext *context_for(int device, hipStream_t stream, int *rc) {
     *rc = QSV_OK;
     if (device < 0 || device >= 16) {
         *rc = qsv_fail(QSV_EINVAL, "device index out of range");
         return nullptr;
     }
-    if (!load_locked(a)) {
+    const hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) {
+        *rc = qsv_fail(QSV_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+        return nullptr;
+    }
+    ContextMap &m = context_map();
+    std::lock_guard<std::mutex> guard(m.lock);
+    std::unique_ptr<StreamContext> &slot = m.contexts[{device, stream}];
+    if (!slot) {
+        slot.reset(new StreamContext);
+        slot->device = device;
+        slot->stream = stream;
+    }
+    return slot.get();
+}
+
+rocblas_handle handle_of(StreamContext &ctx, int *rc) {
+    *rc = QSV_OK;
+    if (ctx.handle) return ctx.handle;
+    RocblasApi &a = api();
+    if (!loaded(a)) {
         *rc = qsv_fail(QSV_EHIP, "rocBLAS could not be loaded (librocblas.so.5): tensor-network entry points need it");
         return nullptr;
     }
-    if (!a.handle[device] && a.create(&a.handle[device]) != rocblas_status_success) {
-        a.handle[device] = nullptr;
+    rocblas_handle h = nullptr;
+    if (a.create(&h) != rocblas_status_success) {
         *rc = qsv_fail(QSV_EHIP, "rocblas_create_handle failed");
         return nullptr;
     }
-    if (a.set_stream(a.handle[device], stream) != rocblas_status_success) {
+    if (a.set_stream(h, ctx.stream) != rocblas_status_success) {
+        (void)a.destroy(h);
         *rc = qsv_fail(QSV_EHIP, "rocblas_set_stream failed");
         return nullptr;
     }
-    return a.handle[device];
+    ctx.handle = h;
+    return h;
+}
+
+int reserve_pool(StreamContext &ctx, size_t bytes) {
+    Pool &pool = ctx.pool;
+    if (pool.capacity >= bytes) return QSV_OK;
+    // The old block is retired, not freed: hipFree would wait for every stream of the device.  (It may still be read by
+    // a call that returned early on an error; it is freed when the context is released, after its stream is done.)
+    const size_t want = bytes + bytes / 8;
+    char *fresh = nullptr;
+    if (hipMalloc(reinterpret_cast<void **>(&fresh), want) != hipSuccess) {
+        (void)hipGetLastError();
+        return QSV_ENOMEM;
+    }
+    if (pool.base) ctx.retired.push_back(pool.base);
+    pool.base = fresh;
+    pool.capacity = want;
+    return QSV_OK;
 }
 
 rocblas_operation op_of(int op) {
     return op == 0 ? rocblas_operation_none : op == 1 ? rocblas_operation_transpose
                                                       : rocblas_operation_conjugate_transpose;
-}
-
-Pool &pool_of(int device) {
-    static Pool pools[16];
-    return pools[device];
 }
 
 }  // namespace qsvl
@@ -143,9 +228,10 @@ int qsvg_gemm(int device, hipStream_t stream, int op_a, int op_b, uint64_t m, ui
         return QSV_OK;
     }
     RocblasApi &a = api();
-    std::lock_guard<std::mutex> guard(a.lock);
     int rc;
-    rocblas_handle h = handle_for(a, device, stream, &rc);
+    StreamContext *ctx = context_for(device, stream, &rc);
+    if (!ctx) return rc;
+    rocblas_handle h = handle_of(*ctx, &rc);
     if (!h) return rc;
     const rocblas_double_complex one{1.0, 0.0}, zero{0.0, 0.0};
     const rocblas_int lda = static_cast<rocblas_int>(op_a == 0 ? k : m);   // columns of the row-major A buffer
@@ -165,17 +251,12 @@ int qsvg_axis_gemm(int device, hipStream_t stream, const amp_t *in, amp_t *out, 
     const uint64_t lim = 0x7fffffffull;
     if (device < 0 || device >= 16 || d_in > lim || d_out > lim || R > lim || L > lim) return 0;
     RocblasApi &a = api();
-    std::lock_guard<std::mutex> guard(a.lock);
-    if (!load_locked(a)) return 0;
-    if (!a.handle[device]) {
-        if (a.create(&a.handle[device]) != rocblas_status_success) {
-            a.handle[device] = nullptr;
-            a.ok = false;
-            return 0;
-        }
-    }
-    rocblas_handle h = a.handle[device];
-    if (a.set_stream(h, stream) != rocblas_status_success) return qsv_fail(QSV_EHIP, "rocblas_set_stream failed");
+    if (!loaded(a)) return 0;
+    int rc;
+    StreamContext *ctx = context_for(device, stream, &rc);
+    if (!ctx) return 0;
+    rocblas_handle h = handle_of(*ctx, &rc);
+    if (!h) return 0;                 // no handle: the caller takes its own kernels, as before
     const rocblas_double_complex one{1.0, 0.0}, zero{0.0, 0.0};
     const auto *A = reinterpret_cast<const rocblas_double_complex *>(in);
     const auto *M = reinterpret_cast<const rocblas_double_complex *>(dev_m);
@@ -200,18 +281,49 @@ int qsvg_axis_gemm(int device, hipStream_t stream, const amp_t *in, amp_t *out, 
     return 1;
 }
 
-// Give the decomposition scratch pool of `device` back to the driver (it is re-grown on demand).
+// Give the scratch memory of every context of `device` back to the driver (pools are re-grown on demand; the contexts
+// and their rocBLAS handles stay), and the probe matrices the low-rank route has evicted.  Waits for the whole device:
+// no other stream of the device may be working in the library meanwhile.
 int qsvg_release_workspace(int device) {
     if (device < 0 || device >= 16) return qsv_fail(QSV_EINVAL, "device index out of range");
-    RocblasApi &a = api();
-    std::lock_guard<std::mutex> guard(a.lock);
-    Pool &pool = pool_of(device);
-    if (pool.base) {
-        QSV_HIP(hipSetDevice(device));
-        QSV_HIP(hipDeviceSynchronize());
-        QSV_HIP(hipFree(pool.base));
-        pool.base = nullptr;
-        pool.capacity = 0;
+    std::vector<StreamContext *> mine;
+    {
+        ContextMap &m = context_map();
+        std::lock_guard<std::mutex> guard(m.lock);
+        for (auto &entry : m.contexts)
+            if (entry.first.first == device) mine.push_back(entry.second.get());
     }
-    return QSV_OK;
+    QSV_HIP(hipSetDevice(device));
+    QSV_HIP(hipDeviceSynchronize());
+    int first = release_retired_probes(device);
+    for (StreamContext *ctx : mine) {
+        const int rc = free_memory(*ctx);
+        if (first == QSV_OK) first = rc;
+    }
+    return first;
+}
+
+// Give the context of one (device, stream) back, after waiting for that stream alone.
+int qsvg_release_stream_workspace(int device, hipStream_t stream) {
+    if (device < 0 || device >= 16) return qsv_fail(QSV_EINVAL, "device index out of range");
+    std::unique_ptr<StreamContext> gone;
+    {
+        ContextMap &m = context_map();
+        std::lock_guard<std::mutex> guard(m.lock);
+        auto it = m.contexts.find({device, stream});
+        if (it == m.contexts.end()) return QSV_OK;
+        gone = std::move(it->second);
+        m.contexts.erase(it);
+    }
+    return free_context(*gone);
+}
+
+// Pre-size the pool of one (device, stream) context, so that the calls of a batch never grow it mid-flight.
+int qsvg_reserve_workspace(int device, hipStream_t stream, uint64_t bytes) {
+    int rc;
+    StreamContext *ctx = context_for(device, stream, &rc);
+    if (!ctx) return rc;
+    rc = reserve_pool(*ctx, static_cast<size_t>(bytes));
+    if (rc == QSV_ENOMEM) return qsv_fail(QSV_ENOMEM, "device allocation of the tensor workspace failed");
+    return rc;
 }

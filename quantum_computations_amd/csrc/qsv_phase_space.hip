@@ -288,12 +288,12 @@ int qsv_tensor_wigner(int device, void *hip_stream, const void *dev_rho, int bat
     const size_t total = pad(bytes_q) + pad(bytes_p) + pad(bytes_scale) + pad(bytes_g) + pad(bytes_a) + pad(bytes_e) +
                          pad(bytes_b);
 
-    RocblasApi &a = api();
-    std::lock_guard<std::mutex> guard(a.lock);
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    QSV_HIP(hipSetDevice(device));
+    int rc;
+    StreamContext *ctx = context_for(device, stream, &rc);
+    if (!ctx) return rc;
     DeviceBuffers buf;
-    buf.reserve(device, total);
+    buf.reserve(*ctx, total);
     double *dq, *dp, *dscale, *dg = nullptr, *da, *de, *db;
     if (!buf.alloc(&dq, bytes_q) || !buf.alloc(&dp, bytes_p) || !buf.alloc(&dscale, bytes_scale) ||
         (!half_grid && !buf.alloc(&dg, bytes_g)) || !buf.alloc(&da, bytes_a) || !buf.alloc(&de, bytes_e) ||
@@ -303,7 +303,6 @@ int qsv_tensor_wigner(int device, void *hip_stream, const void *dev_rho, int bat
     QSV_HIP(hipMemcpyAsync(dp, p, bytes_p, hipMemcpyHostToDevice, stream));
 
     const amp_t *rho = static_cast<const amp_t *>(dev_rho);
-    int rc;
     hipLaunchKernelGGL(k_wigner_scale, dim3(static_cast<unsigned>(B)), dim3(256), 0, stream, rho, d, dx, normalised, dscale);
     if ((rc = check_launch()) != QSV_OK) return rc;
     hipLaunchKernelGGL(k_phase_table, dim3(grid_for(d * np_)), dim3(256), 0, stream, dp, np_, d, x0, dx, de);
@@ -338,15 +337,15 @@ int qsv_tensor_axis_density(int device, void *hip_stream, const void *dev_z, con
     const uint64_t lim = 0x7fffffffull;
     if (d > lim || L * R > lim) return qsv_fail(QSV_EINVAL, "tensor too large");
     RocblasApi &a = api();
-    std::lock_guard<std::mutex> guard(a.lock);
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     int rc;
-    rocblas_handle h = handle_for(a, device, stream, &rc);
+    StreamContext *ctx = context_for(device, stream, &rc);
+    if (!ctx) return rc;
+    rocblas_handle h = handle_of(*ctx, &rc);
     if (!h) return rc;
-    QSV_HIP(hipSetDevice(device));
     const size_t bytes = L * d * R * 16;
     DeviceBuffers buf;
-    buf.reserve(device, 2 * ((bytes + 255) / 256 * 256));
+    buf.reserve(*ctx, 2 * ((bytes + 255) / 256 * 256));
     amp_t *zf, *tf;
     if (!buf.alloc(&zf, bytes) || !buf.alloc(&tf, bytes)) return qsv_fail(QSV_ENOMEM, "workspace allocation failed");
     const unsigned grid = grid_for(L * d * R);

@@ -20,6 +20,7 @@ Constructor signatures, ``repr`` strings, sign conventions (index order, ``dagge
 from __future__ import annotations
 
 import logging
+import threading
 from collections import OrderedDict
 
 import numpy as np
@@ -41,21 +42,29 @@ def _truncation(gate, mps, rng=None) -> dict:
 
 _OPERATORS: "OrderedDict[tuple, object]" = OrderedDict()      # host operators shared by equal gates (LRU)
 _OPERATORS_KEPT = 16
+_OPERATORS_LOCK = threading.Lock()        # simulations on worker threads share the cache (concurrent.map_on_streams)
 
 
 def _cached(gate, name: str, domain: np.ndarray, build):
     """Host operators depend only on the gate's class, parameters and the grid: build once and hand every equal gate
     the same array object (which the registers keep resident on the device), so that a circuit of many ``F`` /
-    ``X(sqrt(pi))`` gates pays for the ``d x d`` matrix once."""
+    ``X(sqrt(pi))`` gates pays for the ``d x d`` matrix once.  Thread-safe: the lookup and the insertion hold the lock,
+    the build does not (two threads may build the same operator; the first one stored is the one both get)."""
     key = (type(gate).__name__, name, repr(gate.arg), bool(gate.dagger), getattr(gate, "angle", None),
            getattr(gate, "index1", 0) < getattr(gate, "index2", 1), float(domain[0]), float(domain[-1]), len(domain))
-    if key in _OPERATORS:
-        _OPERATORS.move_to_end(key)
-    else:
-        _OPERATORS[key] = build()
+    with _OPERATORS_LOCK:
+        if key in _OPERATORS:
+            _OPERATORS.move_to_end(key)
+            return _OPERATORS[key]
+    built = build()
+    with _OPERATORS_LOCK:
+        if key in _OPERATORS:
+            _OPERATORS.move_to_end(key)
+            return _OPERATORS[key]
+        _OPERATORS[key] = built
         while len(_OPERATORS) > _OPERATORS_KEPT:
             _OPERATORS.popitem(last=False)
-    return _OPERATORS[key]
+        return built
 
 
 def _pi_fraction(angle: float) -> str:

@@ -92,7 +92,8 @@ class MPS:
         """Host copy of site ``index`` (or of a slice of sites)."""
         self._sites_only("indexing")
         picked = self.reg.sites[index]
-        return [t.cpu().numpy() for t in picked] if isinstance(index, slice) else picked.cpu().numpy()
+        with self.reg.stream_context():
+            return [t.cpu().numpy() for t in picked] if isinstance(index, slice) else picked.cpu().numpy()
 
     def __setitem__(self, index: int, tensor: np.ndarray) -> None:
         """Replace site ``index`` (uploaded; shapes are the caller's responsibility until :meth:`validate`)."""
@@ -196,7 +197,8 @@ class MPS:
         modes = [int(axis) for axis in modes]
         if self.layout == "sites":
             rho = self.reg.reduced_density_device(modes)
-            w = wigner_device(rho, self.domain, q, p, normalised=normalised)
+            with self.reg.stream_context():
+                w = wigner_device(rho, self.domain, q, p, normalised=normalised)
             if not normalised:
                 w *= self.diff ** (len(self) - 1)
         else:

@@ -59,6 +59,15 @@ class Simulator:
         if logger.isEnabledFor(logging.DEBUG):
             self.debug_info(self)
 
+    @staticmethod
+    def run_batch(simulators, initial_states, **kw) -> list:
+        """``[s.run(x) for s, x in zip(simulators, initial_states)]``, up to ``max_concurrent`` runs at a time, each on
+        a worker thread with a HIP stream of its own (``quantum_computations_amd.concurrent.map_on_streams``; ``kw``
+        goes there).  The initial registers are adopted onto their job's stream; every simulator keeps its own
+        generator, so a seeded run draws what it draws alone.  A failing run is re-raised after the others finish."""
+        from ..concurrent import run_simulators
+        return run_simulators(simulators, initial_states, **kw)
+
     def run(self, initial_state: MPS) -> MPS:
         initial_state.validate()
         self._state, self.results = initial_state, []

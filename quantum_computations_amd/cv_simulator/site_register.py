@@ -24,10 +24,16 @@ register; the truncation keywords of the gates (``max_bond_dim``, ``abs_err``, `
 Like the reference, the split is exact (rocSOLVER ``zgesvd``) unless ``max_bond_dim * 10 < min(matrix shape)``, where it
 switches to the randomized range finder of ``mps.py:5-50`` (``qsv_tensor_rsvd_split``: GEMMs + Householder QR + a small
 SVD), fed with the same Gaussian test matrix a seeded reference run would draw.
+
+A register works on torch's current stream unless it is given one (``stream=`` or :meth:`SiteRegister.adopt_stream`);
+then every launch, allocation and wait of the register goes to that stream, so that independent registers run side by
+side on their own streams (``quantum_computations_amd.concurrent``).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import functools
 from collections import OrderedDict
 from concurrent.futures import ThreadPoolExecutor
 
@@ -36,7 +42,6 @@ import numpy as np
 from .. import _lib
 
 OP_NONE, OP_TRANSPOSE, OP_CONJ_TRANSPOSE = 0, 1, 2
-_DRAW_POOL = ThreadPoolExecutor(max_workers=1, thread_name_prefix="qsv-omega")     # see SiteRegister._split
 
 
 _TORCH = None
@@ -53,14 +58,30 @@ def _torch():
     return _TORCH
 
 
+def _on_stream(method):
+    """Run ``method`` with the register's own stream as torch's current stream (when it has one), so that torch's
+    allocations, copies and read-backs are ordered with the register's launches."""
+    @functools.wraps(method)
+    def wrapper(self, *args, **kwargs):
+        if self.stream is None:
+            return method(self, *args, **kwargs)
+        with self.stream_context():
+            return method(self, *args, **kwargs)
+    return wrapper
+
+
 class SiteRegister:
     layout = "sites"
 
-    def __init__(self, sites: list[np.ndarray], d: int, device: int = 0):
+    def __init__(self, sites: list[np.ndarray], d: int, device: int = 0, stream=None):
+        """``stream``: a ``torch.cuda.Stream`` of ``device`` this register works on; None = torch's current stream at
+        each call (the default)."""
         torch = _torch()
         self.device = int(device)
         self._dev = torch.device("cuda", self.device)
         self.d = int(d)
+        self.stream = stream
+        self._draw_pool: ThreadPoolExecutor | None = None            # see _split: one helper thread per register
         self.sites = [self._upload(np.asarray(s).reshape(1, -1, 1) if np.ndim(s) == 1 else s) for s in sites]
         self._resident: OrderedDict[int, tuple] = OrderedDict()    # host operator id -> (host array, device copy)
         self._scratch_buffers: dict = {}
@@ -68,6 +89,7 @@ class SiteRegister:
         self.split_counts = {"exact": 0, "randomized": 0}          # which branch of tensor_svd the splits took
 
     # ---- plumbing ----------------------------------------------------------------------------------------
+    @_on_stream
     def _upload(self, array, dtype=np.complex128):
         torch = _torch()
         host = np.ascontiguousarray(array, dtype=dtype)
@@ -75,10 +97,12 @@ class SiteRegister:
             host = host.copy()          # torch.from_numpy insists on a writable buffer (cached read-only operators)
         return torch.from_numpy(host).to(self._dev)
 
+    @_on_stream
     def _empty(self, *shape):
         torch = _torch()
         return torch.empty(shape, dtype=torch.complex128, device=self._dev)
 
+    @_on_stream
     def _scratch(self, slot: str, *shape):
         """A complex128 tensor of ``shape`` carved from this register's persistent scratch buffer ``slot`` (grow-only).
         The two-site temporaries (theta, its mapped image, the capacity-sized split outputs) are gigabytes at the
@@ -93,9 +117,15 @@ class SiteRegister:
             self._scratch_buffers[slot] = held
         return held[:count].view(*shape)
 
+    def stream_context(self):
+        """Context manager that makes the register's stream torch's current one (nothing to do without one)."""
+        return _torch().cuda.stream(self.stream) if self.stream is not None else contextlib.nullcontext()
+
+    def _torch_stream(self):
+        return self.stream if self.stream is not None else _torch().cuda.current_stream(self._dev)
+
     def _stream(self) -> C.c_void_p:
-        torch = _torch()
-        return C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
+        return C.c_void_p(self._torch_stream().cuda_stream)
 
     def _keep(self, host: np.ndarray, dtype=np.complex128):
         """Device copy of a host operator, cached while the caller keeps handing in the same array object."""
@@ -132,23 +162,53 @@ class SiteRegister:
         return tuple(tuple(int(x) for x in s.shape) for s in self.sites)
 
     def sync(self) -> None:
-        _torch().cuda.synchronize(self._dev)
+        """Wait for the register's stream (not the whole device: other registers may be working on theirs)."""
+        self._torch_stream().synchronize()
 
     def close(self) -> None:
+        """Drop the site tensors and give the library's scratch memory back: the context of the register's own stream
+        when it has one (other streams keep working), otherwise every context of the device."""
         self.sites = []
         self._resident.clear()
         self._scratch_buffers.clear()
-        _lib.call("qsv_tensor_release_workspace", self.device)
+        if self._draw_pool is not None:
+            self._draw_pool.shutdown(wait=True)
+            self._draw_pool = None
+        if self.stream is not None:
+            _lib.call("qsv_tensor_release_stream_workspace", self.device, self._stream())
+        else:
+            _lib.call("qsv_tensor_release_workspace", self.device)
 
+    def adopt_stream(self, stream, source=None) -> None:
+        """Move the register to ``stream`` (e.g. built by ``parse_to_mps`` on the main thread, run on a worker's stream).
+        ``stream`` waits for what is queued on ``source`` -- the stream the register's tensors were made on; default:
+        the register's own stream, or torch's current stream of the calling thread -- and every device tensor the
+        register holds is marked as used on ``stream``: otherwise torch's caching allocator could hand a freed site's
+        block back to ``source`` while ``stream`` still reads it.  From then on the register owns ``stream``: ``close``
+        releases that stream's library context only."""
+        torch = _torch()
+        old = source if source is not None else self._torch_stream()
+        if stream != old:
+            ready = torch.cuda.Event()
+            ready.record(old)
+            stream.wait_event(ready)
+            held = list(self.sites) + list(self._scratch_buffers.values()) + [dev for _, dev in self._resident.values()]
+            for t in held:
+                t.record_stream(stream)
+        self.stream = stream
+
+    @_on_stream
     def copy(self) -> "SiteRegister":
-        out = SiteRegister([], self.d, self.device)
+        out = SiteRegister([], self.d, self.device, stream=self.stream)
         out.sites = [s.clone() for s in self.sites]     # device-to-device copies
         return out
 
+    @_on_stream
     def site_arrays(self) -> list[np.ndarray]:
         """The site tensors on the host (``MPS.tensors`` of the reference)."""
         return [s.cpu().numpy() for s in self.sites]
 
+    @_on_stream
     def to_numpy(self) -> np.ndarray:
         """Contract the chain on the device (``MPS.contract``, mps.py:163-164) and download ``psi[q_0, ..., q_{m-1}]``."""
         if not self.sites:
@@ -181,6 +241,7 @@ class SiteRegister:
             r = self._gemm(y, OP_NONE, t, OP_CONJ_TRANSPOSE, cl, cl, d * cr)          # right'[i, j]
         return r
 
+    @_on_stream
     def norm2(self) -> float:
         g = self._left_environment(len(self.sites))
         return float(g.cpu().numpy()[0, 0].real)
@@ -193,6 +254,7 @@ class SiteRegister:
         w = self._gemm(t, OP_NONE, r, OP_NONE, cl * d, cr, cr)
         return self._gemm(g, OP_CONJ_TRANSPOSE, w, OP_NONE, cl, d * cr, cl), t
 
+    @_on_stream
     def marginal(self, axis: int) -> np.ndarray:
         """``sum over the other modes of |psi|^2`` per grid point of mode ``axis`` (no grid-measure factors)."""
         torch = _torch()
@@ -202,6 +264,7 @@ class SiteRegister:
         _lib.call("qsv_tensor_axis_overlap", self.device, self._stream(), self._p(z), self._p(t), cl, d, cr, self._p(out))
         return out.cpu().numpy()
 
+    @_on_stream
     def reduced_density(self, axis: int) -> np.ndarray:
         """Full ``(d, d)`` reduced density matrix (mps.py:176-190): environments on the device, the last small
         contraction on the host."""
@@ -209,6 +272,7 @@ class SiteRegister:
         host_t = t.cpu().numpy()
         return np.einsum("bid,bjd -> ij", z.cpu().numpy().reshape(host_t.shape), np.conj(host_t), optimize=True)
 
+    @_on_stream
     def reduced_density_device(self, axes) -> "torch.Tensor":
         """Reduced density matrices of the sites ``axes`` as one device tensor ``(len(axes), d, d)`` (no grid-measure
         factors): :meth:`reduced_density` with the last contraction on the GPU too (``qsv_tensor_axis_density``: the
@@ -224,6 +288,7 @@ class SiteRegister:
         return out
 
     # ---- gates ------------------------------------------------------------------------------------------------
+    @_on_stream
     def apply_mode(self, operator: np.ndarray, mode: int) -> None:
         t = self.sites[mode]
         cl, d, cr = (int(x) for x in t.shape)
@@ -243,6 +308,7 @@ class SiteRegister:
         theta = self._gemm(a, OP_NONE, b, OP_NONE, cl * d, d * cr, chi, scratch="theta")
         return theta, cl, d, cr
 
+    @_on_stream
     def _split(self, theta, rows: int, cols: int, *, max_bond_dim=np.inf, abs_err: float = 0, rel_err: float = 1e-12,
                rng_seed=None):
         """``tensor_svd`` (mps.py:52-97) of the device matrix ``theta``: exact SVD, or -- exactly when the reference does,
@@ -264,7 +330,9 @@ class SiteRegister:
             # the conversion and upload wait for the library to ask; a seed or None creates a generator nobody else sees,
             # and the draw itself waits too.
             draw = lambda: np.random.default_rng(rng_seed).normal(0, 1, size=(full, probes))
-            pending = _DRAW_POOL.submit(draw) if isinstance(rng_seed, np.random.Generator) else None
+            if isinstance(rng_seed, np.random.Generator) and self._draw_pool is None:
+                self._draw_pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="qsv-omega")
+            pending = self._draw_pool.submit(draw) if isinstance(rng_seed, np.random.Generator) else None
             dev_omega = None
             try:
                 for attempt in range(2):
@@ -296,6 +364,7 @@ class SiteRegister:
         self.sites[left] = m1.reshape(cl, self.d, r)
         self.sites[left + 1] = m2.reshape(r, self.d, cr)
 
+    @_on_stream
     def apply_two_mode(self, plane: np.ndarray, mode0: int, mode1: int, **truncation) -> None:
         """``theta[a, j, l, b] *= plane[j, l]`` (legs in the order ``mode0, mode1``), then split: CZ (gates.py:151-163)."""
         left = min(mode0, mode1)
@@ -307,6 +376,7 @@ class SiteRegister:
         m1, m2, r = self._split(theta, cl * d, d * cr, **truncation)
         self._store_pair(left, m1, m2, cl, cr, r)
 
+    @_on_stream
     def apply_two_mode_gather(self, cols: np.ndarray, weights: np.ndarray, mode0: int, mode1: int, **truncation) -> None:
         """Resample every ``(q_left, q_right)`` plane of theta with the row-sparse table, then split: BS, CX
         (gates.py:58-84,166-192) and SWAP (gates.py:48-55; the table is the transposition)."""
@@ -323,6 +393,7 @@ class SiteRegister:
         m1, m2, r = self._split(mapped, cl * d, d * cr, **truncation)
         self._store_pair(left, m1, m2, cl, cr, r)
 
+    @_on_stream
     def apply_plane_phase(self, grid: np.ndarray, strength: float, left: int, **truncation) -> None:
         """CZ with the phases ``exp(i strength q_j q_l)`` evaluated in the kernel (no ``(d, d)`` table)."""
         theta, cl, d, cr = self._two_site(left)
@@ -331,6 +402,7 @@ class SiteRegister:
         m1, m2, r = self._split(theta, cl * d, d * cr, **truncation)
         self._store_pair(left, m1, m2, cl, cr, r)
 
+    @_on_stream
     def apply_plane_affine(self, grid: np.ndarray, coefficients, left: int, **truncation) -> None:
         """BS / CX: resample every plane at ``(a00 x + a01 y, a10 x + a11 y)``, bilinear, computed in the kernel."""
         theta, cl, d, cr = self._two_site(left)
@@ -341,6 +413,7 @@ class SiteRegister:
         m1, m2, r = self._split(mapped, cl * d, d * cr, **truncation)
         self._store_pair(left, m1, m2, cl, cr, r)
 
+    @_on_stream
     def project(self, mode: int, level: int, scale: float) -> None:
         """Keep grid point ``level`` of ``mode`` (times ``scale``) and absorb the bond matrix into a neighbour, on the
         side the reference picks (gates.py:108-115): into the left neighbour iff the slice is at least as tall as wide
@@ -360,6 +433,7 @@ class SiteRegister:
             self.sites[mode + 1] = self._gemm(bond, OP_NONE, nb, OP_NONE, cl, nd * ncr, cr).reshape(cl, nd, ncr)
         self.sites.pop(mode)
 
+    @_on_stream
     def insert(self, mode: int, vec: np.ndarray, **truncation) -> None:
         """New mode at ``mode``: a free-standing site at either end, otherwise attached to the site now at ``mode``
         and split off again (gates.py:24-45)."""
@@ -384,6 +458,7 @@ class SiteRegister:
                   int(swap_last))
         return out
 
+    @_on_stream
     def insert_bond_pair(self, mode: int, first: np.ndarray, second: np.ndarray, **truncation) -> None:
         """Insert two new modes at ``mode`` that share a bond: ``first`` is ``(d, chi)``, ``second`` ``(chi, d)`` (a GKP
         Bell pair has chi = 2).  At the ends of the chain they are simply attached; inside, each half is multiplied into
@@ -406,6 +481,7 @@ class SiteRegister:
         new_second, new_t2 = m1.reshape(b * chi, d, r2), m2.reshape(r2, d, c)
         self.sites[mode - 1:mode + 1] = [new_t1, new_first, new_second, new_t2]
 
+    @_on_stream
     def operator_string_coefficients(self, operators: list[np.ndarray]) -> np.ndarray:
         """``C[i_0, ..., i_{m-1}] = <psi| O_{i_0} (x) ... (x) O_{i_{m-1}} |psi>`` (no grid-measure factors) for every
         string over the given single-mode operators: the contraction loop of ``full_logical_density_mps``

@@ -8,6 +8,7 @@ teleport a T / T^dagger gate.
 from __future__ import annotations
 
 import logging
+import threading
 from enum import Enum
 
 import numpy as np
@@ -23,6 +24,7 @@ SQPI = np.sqrt(np.pi)
 
 
 _HALVES: dict = {}      # (pair, grid, epsilon) -> (first, second), see GKPBellState.halves
+_HALVES_LOCK = threading.Lock()      # held for lookup and insertion (simulations on worker threads share the cache)
 
 
 class GKPBellState(Enum):
@@ -52,9 +54,11 @@ class GKPBellState(Enum):
         # the two theta-function combs are evaluated once per (pair, grid, epsilon) and handed out read-only, which also
         # lets the register keep ONE device copy of them (SiteRegister._keep goes by array identity)
         key = (self.name, qs.shape[0], qs.dtype.str, qs.tobytes() if qs.shape[0] <= 4096 else None, gkp_epsilon)
-        hit = _HALVES.get(key) if key[3] is not None else None
-        if hit is not None:
-            return hit
+        if key[3] is not None:
+            with _HALVES_LOCK:
+                hit = _HALVES.get(key)
+            if hit is not None:
+                return hit
         first = np.empty((len(qs), 2), dtype=complex)
         first[:, 0] = 2 ** (-1 / 4) * State.GKP_ZERO.eval(qs, gkp_epsilon)
         first[:, 1] = 2 ** (-1 / 4) * self._second_weight * State.GKP_ONE.eval(qs, gkp_epsilon)
@@ -62,9 +66,13 @@ class GKPBellState(Enum):
         if key[3] is not None:
             first.setflags(write=False)
             second.setflags(write=False)
-            if len(_HALVES) >= 32:
-                _HALVES.clear()
-            _HALVES[key] = (first, second)
+            with _HALVES_LOCK:
+                hit = _HALVES.get(key)
+                if hit is not None:         # another thread was quicker: hand out its arrays
+                    return hit
+                if len(_HALVES) >= 32:
+                    _HALVES.clear()
+                _HALVES[key] = (first, second)
         return first, second
 
     def eval(self, qs: np.ndarray, gkp_epsilon: float = None, *, device: int = 0) -> MPS:

@@ -7,6 +7,7 @@ the device does ``(4^(N+1) - 4) / 3`` small GEMM pairs instead of ``N 4^N`` eins
 """
 from __future__ import annotations
 
+import threading
 from functools import reduce
 from itertools import product
 
@@ -64,6 +65,7 @@ def syndrome_matrix(syndromes: list[tuple[int, int]]) -> np.ndarray:
 
 
 _READOUT_OPERATORS: dict = {}      # grid -> [I, X, Y, Z] read-out operators, see pauli_readout_operators
+_READOUT_LOCK = threading.Lock()   # held for lookup and insertion (simulations on worker threads share the cache)
 
 
 def pauli_readout_operators(qs: np.ndarray) -> list[np.ndarray]:
@@ -74,8 +76,11 @@ def pauli_readout_operators(qs: np.ndarray) -> list[np.ndarray]:
     # the operators depend on the grid alone (0.2 s of sinc evaluations at d = 1000): one set per grid is kept, read-only,
     # which also lets a register keep ONE device copy of each (SiteRegister._keep goes by array identity)
     key = (qs.shape[0], qs.dtype.str, qs.tobytes()) if isinstance(qs, np.ndarray) and qs.ndim == 1 and qs.shape[0] <= 4096 else None
-    if key is not None and key in _READOUT_OPERATORS:
-        return _READOUT_OPERATORS[key]
+    if key is not None:
+        with _READOUT_LOCK:
+            hit = _READOUT_OPERATORS.get(key)
+        if hit is not None:
+            return hit
     d = len(qs)
     dq = (qs[-1] - qs[0]) / d
     offsets = qs[:, None] - qs[None, :]
@@ -88,9 +93,13 @@ def pauli_readout_operators(qs: np.ndarray) -> list[np.ndarray]:
     if key is not None:
         for op in operators:
             op.setflags(write=False)
-        if len(_READOUT_OPERATORS) >= 2:
-            _READOUT_OPERATORS.clear()
-        _READOUT_OPERATORS[key] = operators
+        with _READOUT_LOCK:
+            hit = _READOUT_OPERATORS.get(key)
+            if hit is not None:         # another thread was quicker: hand out its arrays (one device copy per register)
+                return hit
+            if len(_READOUT_OPERATORS) >= 2:
+                _READOUT_OPERATORS.clear()
+            _READOUT_OPERATORS[key] = operators
     return operators
 
 

@@ -364,6 +364,27 @@ int qsv_tensor_axis_density(int device, void *hip_stream, const void *dev_z, con
  * the quadrature aliases; every check runs before the first HIP call.  Synchronises `hip_stream` before it returns. */
 int qsv_tensor_wigner(int device, void *hip_stream, const void *dev_rho, int batch, uint64_t d, double x0, double dx,
                       const double *q, uint64_t nq, const double *p, uint64_t np, int normalised, void *dev_w);
+/* One site step of multi-shot homodyne sampling (SiteRegister.sample): S shots advance together through the site
+ * `dev_site` (L x d x R) of a matrix-product state.  A shot is the outcome list of the chain Mq(0), Mq(0), ... of the
+ * reference (cv_simulator/gates.py:87-117; the pre-rotations of Mp / Homodyne, :120-148, are applied to the site by the
+ * caller), and rng.choice(range(d), p = w / w.sum()) of gates.py:98 is searchsorted(cumsum(p) / cumsum(p)[-1], u,
+ * "right") of one uniform u.  With `dev_v` (S x L) the shots' boundary vectors -- the chain to the left collapsed onto
+ * each shot's earlier picks -- and w[s, j, :] = v_s . site[:, j, :], the step is
+ *     p[s, j]    = sum_b |w[s, j, b]|^2                      when dev_site_env is NULL (no sites to the right), else
+ *                = Re sum_b conj(w[s, j, b]) (v_s . site_env[:, j, :])[b],   site_env = site . E (L x d x R), E the right
+ *                  environment of mps.py:185-186: the diagonal of partial_density_mps (mps.py:176-190) of the collapsed
+ *                  register without its grid measure;
+ *     pick[s]    = the first j with cumsum(p[s, :])[j] / cumsum(p[s, :])[d - 1] > u[s]              (int32);
+ *     density[s] = scale * p[s, pick[s]], `scale` = dq^(modes to the right): MeasurementResult.probability (gates.py:102);
+ *     v_out[s,:] = v_s . site[:, pick[s], :] / sqrt(density[s])   (S x R; gates.py:108-113).  NULL: not computed.
+ * p is never stored beyond a bounded block of shots, w not at all; nothing the caller passed is modified except the
+ * outputs.  QSV_EINVAL for S < 1, d < 2, L < 1, R < 1, L > 512, a scale that is not positive and finite, or a NULL
+ * dev_v / dev_site / dev_u / dev_pick / dev_density; every check runs before the first HIP call.  Synchronises
+ * `hip_stream` before it returns. */
+int qsv_tensor_sample_site(int device, void *hip_stream, const void *dev_v, const void *dev_site,
+                           const void *dev_site_env /* may be NULL */, uint64_t S, uint64_t L, uint64_t d, uint64_t R,
+                           double scale, const double *dev_u, int32_t *dev_pick, double *dev_density,
+                           void *dev_v_out /* may be NULL */);
 
 /* ---- whole circuits in one launch (registers of at most 13 qubits) ------------------------------------------------
  * Replaces the caller loop itself -- `for gate in self.circuit: ... gate.apply(state)` with its measurement record and

@@ -101,6 +101,8 @@ SIGNATURES: dict[str, list] = {
     "qsv_tensor_axis_density": [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p],
     "qsv_tensor_wigner": [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_double, C.c_double, _dbl_p, C.c_uint64,
                           _dbl_p, C.c_uint64, C.c_int, C.c_void_p],
+    "qsv_tensor_sample_site": [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
+                               C.c_uint64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "qsv_run_programs": [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "qsv_timer_start": [_state_p],

@@ -209,6 +209,54 @@ class MPS:
             w = wigner_device(rho, self.domain, q, p, normalised=normalised)
         return w if np.ndim(mode) else w[0]
 
+    def sample(self, shots: int, *, quadratures=None, rng=None, return_density: bool = False):
+        """``shots`` independent outcomes of measuring every mode, as grid values ``(shots, m)``; the register is not
+        modified.  Shot ``s`` is what the chain ``Mq(0), Mq(0), ...`` (gates.py:87-117) returns on a copy of the register
+        when ``rng.choice`` is fed ``U[s, :]`` of ``U = rng.random((shots, m))``; all shots advance through the chain
+        together on the device (``SiteRegister.sample``).  No upstream counterpart.
+
+        ``quadratures[k]``: ``"q"`` (default), ``"p"`` (the inverse Fourier matrix of ``Mp``) or an angle (the rotation
+        by ``-angle`` of ``Homodyne``; multiples of pi measure ``q`` and multiply the outcome by ``round(cos(angle))``).
+        ``rng``: a ``numpy.random.Generator`` or a seed.  ``return_density=True`` also returns the probability density
+        of every outcome given the shot's earlier ones (``MeasurementResult.probability``), ``(shots, m)``: the product
+        along a row is the joint density of the shot."""
+        from .utils import fourier_matrix, rotation_matrix
+        self._sites_only("sampling")
+        m = len(self)
+        if int(shots) != shots or shots < 1:
+            raise ValueError(f"shots must be a positive integer, got {shots}")
+        if m < 1:
+            raise IndexError("cannot sample an empty register")
+        quadratures = ["q"] * m if quadratures is None else list(quadratures)
+        if len(quadratures) != m:
+            raise IndexError(f"quadratures must have one entry per mode ({m}), got {len(quadratures)}")
+        built: dict = {}
+        operators, signs = [None] * m, np.ones(m)
+        for k, quad in enumerate(quadratures):
+            if isinstance(quad, str):
+                if quad not in ("q", "p"):
+                    raise ValueError(f"quadratures[{k}] must be 'q', 'p' or an angle, got {quad!r}")
+                if quad == "p":
+                    if "p" not in built:
+                        built["p"] = fourier_matrix(self.domain, inv=True)
+                    operators[k] = built["p"]
+                continue
+            angle = float(quad)
+            if np.isclose(np.sin(angle), 0):
+                signs[k] = np.round(np.cos(angle))
+                continue
+            if angle not in built:
+                built[angle] = rotation_matrix(self.domain, -angle)
+            operators[k] = built[angle]
+        generator = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+        uniforms = generator.random((int(shots), m))
+        picks, densities = self.reg.sample(uniforms, operators if any(op is not None for op in operators) else None,
+                                           measure=self.diff)
+        if not np.all(np.isfinite(densities)) or np.any(densities <= 0):
+            raise ValueError("sampling met an outcome of zero density: the register has no norm")
+        values = self.domain[picks] * signs
+        return (values, densities) if return_density else values
+
     @staticmethod
     def fidelity(a: "MPS", b: "MPS") -> float:
         """``|<a|b>|^2`` on a shared grid.  (The reference's version, mps.py:192-201, contracts ``a`` with itself

@@ -287,6 +287,71 @@ class SiteRegister:
                       self._p(out[slot]))
         return out
 
+    # ---- multi-shot sampling ----------------------------------------------------------------------------------
+    @_on_stream
+    def sample(self, uniforms: np.ndarray, operators=None, measure: float = 1.0):
+        """``shots`` independent outcome lists of measuring every mode from the left (the chain ``Mq(0), Mq(0), ...`` of
+        the reference, gates.py:87-117), all shots advancing together one site at a time on the device
+        (``qsv_tensor_sample_site``); the register is not modified.
+
+        ``uniforms``: ``(shots, m)`` numbers in [0, 1), ``uniforms[s, k]`` decides mode ``k`` of shot ``s`` the way
+        ``rng.choice`` would with that draw.  ``operators[k]``: ``None`` or a ``(d, d)`` matrix applied to a copy of
+        site ``k`` first (rotated quadratures).  ``measure``: the grid spacing ``dq``; the densities carry
+        ``dq^(modes still unmeasured - 1)`` like ``MeasurementResult.probability``.  Returns ``picks (shots, m) int64``
+        and ``densities (shots, m) float64``.
+
+        The conditional weights need the right environment of every site (the registers here are not in canonical
+        form): one right-to-left pass of the ``_right_environment`` recurrence whose intermediate ``site . E`` is kept
+        per site and handed to the kernel next to the site itself."""
+        torch = _torch()
+        uniforms = np.asarray(uniforms, dtype=np.float64)
+        m = len(self.sites)
+        if uniforms.ndim != 2 or uniforms.shape[1] != m or uniforms.shape[0] < 1 or m < 1:
+            raise ValueError(f"uniforms must have shape (shots >= 1, {m}), got {uniforms.shape}")
+        if operators is not None and len(operators) != m:
+            raise ValueError(f"operators must have one entry per mode ({m}), got {len(operators)}")
+        shots = int(uniforms.shape[0])
+        sites = list(self.sites)
+        if operators is not None:
+            for k, op in enumerate(operators):
+                if op is None:
+                    continue
+                t = sites[k]
+                cl, d, cr = (int(x) for x in t.shape)
+                if np.shape(op) != (d, d):
+                    raise ValueError(f"operators[{k}] must be a ({d}, {d}) matrix")
+                out = self._empty(cl, d, cr)
+                _lib.call("qsv_tensor_apply_axis_dev", self.device, self._stream(), self._p(t), self._p(out), cl, d, d, cr,
+                          self._p(self._keep(op)))
+                sites[k] = out
+        # dressed[k] = (measured) site_k . E_k, E_k the environment of everything to the right of k (None at the right end:
+        # E = 1).  The chain rotates a mode only when its turn comes, so E_k is built from the sites as they are -- a
+        # rotation sampled on a finite grid is not exactly unitary, and the reference's densities show the difference.
+        dressed = [None] * m
+        r = None
+        for k in range(m - 1, -1, -1):
+            t = self.sites[k]
+            cl, d, cr = (int(x) for x in t.shape)
+            y = self._gemm(t, OP_NONE, r, OP_NONE, cl * d, cr, cr) if r is not None else None       # Y[(i, c), b]
+            if r is not None:
+                dressed[k] = y if sites[k] is t else self._gemm(sites[k], OP_NONE, r, OP_NONE, cl * d, cr, cr)
+            if k > 0:
+                r = self._gemm(y if y is not None else t, OP_NONE, t, OP_CONJ_TRANSPOSE, cl, cl, d * cr)
+        u = self._upload(np.ascontiguousarray(uniforms.T), np.float64)          # (m, shots): one contiguous row per site
+        picks = torch.empty((m, shots), dtype=torch.int32, device=self._dev)
+        densities = torch.empty((m, shots), dtype=torch.float64, device=self._dev)
+        v = self._upload(np.ones((shots, 1)))
+        for k, t in enumerate(sites):
+            cl, d, cr = (int(x) for x in t.shape)
+            v_next = self._empty(shots, cr) if k + 1 < m else None
+            _lib.call("qsv_tensor_sample_site", self.device, self._stream(), self._p(v), self._p(t),
+                      self._p(dressed[k]) if dressed[k] is not None else None, shots, cl, d, cr,
+                      float(measure) ** (m - 1 - k), self._p(u[k]), self._p(picks[k]), self._p(densities[k]),
+                      self._p(v_next) if v_next is not None else None)
+            v = v_next
+        return (np.ascontiguousarray(picks.cpu().numpy().T.astype(np.int64)),
+                np.ascontiguousarray(densities.cpu().numpy().T))
+
     # ---- gates ------------------------------------------------------------------------------------------------
     @_on_stream
     def apply_mode(self, operator: np.ndarray, mode: int) -> None:

@@ -137,3 +137,31 @@ def full_logical_density(qs: np.ndarray, state: np.ndarray, normalised: bool = F
         sites.append(head)
     sites.append(rest)
     return full_logical_density_mps(MPS(qs, sites, device=device, layout="sites"), normalised)
+
+
+def sample_logical(mps: MPS, shots: int, basis="Z", rng=None) -> np.ndarray:
+    """Logical bit strings of an N-mode GKP register as the experiment reads them: ``shots`` homodyne outcomes of every
+    mode (``MPS.sample``), each binned to the nearest multiple of sqrt(pi) by :func:`cv2dv_information`.  ``basis``:
+    ``"Z"`` (q outcomes) or ``"X"`` (p outcomes) for the whole register, or one character per mode (``"ZXZ"`` or a
+    sequence).  Returns ``uint8 (shots, N)``; the register is not modified.  No upstream counterpart."""
+    n = len(mps)
+    letters = [basis] * n if isinstance(basis, str) and len(basis) == 1 else list(basis)
+    if len(letters) != n:
+        raise IndexError(f"basis must be one character or one per mode ({n}), got {basis!r}")
+    if any(letter not in ("Z", "X") for letter in letters):
+        raise ValueError(f"basis characters must be 'Z' or 'X', got {basis!r}")
+    values = mps.sample(shots, quadratures=["q" if letter == "Z" else "p" for letter in letters], rng=rng)
+    return cv2dv_information(values).astype(np.uint8)
+
+
+def logical_distribution(bits: np.ndarray) -> np.ndarray:
+    """Frequencies of the ``2^N`` logical basis states in ``bits`` (``(shots, N)`` zeros and ones, as
+    :func:`sample_logical` returns them), qubit 0 the most significant bit of the index."""
+    bits = np.asarray(bits)
+    if bits.ndim != 2 or bits.shape[0] < 1:
+        raise ValueError(f"bits must have shape (shots >= 1, N), got {bits.shape}")
+    if not np.all((bits == 0) | (bits == 1)):
+        raise ValueError("bits must be zeros and ones")
+    n = bits.shape[1]
+    index = bits.astype(np.int64) @ (1 << np.arange(n - 1, -1, -1, dtype=np.int64))
+    return np.bincount(index, minlength=2 ** n) / bits.shape[0]

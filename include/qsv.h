@@ -386,6 +386,28 @@ int qsv_tensor_sample_site(int device, void *hip_stream, const void *dev_v, cons
                            double scale, const double *dev_u, int32_t *dev_pick, double *dev_density,
                            void *dev_v_out /* may be NULL */);
 
+/* One step of bringing a matrix-product state into canonical form (SiteRegister.canonicalise / compress): factor the
+ * site `dev_site` (L x d x R, read as it is stored, not modified) into an isometry and a small carry matrix.
+ *   side = 0 (left):  site[(l,j), r] = sum_k iso[(l,j), k] carry[k, r];  iso (L, d, rank) with orthonormal columns,
+ *                     carry (rank x R) = diag(s) Vh;   the bond that is orthogonalised is R.
+ *   side = 1 (right): site[l, (j,r)] = sum_k carry[l, k] iso[k, (j,r)];  iso (rank, d, R) with orthonormal rows,
+ *                     carry (L x rank) = U diag(s);    the bond that is orthogonalised is L.
+ * s are the singular values of the site matrix in decreasing order (absolute accuracy of a few 8 eps max(bond,
+ * sqrt(rows)) s[0]), *rank = the number of them above rank_tol * s[0].  Directions whose
+ * singular value is below that rounding level (about 1e-13 s[0] for sites of a thousand rows, 1e-12 s[0] for 1e5 rows)
+ * cannot be told from zero and come out as exactly 0: they are never kept, so
+ * with rank_tol = 0 a site of full numerical rank keeps min(rows, cols) directions and a rank-deficient one its numerical
+ * rank, and iso is an isometry either way.  Both outputs are written compactly for the returned rank; dev_iso must
+ * hold L d R amplitudes, dev_carry bond^2.  singular_values (host, may be NULL) receives min(rows, cols) doubles with
+ * (rows, cols) = (L d, R) resp. (L, d R).  The orthogonalised bond may be at most QSV_SITE_MAX_BOND wide.  The order of
+ * every sum depends on (L, d, R, side) alone.  QSV_EINVAL, before the first HIP call, for d < 2, L < 1, R < 1, a side
+ * other than 0 / 1, a bond above QSV_SITE_MAX_BOND, a NULL dev_site / dev_iso / dev_carry / rank, a rank_tol that is
+ * negative or not finite.  Synchronises `hip_stream` before it returns. */
+#define QSV_SITE_MAX_BOND 128
+int qsv_tensor_site_orthogonalise(int device, void *hip_stream, const void *dev_site, uint64_t L, uint64_t d, uint64_t R,
+                                  int side, double rank_tol, void *dev_iso, void *dev_carry, uint64_t *rank,
+                                  double *singular_values);
+
 /* ---- whole circuits in one launch (registers of at most 13 qubits) ------------------------------------------------
  * Replaces the caller loop itself -- `for gate in self.circuit: ... gate.apply(state)` with its measurement record and
  * ClassicalControl (dv_simulator/simulator.py:40-52, :6-17) -- for the register sizes the reference can run (4..12

@@ -13,6 +13,7 @@ OPT_SPECIALIZE, OPT_UNROLL, OPT_GRID_CAP, OPT_NONTEMPORAL, OPT_ITEM_STRIDE_BIT, 
 OPT_KQ_VARIANT, OPT_PLANE_KERNEL, OPT_READOUT_VARIANT, OPT_COMPLEX_PRODUCT, OPT_SEQUENCE_WORK = 7, 8, 9, 10, 11
 OPT_TILE_SEQUENCE_GATES, OPT_DEFER = 12, 13
 
+SITE_MAX_BOND = 128                 # QSV_SITE_MAX_BOND: widest bond qsv_tensor_site_orthogonalise takes
 RANK_NEEDS_OMEGA = (1 << 64) - 1     # qsv_tensor_rsvd_split without a test matrix: call again with one
 
 _state_p = C.c_void_p
@@ -103,6 +104,8 @@ SIGNATURES: dict[str, list] = {
                           _dbl_p, C.c_uint64, C.c_int, C.c_void_p],
     "qsv_tensor_sample_site": [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
                                C.c_uint64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "qsv_tensor_site_orthogonalise": [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_double,
+                                      C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p],
     "qsv_run_programs": [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "qsv_timer_start": [_state_p],

@@ -16,6 +16,7 @@ Either way the class keeps the constructor, ``domain`` / ``diff``, ``len``, ``co
 from __future__ import annotations
 
 import inspect
+import logging
 from functools import reduce
 
 import numpy as np
@@ -257,11 +258,72 @@ class MPS:
         values = self.domain[picks] * signs
         return (values, densities) if return_density else values
 
+    # ---- canonical forms, Schmidt spectra, compression (no upstream counterpart) ------------------------------------
+    def canonicalise(self, centre: int = 0, *, rank_tol: float = 1e-13) -> list[np.ndarray]:
+        """Mixed canonical form around ``centre``, in place (``SiteRegister.canonicalise``): sites before ``centre`` become
+        left isometries, sites after it right isometries, the state stays what it was up to rounding.  Returns the Schmidt
+        values of all ``m - 1`` bonds (of the unnormalised state, without grid-measure factors)."""
+        self._sites_only("canonicalise")
+        return self.reg.canonicalise(centre, rank_tol)
+
+    def compress(self, centre: int = 0, **svd_options) -> list[float]:
+        """Truncate every bond of the finished register by its Schmidt values with the rule of the gates'
+        ``max_bond_dim`` / ``abs_err`` / ``rel_err`` (``SiteRegister.compress``), in place; returns the discarded weight
+        per bond relative to ``norm()**2``.  Unknown keywords are logged and ignored, like the gates do."""
+        self._sites_only("compress")
+        known = {k: v for k, v in svd_options.items() if k in ("max_bond_dim", "abs_err", "rel_err")}
+        for name in svd_options:
+            if name not in known:
+                logging.getLogger(__name__).warning("compress ignores the keyword %r", name)
+        return self.reg.compress(centre, **known)
+
+    def schmidt_values(self, bond: int | None = None):
+        """Schmidt values of the cut between modes ``bond`` and ``bond + 1`` (or the list for all ``m - 1`` cuts),
+        computed on a canonicalised copy: the register is untouched."""
+        self._sites_only("schmidt_values")
+        m = len(self)
+        if bond is not None and (int(bond) != bond or not 0 <= bond < m - 1):
+            raise IndexError(f"bond={bond} out of bounds for {m} modes")
+        if m < 1:
+            raise IndexError("an empty register has no bonds")
+        work = self.reg.copy()
+        values = work.canonicalise(0)
+        work.sites = []
+        return values if bond is None else values[int(bond)]
+
+    def entanglement_entropy(self, bond: int | None = None):
+        """Von Neumann entropy (nats) of ``p = s^2 / sum s^2`` over the Schmidt values of ``bond`` (or of every bond)."""
+        values = self.schmidt_values(bond)
+
+        def entropy(s):
+            p = np.asarray(s, dtype=np.float64) ** 2
+            p = p[p > 0] / np.sum(p)
+            return float(-np.sum(p * np.log(p)))
+
+        return entropy(values) if bond is not None else [entropy(s) for s in values]
+
+    @staticmethod
+    def overlap(a: "MPS", b: "MPS") -> complex:
+        """``<a|b> = int conj(a) b`` with the grid measure ``diff^m``, contracted site by site on the device
+        (``SiteRegister.overlap``): no dense tensor is built."""
+        a._sites_only("overlap")
+        b._sites_only("overlap")
+        if len(a) != len(b):
+            raise ValueError("registers of different sizes")
+        if len(a.domain) != len(b.domain) or not np.allclose(a.domain, b.domain):
+            raise ValueError("registers on different grids")
+        if a.reg.device != b.reg.device:
+            raise ValueError("registers on different devices")
+        return a.reg.overlap(b.reg) * a.diff ** len(a)
+
     @staticmethod
     def fidelity(a: "MPS", b: "MPS") -> float:
         """``|<a|b>|^2`` on a shared grid.  (The reference's version, mps.py:192-201, contracts ``a`` with itself
-        and never reads ``b``; this one computes what its docstring says.)"""
+        and never reads ``b``; this one computes what its docstring says.)  Two ``sites`` registers go through
+        :meth:`overlap` and need no ``d^m`` host memory; a dense register is contracted on the host."""
         if len(a) != len(b):
             raise ValueError("registers of different sizes")
+        if a.layout == "sites" and b.layout == "sites":
+            return float(np.abs(MPS.overlap(a, b)) ** 2)
         overlap = np.vdot(a.contract(), b.contract()) * a.diff ** len(a)
         return float(np.abs(overlap) ** 2)

@@ -44,6 +44,18 @@ from .. import _lib
 OP_NONE, OP_TRANSPOSE, OP_CONJ_TRANSPOSE = 0, 1, 2
 
 
+def kept_rank(s, max_bond_dim=np.inf, abs_err: float = 0, rel_err: float = 1e-12) -> int:
+    """How many of the decreasing values ``s`` the truncation rule of the splits keeps (``tensor_svd``, mps.py:86-93;
+    ``qsv_tensor_svd_split``): drop the longest tail whose sum stays ``<= max(abs_err, rel_err * sum(s))``, then cap at
+    ``max_bond_dim``; at least one value stays."""
+    s = np.asarray(s, dtype=np.float64)
+    tails = np.cumsum(s[::-1])[::-1]                    # tails[i] = s[i] + ... + s[-1]
+    keep = int(np.count_nonzero(tails > max(abs_err, rel_err * float(np.sum(s)))))
+    if np.isfinite(max_bond_dim):
+        keep = min(keep, int(max_bond_dim))
+    return max(1, keep)
+
+
 _TORCH = None
 
 
@@ -286,6 +298,142 @@ class SiteRegister:
             _lib.call("qsv_tensor_axis_density", self.device, self._stream(), self._p(z), self._p(t), cl, d, cr,
                       self._p(out[slot]))
         return out
+
+    # ---- canonical forms (no upstream counterpart) --------------------------------------------------------------
+    def _orthogonalise(self, site, side: int, rank_tol: float):
+        """``qsv_tensor_site_orthogonalise`` of one site: ``(iso, carry, singular values)`` with compact device
+        tensors -- ``iso`` ``(L, d, r)`` and ``carry`` ``(r, R)`` for ``side = 0``, ``carry`` ``(L, r)`` and ``iso``
+        ``(r, d, R)`` for ``side = 1``."""
+        cl, d, cr = (int(x) for x in site.shape)
+        width = cr if side == 0 else cl
+        rows, cols = (cl * d, cr) if side == 0 else (cl, d * cr)
+        iso, carry = self._scratch("iso", cl * d * cr), self._scratch("carry", width * width)
+        s = np.zeros(min(rows, cols), dtype=np.float64)
+        rank = C.c_uint64(0)
+        _lib.call("qsv_tensor_site_orthogonalise", self.device, self._stream(), self._p(site), cl, d, cr, int(side),
+                  float(rank_tol), self._p(iso), self._p(carry), C.byref(rank), s.ctypes.data_as(C.c_void_p))
+        r = int(rank.value)
+        if r < 1:
+            raise ValueError("cannot orthogonalise a site that is zero: the register has no norm")
+        if side == 0:
+            return iso[: cl * d * r].view(cl, d, r), carry[: r * cr].view(r, cr), s
+        return iso[: r * d * cr].view(r, d, cr), carry[: cl * r].view(cl, r), s
+
+    def _check_centre(self, centre) -> int:
+        m = len(self.sites)
+        if m < 1:
+            raise IndexError("cannot canonicalise an empty register")
+        if int(centre) != centre or not 0 <= centre < m:
+            raise IndexError(f"centre={centre} out of bounds for {m} modes")
+        return int(centre)
+
+    def _sweep_right(self, stop: int, rank_tol: float) -> None:
+        """Make the sites before ``stop`` left isometries, each carry absorbed into its right neighbour."""
+        for k in range(stop):
+            iso, carry, _ = self._orthogonalise(self.sites[k], 0, rank_tol)
+            r = int(carry.shape[0])
+            nb = self.sites[k + 1]
+            _, d, ncr = (int(x) for x in nb.shape)
+            self.sites[k] = iso.clone()
+            self.sites[k + 1] = self._gemm(carry, OP_NONE, nb, OP_NONE, r, d * ncr, int(carry.shape[1])).reshape(r, d, ncr)
+
+    def _sweep_left(self, stop: int, rank_tol: float, keep=None) -> list[np.ndarray]:
+        """Make the sites after ``stop`` right isometries from the right end, each carry absorbed into its left
+        neighbour; returns the singular values met at the bonds ``m - 2, ..., stop`` in that order.  ``keep(s)`` = how
+        many of them stay (default: all the library kept)."""
+        met = []
+        for k in range(len(self.sites) - 1, stop, -1):
+            iso, carry, s = self._orthogonalise(self.sites[k], 1, rank_tol)
+            r = int(iso.shape[0])
+            s = s[:r].copy()
+            met.append(s)
+            cut = r if keep is None else max(1, min(r, int(keep(s))))
+            _, d, cr = (int(x) for x in iso.shape)
+            self.sites[k] = iso[:cut].clone()
+            if cut < r:
+                carry = carry[:, :cut].contiguous()
+            nb = self.sites[k - 1]
+            ncl, nd, chi = (int(x) for x in nb.shape)
+            self.sites[k - 1] = self._gemm(nb, OP_NONE, carry, OP_NONE, ncl * nd, cut, chi).reshape(ncl, nd, cut)
+        return met
+
+    @_on_stream
+    def canonicalise(self, centre: int, rank_tol: float = 1e-13) -> list[np.ndarray]:
+        """Bring the register into mixed canonical form around ``centre``, in place: the sites before ``centre`` become
+        left isometries (``sum_{l,j} conj(A[l,j,r]) A[l,j,r'] = 1``), the sites after it right isometries, and the state
+        is unchanged up to rounding.  The sweep runs all the way to the right end, back to site 0 and forward again to
+        ``centre``: the way back meets every bond with orthonormal environments on both sides, so the singular values
+        it finds are the Schmidt values of the state.  They are returned for all ``m - 1`` bonds (bond ``b`` joins
+        sites ``b`` and ``b + 1``).  Bonds shrink to their numerical rank: Schmidt values at or below
+        ``rank_tol * s[0]`` are dropped."""
+        centre = self._check_centre(centre)
+        if not (np.isfinite(rank_tol) and rank_tol >= 0):
+            raise ValueError(f"rank_tol must be finite and >= 0, got {rank_tol}")
+        m = len(self.sites)
+        self._sweep_right(m - 1, rank_tol)
+        schmidt = self._sweep_left(0, rank_tol)[::-1]
+        self._sweep_right(centre, rank_tol)
+        return schmidt
+
+    @_on_stream
+    def compress(self, centre: int = 0, *, max_bond_dim=np.inf, abs_err: float = 0, rel_err: float = 1e-12,
+                 rank_tol: float = 1e-13) -> list[float]:
+        """Globally optimal truncation of the finished register, in place: the sweep of :meth:`canonicalise`, cutting
+        every bond's Schmidt values on the way back with the rule of the splits (``qsv_tensor_svd_split``): drop the
+        longest tail whose sum stays ``<= max(abs_err, rel_err * sum)``, then cap at ``max_bond_dim``.  Returns the
+        discarded weight per bond, ``sum(dropped s^2) / norm2()`` with ``norm2()`` taken before the sweep; the
+        register ends in canonical form around ``centre``."""
+        centre = self._check_centre(centre)
+        if not (np.isfinite(rank_tol) and rank_tol >= 0):
+            raise ValueError(f"rank_tol must be finite and >= 0, got {rank_tol}")
+        if np.isnan(max_bond_dim) or max_bond_dim < 1:
+            raise ValueError(f"max_bond_dim must be at least 1, got {max_bond_dim}")
+        if not (abs_err >= 0 and rel_err >= 0):
+            raise ValueError("abs_err and rel_err must be >= 0")
+        m = len(self.sites)
+        self._sweep_right(m - 1, rank_tol)
+        kept = []
+
+        def keep(s):
+            kept.append(kept_rank(s, max_bond_dim, abs_err, rel_err))
+            return kept[-1]
+
+        met = self._sweep_left(0, rank_tol, keep)
+        # the first bond met has isometries on its left and nothing cut yet: its Schmidt values square-sum to <psi|psi>,
+        # which is norm2() before the sweep up to rounding, without the environment GEMMs norm2() would spend on it
+        norm2 = float(np.sum(met[0] ** 2)) if met else 1.0
+        weights = [float(np.sum(s[max(1, k):] ** 2) / norm2) for s, k in zip(met, kept)][::-1]
+        self._sweep_right(centre, rank_tol)
+        return weights
+
+    @_on_stream
+    def overlap(self, other: "SiteRegister") -> complex:
+        """``sum conj(a) b`` over all amplitudes (``a`` = this register; no grid-measure factors) by the transfer-matrix
+        recurrence of :meth:`_left_environment` with two chains: ``E' = sum_j A_j^H E B_j``, two GEMMs per site, the
+        environment ``chi_a x chi_b``.  Neither register is contracted."""
+        if not isinstance(other, SiteRegister):
+            raise TypeError("overlap needs another SiteRegister")
+        if len(other.sites) != len(self.sites) or other.d != self.d:
+            raise ValueError("overlap needs registers with the same number of modes and the same grid size")
+        if other.device != self.device:
+            raise ValueError("overlap needs both registers on one device")
+        torch = _torch()
+        mine, theirs = self._torch_stream(), other._torch_stream()
+        if theirs != mine:      # this stream reads the other register's sites: wait for what is queued on them
+            ready = torch.cuda.Event()
+            ready.record(theirs)
+            mine.wait_event(ready)
+        e = self._upload(np.ones((1, 1)))
+        for a, b in zip(self.sites, other.sites):
+            al, d, ar = (int(x) for x in a.shape)
+            bl, _, br = (int(x) for x in b.shape)
+            x = self._gemm(e, OP_NONE, b, OP_NONE, al, d * br, bl)                     # X[a, (j, b')]
+            e = self._gemm(a, OP_CONJ_TRANSPOSE, x, OP_NONE, ar, br, al * d)          # E'[a', b']
+        if theirs != mine:      # and the other stream must not overwrite or free those sites before the reads are done
+            done = torch.cuda.Event()
+            done.record(mine)
+            theirs.wait_event(done)
+        return complex(e.cpu().numpy()[0, 0])
 
     # ---- multi-shot sampling ----------------------------------------------------------------------------------
     @_on_stream

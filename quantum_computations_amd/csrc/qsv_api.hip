@@ -260,6 +260,7 @@ qsv_plan::Gate plan_gate(const QsvOp &op) {
     }
     g.cost = cost < 0.2f ? 0.2f : cost;
     g.exact = qsvk_op_exact(op);
+    g.dense = op.kind == QSV_OP_DENSE || op.kind == QSV_OP_PAIR;
     return g;
 }
 

@@ -2997,25 +2997,44 @@ int qsvk_sequence_tile(qsv_state *st, int k, const int *bits, int n_gates, const
 // ---- deferred gates: one PASS of queued 1- and 2-qubit gates over LDS-resident tiles ----------------------------------
 // The queue of a deferring register (qsv_api.hip) is cut into passes by qsv_plan.h.  A workgroup brings one 4096-amplitude
 // tile into LDS -- bits 0..5 plus the pass's six further tile bits, so every tile row is one 1 KiB run of HBM, straight
-// into LDS on the way in -- applies the pass's gates to it one after the other (a barrier between gates) and stores it back:
-// one round trip over HBM for the whole list.  A gate's control bits outside the tile are the same for every amplitude of
-// a tile: they decide per workgroup whether the gate acts (omask), and a tile on which no gate of the pass acts is neither
-// loaded nor stored.  Each gate is computed with the expression and the summation order of the per-gate kernel it would
-// have run on (tile12_body: products summed from zero in kernel-index order; dense_body: low-lane combinations outer,
-// high rows inner; k_diag: one complex product), so the amplitudes are bit for bit those of the per-gate path.
-enum { PASS_D2 = 0, PASS_D2X = 1, PASS_D4 = 2, PASS_D4X = 3, PASS_D4HL = 4, PASS_DIAG = 5 };
+// into LDS on the way in -- applies the pass's gates to it and stores it back: one round trip over HBM for the whole list.
+// The gates are applied in GROUPS (qsv_plan::cut_groups: consecutive gates whose targets fit four tile bits): each of the
+// 256 threads takes the 16 amplitudes of one setting of the other eight tile bits into registers, applies the group's
+// gates there and puts them back -- one LDS round trip and one barrier per group, not per gate (the benchmark circuit: 123 groups for 399 gates in 40 passes;
+// measured figures in DESIGN.md section 10).
+// Register indices are compile-time: one unrolled body per register bit (1-qubit gates) or ordered pair of them (2-qubit
+// gates) and summation form, behind a wave-uniform switch.
+// A gate's control bits outside the tile are the same for every amplitude of a tile: they decide per workgroup whether
+// the gate acts (omask); a group none of whose gates acts makes no LDS trip, and a tile on which no gate of the pass acts is
+// neither loaded nor stored.  A control bit inside the tile is a register bit (rc: amplitudes of the thread that the gate
+// skips, wave-uniform) or a thread bit (tc: the new values replace the old ones by a select).  Each gate is computed with
+// the expression and the summation order of the per-gate kernel it would have run on (tile12_body: products summed from
+// zero in kernel-index order; dense_body: low-lane combinations outer, high rows inner; k_diag: one complex product), so
+// the amplitudes are bit for bit those of the per-gate path.  A pair exchange moves registers.
+enum {
+    PASS_D2 = 0, PASS_D2X = 1, PASS_D4 = 2, PASS_D4X = 3, PASS_D4HL = 4,   // dense on 2 / 4 amplitudes, by summation form
+    PASS_PAIR = 5,                                                          // exchange of (a, b) = (1, 0) and (0, 1)
+    PASS_DIAG_T = 6, PASS_DIAG_R1 = 7, PASS_DIAG_R2 = 8, PASS_DIAG_M = 9    // diagonal, by where its selector bits sit
+};
 struct PassGate {
-    int32_t form;        // PASS_*: dense on 2 / 4 amplitudes in one of dense_body's / tile12_body's orders, or diagonal
-    int32_t z0, z1;      // dense: tile bits that are 0 in a group's base, ascending (z1 < 0: one); diagonal: the bits
-                         // that select d (d[(s0 << 1) | s1]; z1 < 0: d[s0])
-    uint32_t cmask;      // tile bits that must be 1 (controls inside the tile)
-    uint32_t off[4];     // dense: tile offset of kernel index c
+    int32_t form;        // PASS_*
+    int32_t code;        // the body of the form: register bit P of kernel bit 0 (D2*, DIAG_R1, DIAG_M), or 4 P0 + P1 for
+                         // the register bits of kernel bits 0 and 1 (D4*), of the two legs (PAIR) or P0 < P1 (DIAG_R2)
+    uint32_t rc;         // controls on register bits, as a mask of the register index 0..15
+    uint32_t tc;         // controls on thread bits, as a mask of tile indices
+    int32_t tz0, tz1;    // DIAG_T: tile indices of the thread bits s0, s1 that select d[(s0 << 1) | s1]; DIAG_M: tz0 = the
+                         // thread bit s of d[(register bit << 1) | s]
     uint64_t omask;      // register bits outside the tile that must be 1 (the same for every amplitude of a tile)
-    uint64_t pad;
-    double m[32];        // dense: D x D kernel-order matrix, (re, im) interleaved; diagonal: d[0..3]
+    double m[32];        // dense: D x D kernel-order matrix, (re, im) interleaved; diagonal: d[0..3] as the form reads them
+};
+struct PassGroup {
+    int32_t first, count;   // gates [first, first + count) of the pass
+    int32_t q[4];           // the group's register bits as tile indices, ascending
+    uint64_t gates;         // bit i = gate i of the pass belongs to the group
 };
 constexpr int PASS_TILE = 1 << qsv_plan::TILE_BITS, PASS_ROWS = PASS_TILE / 64, PASS_THREADS = 256;
 constexpr int PASS_ROWS_PER_WAVE = PASS_ROWS / (PASS_THREADS / 64);
+static_assert(PASS_TILE == PASS_THREADS << qsv_plan::REG_BITS, "one thread per setting of the tile bits outside the registers");
 
 struct PassArgs {
     BigArgs g;                     // pos[] = the 12 tile bits: the tile number is deposited around them
@@ -3030,50 +3049,135 @@ __device__ __forceinline__ constexpr int pass_col(int r, int j) {
     return FORM == 0 ? j : FORM == 1 ? (j ^ r) : (((j & 1) << 1) | ((r & 1) ^ (j >> 1)));
 }
 
-template <int D, int FORM>
-__device__ __forceinline__ void pass_dense(amp_t *__restrict__ tile, const PassGate &pg) {
-    const int count = PASS_TILE >> (pg.z1 >= 0 ? 2 : 1);
-    for (int grp = threadIdx.x; grp < count; grp += PASS_THREADS) {
-        uint32_t g0 = static_cast<uint32_t>(insert_zero(static_cast<uint64_t>(grp), pg.z0));
-        if (pg.z1 >= 0) g0 = static_cast<uint32_t>(insert_zero(g0, pg.z1));
-        if ((g0 & pg.cmask) != pg.cmask) continue;
-        amp_t x[D], y[D];
+// The controls of a gate inside the tile, as one thread sees them.
+struct PassCtl {
+    uint32_t rc;     // wave-uniform: register-index bits that must be 1
+    bool sel;        // wave-uniform: the gate has controls on thread bits
+    bool ok;         // this thread's control bits are all 1
+};
+
+__device__ __forceinline__ void pass_put(amp_t &x, amp_t y, const PassCtl &ct) {
+    if (ct.sel) {
+        x.x = ct.ok ? y.x : x.x;
+        x.y = ct.ok ? y.y : x.y;
+    } else {
+        x = y;
+    }
+}
+
+// Dense gate on D amplitudes: kernel index bit 0 <-> register bit P0, bit 1 <-> register bit P1 (D = 4).
+template <int D, int FORM, int P0, int P1>
+__device__ __forceinline__ void pass_dense(amp_t (&x)[16], const double *__restrict__ m, const PassCtl &ct) {
+    constexpr int TARGETS = (1 << P0) | (D == 4 ? (1 << P1) : 0);
 #pragma unroll
-        for (int c = 0; c < D; ++c) x[c] = tile[g0 | pg.off[c]];
+    for (int b = 0; b < 16; ++b) {
+        if (b & TARGETS) continue;
+        if ((b & ct.rc) != ct.rc) continue;      // wave-uniform: a control on a register bit is 0 here
+        int idx[D];
+#pragma unroll
+        for (int c = 0; c < D; ++c) idx[c] = b | ((c & 1) << P0) | (D == 4 ? ((c >> 1) << P1) : 0);
+        amp_t y[D];
 #pragma unroll
         for (int r = 0; r < D; ++r) {
             amp_t acc = {0.0, 0.0};
 #pragma unroll
             for (int j = 0; j < D; ++j) {
                 const int c = pass_col<FORM>(r, j);
-                acc = cfma(cplx{pg.m[2 * (r * D + c)], pg.m[2 * (r * D + c) + 1]}, x[c], acc);
+                acc = cfma(cplx{m[2 * (r * D + c)], m[2 * (r * D + c) + 1]}, x[idx[c]], acc);
             }
             y[r] = acc;
         }
 #pragma unroll
-        for (int r = 0; r < D; ++r) tile[g0 | pg.off[r]] = y[r];
+        for (int r = 0; r < D; ++r) pass_put(x[idx[r]], y[r], ct);
     }
 }
 
-__device__ __forceinline__ void pass_diag(amp_t *__restrict__ tile, const PassGate &pg) {
-    const cplx d0 = {pg.m[0], pg.m[1]}, d1 = {pg.m[2], pg.m[3]}, d2 = {pg.m[4], pg.m[5]}, d3 = {pg.m[6], pg.m[7]};
-    for (int i = threadIdx.x; i < PASS_TILE; i += PASS_THREADS) {
-        if ((static_cast<uint32_t>(i) & pg.cmask) != pg.cmask) continue;
-        const int s0 = (i >> pg.z0) & 1;
-        cplx d;
-        if (pg.z1 < 0) {
-            d = s0 ? d1 : d0;
-        } else {
-            const int s1 = (i >> pg.z1) & 1;
-            d = s0 ? (s1 ? d3 : d2) : (s1 ? d1 : d0);
-        }
-        tile[i] = cmul_diag(d, tile[i]);
+template <int PA, int PB>
+__device__ __forceinline__ void pass_pair(amp_t (&x)[16], const PassCtl &ct) {
+#pragma unroll
+    for (int b = 0; b < 16; ++b) {
+        if (b & ((1 << PA) | (1 << PB))) continue;
+        if ((b & ct.rc) != ct.rc) continue;
+        const amp_t u = x[b | (1 << PA)], v = x[b | (1 << PB)];
+        pass_put(x[b | (1 << PA)], v, ct);
+        pass_put(x[b | (1 << PB)], u, ct);
     }
+}
+
+// Diagonal gate whose factor for register index c is d[SEL(c)] (d[] per thread or wave-uniform).
+template <class Sel>
+__device__ __forceinline__ void pass_diag(amp_t (&x)[16], const cplx (&d)[4], const PassCtl &ct, Sel sel) {
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        if ((c & ct.rc) != ct.rc) continue;
+        pass_put(x[c], cmul_diag(d[sel(c)], x[c]), ct);
+    }
+}
+
+__device__ __forceinline__ cplx pass_pick(bool s, cplx one, cplx zero) {
+    return cplx{s ? one.re : zero.re, s ? one.im : zero.im};
+}
+
+__device__ __forceinline__ void pass_gate16(amp_t (&x)[16], const PassGate &pg, uint32_t g0) {
+    const double *__restrict__ m = pg.m;
+    const PassCtl ct = {pg.rc, pg.tc != 0, (g0 & pg.tc) == pg.tc};
+#define QSV_PASS_D4(FORM, P0, P1) case (FORM) * 16 + (P0) * 4 + (P1): pass_dense<4, (FORM) - PASS_D4, P0, P1>(x, m, ct); break;
+#define QSV_PASS_D4_BOTH(FORM, LO, HI) QSV_PASS_D4(FORM, LO, HI) QSV_PASS_D4(FORM, HI, LO)
+    switch (pg.form * 16 + pg.code) {     // wave-uniform (scalar loads)
+        case PASS_D2 * 16 + 0: pass_dense<2, 0, 0, 0>(x, m, ct); break;
+        case PASS_D2 * 16 + 1: pass_dense<2, 0, 1, 0>(x, m, ct); break;
+        case PASS_D2 * 16 + 2: pass_dense<2, 0, 2, 0>(x, m, ct); break;
+        case PASS_D2 * 16 + 3: pass_dense<2, 0, 3, 0>(x, m, ct); break;
+        case PASS_D2X * 16 + 0: pass_dense<2, 1, 0, 0>(x, m, ct); break;
+        case PASS_D2X * 16 + 1: pass_dense<2, 1, 1, 0>(x, m, ct); break;
+        case PASS_D2X * 16 + 2: pass_dense<2, 1, 2, 0>(x, m, ct); break;
+        case PASS_D2X * 16 + 3: pass_dense<2, 1, 3, 0>(x, m, ct); break;
+        QSV_PASS_D4_BOTH(PASS_D4, 0, 1) QSV_PASS_D4_BOTH(PASS_D4, 0, 2) QSV_PASS_D4_BOTH(PASS_D4, 0, 3)
+        QSV_PASS_D4_BOTH(PASS_D4, 1, 2) QSV_PASS_D4_BOTH(PASS_D4, 1, 3) QSV_PASS_D4_BOTH(PASS_D4, 2, 3)
+        QSV_PASS_D4_BOTH(PASS_D4X, 0, 1) QSV_PASS_D4_BOTH(PASS_D4X, 0, 2) QSV_PASS_D4_BOTH(PASS_D4X, 0, 3)
+        QSV_PASS_D4_BOTH(PASS_D4X, 1, 2) QSV_PASS_D4_BOTH(PASS_D4X, 1, 3) QSV_PASS_D4_BOTH(PASS_D4X, 2, 3)
+        // one low and one high target: the low one (kernel bit 0) has the smaller tile index, so the smaller register bit
+        QSV_PASS_D4(PASS_D4HL, 0, 1) QSV_PASS_D4(PASS_D4HL, 0, 2) QSV_PASS_D4(PASS_D4HL, 0, 3)
+        QSV_PASS_D4(PASS_D4HL, 1, 2) QSV_PASS_D4(PASS_D4HL, 1, 3) QSV_PASS_D4(PASS_D4HL, 2, 3)
+        case PASS_PAIR * 16 + 0 * 4 + 1: pass_pair<0, 1>(x, ct); break;
+        case PASS_PAIR * 16 + 0 * 4 + 2: pass_pair<0, 2>(x, ct); break;
+        case PASS_PAIR * 16 + 0 * 4 + 3: pass_pair<0, 3>(x, ct); break;
+        case PASS_PAIR * 16 + 1 * 4 + 2: pass_pair<1, 2>(x, ct); break;
+        case PASS_PAIR * 16 + 1 * 4 + 3: pass_pair<1, 3>(x, ct); break;
+        case PASS_PAIR * 16 + 2 * 4 + 3: pass_pair<2, 3>(x, ct); break;
+        case PASS_DIAG_T * 16: {       // both selector bits are thread bits: one factor per thread
+            const bool s0 = (g0 >> pg.tz0) & 1, s1 = (g0 >> pg.tz1) & 1;
+            const cplx d[4] = {pass_pick(s0, pass_pick(s1, cplx{m[6], m[7]}, cplx{m[4], m[5]}),
+                                         pass_pick(s1, cplx{m[2], m[3]}, cplx{m[0], m[1]})), {}, {}, {}};
+            pass_diag(x, d, ct, [](int) { return 0; });
+            break;
+        }
+#define QSV_PASS_R1(P) case PASS_DIAG_R1 * 16 + (P): { \
+            const cplx d[4] = {{m[0], m[1]}, {m[2], m[3]}, {}, {}}; \
+            pass_diag(x, d, ct, [](int c) { return (c >> (P)) & 1; }); break; }
+        QSV_PASS_R1(0) QSV_PASS_R1(1) QSV_PASS_R1(2) QSV_PASS_R1(3)
+#define QSV_PASS_R2(P0, P1) case PASS_DIAG_R2 * 16 + (P0) * 4 + (P1): { \
+            const cplx d[4] = {{m[0], m[1]}, {m[2], m[3]}, {m[4], m[5]}, {m[6], m[7]}}; \
+            pass_diag(x, d, ct, [](int c) { return (((c >> (P0)) & 1) << 1) | ((c >> (P1)) & 1); }); break; }
+        QSV_PASS_R2(0, 1) QSV_PASS_R2(0, 2) QSV_PASS_R2(0, 3) QSV_PASS_R2(1, 2) QSV_PASS_R2(1, 3) QSV_PASS_R2(2, 3)
+#define QSV_PASS_M(P) case PASS_DIAG_M * 16 + (P): { \
+            const bool s = (g0 >> pg.tz0) & 1; \
+            const cplx d[4] = {pass_pick(s, cplx{m[2], m[3]}, cplx{m[0], m[1]}), pass_pick(s, cplx{m[6], m[7]}, cplx{m[4], m[5]}), {}, {}}; \
+            pass_diag(x, d, ct, [](int c) { return (c >> (P)) & 1; }); break; }
+        QSV_PASS_M(0) QSV_PASS_M(1) QSV_PASS_M(2) QSV_PASS_M(3)
+        default: break;       // qsvk_pass builds no other record
+    }
+#undef QSV_PASS_D4
+#undef QSV_PASS_D4_BOTH
+#undef QSV_PASS_R1
+#undef QSV_PASS_R2
+#undef QSV_PASS_M
 }
 
 template <bool NT>
 __global__ __launch_bounds__(PASS_THREADS) void k_pass_tile(amp_t *__restrict__ a, const PassArgs pa,
-                                                            const PassGate *__restrict__ gates, int n_gates) {
+                                                            const PassGate *__restrict__ gates, int n_gates,
+                                                            const PassGroup *__restrict__ groups, int n_groups) {
     __shared__ amp_t tile[PASS_TILE];      // [row][64 lanes]: LDS index = tile index (bits 0..5 lane, 6..11 row)
     const BigArgs &g = pa.g;
     const int lane = threadIdx.x & 63;
@@ -3094,17 +3198,26 @@ __global__ __launch_bounds__(PASS_THREADS) void k_pass_tile(amp_t *__restrict__ 
 #endif
     __syncthreads();
 #pragma unroll 1
-    for (int i = 0; i < n_gates; ++i) {
-        if (!((active >> i) & 1)) continue;
-        const PassGate &pg = gates[i];
-        switch (pg.form) {     // wave-uniform (scalar loads)
-            case PASS_D2: pass_dense<2, 0>(tile, pg); break;
-            case PASS_D2X: pass_dense<2, 1>(tile, pg); break;
-            case PASS_D4: pass_dense<4, 0>(tile, pg); break;
-            case PASS_D4X: pass_dense<4, 1>(tile, pg); break;
-            case PASS_D4HL: pass_dense<4, 2>(tile, pg); break;
-            default: pass_diag(tile, pg); break;
-        }
+    for (int p = 0; p < n_groups; ++p) {
+        const PassGroup &gr = groups[p];
+        if (!(active & gr.gates)) continue;     // no gate of the group acts on this tile: no LDS trip
+        const int q0 = gr.q[0], q1 = gr.q[1], q2 = gr.q[2], q3 = gr.q[3];
+        // this thread's setting of the other eight tile bits: its index with zeros inserted at the register bits
+        uint32_t g0 = threadIdx.x;
+        g0 = static_cast<uint32_t>(insert_zero(g0, q0));
+        g0 = static_cast<uint32_t>(insert_zero(g0, q1));
+        g0 = static_cast<uint32_t>(insert_zero(g0, q2));
+        g0 = static_cast<uint32_t>(insert_zero(g0, q3));
+        amp_t x[16];
+#pragma unroll
+        for (int c = 0; c < 16; ++c)
+            x[c] = tile[g0 | ((c & 1) << q0) | (((c >> 1) & 1) << q1) | (((c >> 2) & 1) << q2) | (((c >> 3) & 1) << q3)];
+#pragma unroll 1
+        for (int i = gr.first; i < gr.first + gr.count; ++i)
+            if ((active >> i) & 1) pass_gate16(x, gates[i], g0);
+#pragma unroll
+        for (int c = 0; c < 16; ++c)
+            tile[g0 | ((c & 1) << q0) | (((c >> 1) & 1) << q1) | (((c >> 2) & 1) << q2) | (((c >> 3) & 1) << q3)] = x[c];
         __syncthreads();
     }
 #pragma unroll
@@ -3161,41 +3274,41 @@ int qsvk_pass(qsv_state *st, const QsvOp *const *ops, int count, uint64_t tile_h
         local_of[b] = qsv_plan::tile_index(b, tile_high);
         if (local_of[b] >= 0) tile_bits[local_of[b]] = b;
     }
+    // first what each gate is, in tile indices (leg[]: dense, kernel bit 0 first; pair: both legs; diagonal: the bits that
+    // select d[(s0 << 1) | s1], leg[1] < 0: d[s0], leg[0] < 0: one factor for all); then the groups; then each gate's
+    // record relative to the register bits of its group
     std::vector<PassGate> rec(count);
+    std::vector<std::array<int, 2>> leg(count, std::array<int, 2>{-1, -1});
+    std::vector<uint32_t> cmask(count, 0), need(count, 0);
     for (int i = 0; i < count; ++i) {
         const QsvOp &op = *ops[i];
         PassGate &pg = rec[i];
         std::memset(&pg, 0, sizeof(pg));
-        pg.z1 = -1;
         uint64_t ctrl = 0;
         for (int c = 0; c < op.nctrl; ++c) ctrl |= 1ull << op.cbits[c];
         const qsv_plan::ControlMasks cm = qsv_plan::control_masks(ctrl, tile_high);
-        pg.cmask = cm.inside;
+        cmask[i] = cm.inside;
         pg.omask = cm.outside;
         for (int j = 0; j < op.k; ++j)
             if (local_of[op.bits[j]] < 0) return qsv_fail(QSV_EINVAL, "internal: gate target outside its pass's tile");
         if (op.kind == QSV_OP_DIAG || op.kind == QSV_OP_PHASE) {
-            pg.form = PASS_DIAG;
-            if (op.kind == QSV_OP_PHASE) {           // k_diag with b0 = 0 and d0 = d1 = the phase (qsvk_phase)
-                pg.z0 = 0;
-                pg.m[0] = pg.m[2] = op.m[0];
-                pg.m[1] = pg.m[3] = op.m[1];
+            pg.form = PASS_DIAG_T;
+            if (op.kind == QSV_OP_PHASE) {           // k_diag with d0 = d1 = the phase (qsvk_phase)
+                for (int e = 0; e < 4; ++e) {
+                    pg.m[2 * e] = op.m[0];
+                    pg.m[2 * e + 1] = op.m[1];
+                }
             } else {
-                pg.z0 = local_of[op.bits[0]];
-                if (op.k == 2) pg.z1 = local_of[op.bits[1]];
+                leg[i][0] = local_of[op.bits[0]];
+                if (op.k == 2) leg[i][1] = local_of[op.bits[1]];
                 std::memcpy(pg.m, op.m, sizeof(double) * (2u << op.k));
             }
             continue;
         }
-        if (op.kind == QSV_OP_PAIR) {               // qsvk_pair_exchange: X between (a, b) = (1, 0) and (0, 1)
-            const int la = local_of[op.bits[0]], lb = local_of[op.bits[1]];
-            pg.form = PASS_D2;
-            pg.z0 = std::min(la, lb);
-            pg.z1 = std::max(la, lb);
-            pg.off[0] = 1u << la;
-            pg.off[1] = 1u << lb;
-            pg.m[2] = 1.0;
-            pg.m[4] = 1.0;
+        if (op.kind == QSV_OP_PAIR) {               // qsvk_pair_exchange: (a, b) = (1, 0) <-> (0, 1)
+            pg.form = PASS_PAIR;
+            leg[i] = {local_of[op.bits[0]], local_of[op.bits[1]]};
+            need[i] = (1u << leg[i][0]) | (1u << leg[i][1]);
             continue;
         }
         // dense: kernel index bit i <-> register bit kb[i], matrix re-indexed as the per-gate launcher does
@@ -3230,21 +3343,78 @@ int qsvk_pass(qsv_state *st, const QsvOp *const *ops, int count, uint64_t tile_h
                 pg.m[2 * (r * D + c)] = op.m[2 * (ur * D + uc)];
                 pg.m[2 * (r * D + c) + 1] = op.m[2 * (ur * D + uc) + 1];
             }
-        for (int c = 0; c < D; ++c)
-            for (int i2 = 0; i2 < k; ++i2)
-                if ((c >> i2) & 1) pg.off[c] |= 1u << local_of[kb[i2]];
-        const int l0 = local_of[kb[0]];
-        pg.z0 = l0;
-        if (k == 2) {
-            const int l1 = local_of[kb[1]];
-            pg.z0 = std::min(l0, l1);
-            pg.z1 = std::max(l0, l1);
+        for (int i2 = 0; i2 < k; ++i2) {
+            leg[i][i2] = local_of[kb[i2]];
+            need[i] |= 1u << leg[i][i2];
+        }
+    }
+    const std::vector<qsv_plan::Group> cut = qsv_plan::cut_groups(need);
+    std::vector<PassGroup> grp(cut.size());
+    for (size_t p = 0; p < cut.size(); ++p) {
+        PassGroup &gr = grp[p];
+        std::memset(&gr, 0, sizeof(gr));
+        gr.first = cut[p].first;
+        gr.count = cut[p].count;
+        int reg_of[qsv_plan::TILE_BITS];       // register bit of a tile index, -1: a thread bit
+        for (int t = 0; t < qsv_plan::TILE_BITS; ++t) reg_of[t] = -1;
+        for (int j = 0; j < qsv_plan::REG_BITS; ++j) {
+            gr.q[j] = cut[p].reg[j];
+            reg_of[gr.q[j]] = j;
+        }
+        for (int i = gr.first; i < gr.first + gr.count; ++i) {
+            PassGate &pg = rec[i];
+            gr.gates |= 1ull << i;
+            for (int t = 0; t < qsv_plan::TILE_BITS; ++t)
+                if ((cmask[i] >> t) & 1) {
+                    if (reg_of[t] >= 0) pg.rc |= 1u << reg_of[t];
+                    else pg.tc |= 1u << t;
+                }
+            const int l0 = leg[i][0], l1 = leg[i][1];
+            if (pg.form == PASS_DIAG_T) {
+                const int r0 = l0 >= 0 ? reg_of[l0] : -1, r1 = l1 >= 0 ? reg_of[l1] : -1;
+                auto swap_d1_d2 = [&pg]() {          // d[(s0 << 1) | s1] -> d[(s1 << 1) | s0]
+                    std::swap(pg.m[2], pg.m[4]);
+                    std::swap(pg.m[3], pg.m[5]);
+                };
+                if (l0 < 0) {                        // a phase: the same factor whatever the bits
+                    pg.tz0 = pg.tz1 = 0;
+                } else if (l1 < 0) {
+                    if (r0 >= 0) {
+                        pg.form = PASS_DIAG_R1;
+                        pg.code = r0;
+                    } else {                         // d[s0] as d[(s0 << 1) | s0]
+                        pg.m[6] = pg.m[2];
+                        pg.m[7] = pg.m[3];
+                        pg.tz0 = pg.tz1 = l0;
+                    }
+                } else if (r0 >= 0 && r1 >= 0) {
+                    pg.form = PASS_DIAG_R2;
+                    if (r0 > r1) swap_d1_d2();
+                    pg.code = std::min(r0, r1) * 4 + std::max(r0, r1);
+                } else if (r0 >= 0 || r1 >= 0) {     // d[(register bit << 1) | thread bit]
+                    pg.form = PASS_DIAG_M;
+                    if (r0 < 0) swap_d1_d2();
+                    pg.code = r0 >= 0 ? r0 : r1;
+                    pg.tz0 = r0 >= 0 ? l1 : l0;
+                } else {
+                    pg.tz0 = l0;
+                    pg.tz1 = l1;
+                }
+                continue;
+            }
+            const int r0 = reg_of[l0], r1 = l1 >= 0 ? reg_of[l1] : 0;
+            if (r0 < 0 || r1 < 0) return qsv_fail(QSV_EINVAL, "internal: gate target outside its group's register bits");
+            if (pg.form == PASS_PAIR) pg.code = std::min(r0, r1) * 4 + std::max(r0, r1);
+            else if (pg.form == PASS_D2 || pg.form == PASS_D2X) pg.code = r0;
+            else pg.code = r0 * 4 + r1;
         }
     }
     StageRef staged;
-    int rc = qsvk_stage(st, rec.data(), sizeof(PassGate) * rec.size(), nullptr, 0, &staged);
+    int rc = qsvk_stage(st, rec.data(), sizeof(PassGate) * rec.size(), grp.data(), sizeof(PassGroup) * grp.size(), &staged);
     if (rc) return rc;
     const PassGate *dev_g = reinterpret_cast<const PassGate *>(staged.dev);
+    const PassGroup *dev_p = reinterpret_cast<const PassGroup *>(staged.dev + qsv_pad16(sizeof(PassGate) * rec.size()));
+    const int n_groups = static_cast<int>(grp.size());
     PassArgs pa;
     std::memset(&pa, 0, sizeof(pa));
     BigArgs &g = pa.g;
@@ -3260,8 +3430,8 @@ int qsvk_pass(qsv_state *st, const QsvOp *const *ops, int count, uint64_t tile_h
     const uint64_t per_launch = 1ull << 23;       // tiles per dispatch (a power of two: the tile order stays whole)
     for (g.w0 = 0; g.w0 < g.W; g.w0 += per_launch) {
         const dim3 gd(static_cast<unsigned>(std::min(per_launch, g.W - g.w0))), bd(PASS_THREADS);
-        if (nt) hipLaunchKernelGGL(k_pass_tile<true>, gd, bd, 0, st->stream, st->data, pa, dev_g, count);
-        else hipLaunchKernelGGL(k_pass_tile<false>, gd, bd, 0, st->stream, st->data, pa, dev_g, count);
+        if (nt) hipLaunchKernelGGL(k_pass_tile<true>, gd, bd, 0, st->stream, st->data, pa, dev_g, count, dev_p, n_groups);
+        else hipLaunchKernelGGL(k_pass_tile<false>, gd, bd, 0, st->stream, st->data, pa, dev_g, count, dev_p, n_groups);
         rc = check_launch();
         if (rc) return rc;
     }

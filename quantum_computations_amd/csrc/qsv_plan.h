@@ -6,7 +6,8 @@
 // queued gates to it and writes it back (k_pass_tile): one round trip over HBM instead of one per gate.  A gate fits a pass
 // when its target bits are tile bits; its control bits may lie anywhere -- inside the tile they select amplitudes, outside it
 // they select whole tiles (the same bits for every amplitude of a tile).  A CZ on two bits is all controls, a CX's control
-// may stay outside the tile.
+// may stay outside the tile.  Inside the kernel the gates of a pass are applied in GROUPS (cut_groups): consecutive gates whose
+// targets fit four tile bits are applied in registers, 16 amplitudes per thread, with one LDS round trip per group.
 //
 // Ordering.  The gates of a pass keep queue order, with one exception: a gate that is a signed permutation (CX, CZ, SWAP,
 // X, Z: every matrix entry 0 or +-1) may move ahead of earlier queued gates that act on none of its qubits.  Such a gate
@@ -26,19 +27,25 @@ constexpr int HIGH_BITS = TILE_BITS - LANE_BITS;    // further tile bits chosen 
 constexpr int MAX_PASS_GATES = 64;                  // gates per pass (the kernel keeps one activity bit per gate)
 constexpr uint64_t LOW_MASK = (1ull << LANE_BITS) - 1;
 
+constexpr int REG_BITS = 4;                         // tile bits a thread of k_pass_tile holds in registers (16 amplitudes)
+
 // Cost model, in units of one full pass of a per-gate kernel over the register (k_dense_tile12<1> at n = 28: 1.31 ms).
-// k_pass_tile on the benchmark circuit (profiles/r04_pass_costs.txt): 1.95-4.48 ms for 6-20 gates, least squares
-// 0.99 ms + 0.172 ms per gate (0.75 + 0.131 per gate in these units); the intercept is rounded up to one full pass, below
-// which no pass over HBM can go.  A pass costs PASS_BASE times the fraction of tiles it loads plus PASS_PER_GATE per
-// gate; a gate launched on its own costs what qsv_api.hip (plan_gate) gives its kind.
+// k_pass_tile applies a pass's gates in GROUPS (cut_groups below): one LDS round trip and one barrier per group, the
+// gates of a group in registers.  On the benchmark circuit (profiles/r05_pass_costs.txt): 1.77-3.67 ms for 6-20 gates in
+// 2-5 groups, least squares 0.85 ms + 0.160 ms per group + 0.101 ms per gate (0.65 + 0.122 per group + 0.077 per gate in
+// these units); the intercept is rounded up to one full pass, below which no pass over HBM can go.  A pass costs
+// PASS_BASE times the fraction of tiles it loads plus PASS_PER_GROUP per group plus PASS_PER_GATE per gate; a gate
+// launched on its own costs what qsv_api.hip (plan_gate) gives its kind.
 constexpr float PASS_BASE = 1.0f;
-constexpr float PASS_PER_GATE = 0.13f;
+constexpr float PASS_PER_GROUP = 0.12f;
+constexpr float PASS_PER_GATE = 0.08f;
 
 struct Gate {
     uint64_t need = 0;   // register bits that must be tile bits (target legs)
     uint64_t ctrl = 0;   // register bits that must be 1 for the gate to act (controls, the bits of a phase)
     bool exact = false;  // a signed permutation: may move ahead of earlier gates on disjoint bits
     float cost = 1.0f;   // its per-gate launch, in full passes
+    bool dense = true;   // false: a diagonal gate (it scales amplitudes in place and needs no register bits of a group)
 };
 
 struct Pass {
@@ -84,8 +91,70 @@ inline float active_fraction(const std::vector<Gate> &q, const std::vector<int> 
     return frac;
 }
 
+// One group of a pass: gates [first, first + count) of the pass's ordered list, applied on the 16 amplitudes of the four
+// tile indices reg[] (ascending) that a thread holds in registers.
+struct Group {
+    int first = 0, count = 0;
+    int reg[REG_BITS] = {0, 0, 0, 0};
+};
+
+// Cut the gates of one pass into groups.  need[i]: the target bits of gate i as a mask of tile indices (0 .. tile_bits -
+// 1), in application order; a gate without targets (phases, CZ, diagonal gates: they only scale amplitudes, wherever
+// their bits sit) has need 0.  A group is a maximal run of consecutive gates whose targets together occupy at most REG_BITS
+// tile indices: a gate joins the open group when it fits, otherwise it closes the group and opens the next.  Nothing is
+// reordered.  A gate without targets always fits, so it never opens a group unless it is first in the pass.  A group's
+// register bits are completed to REG_BITS with the highest unused tile indices: the low tile bits then stay thread bits,
+// so that consecutive lanes read consecutive 16-byte amplitudes of LDS.
+inline std::vector<Group> cut_groups(const std::vector<uint32_t> &need, int tile_bits = TILE_BITS) {
+    std::vector<Group> out;
+    std::vector<uint32_t> masks;
+    uint32_t cur = 0;
+    for (int i = 0; i < static_cast<int>(need.size()); ++i) {
+        const uint32_t grown = cur | need[i];
+        if (out.empty() || popcount64(grown) > REG_BITS) {
+            if (!out.empty()) masks.push_back(cur);
+            Group g;
+            g.first = i;
+            out.push_back(g);
+            cur = need[i];
+        } else {
+            cur = grown;
+        }
+        ++out.back().count;
+    }
+    if (!out.empty()) masks.push_back(cur);
+    for (size_t k = 0; k < out.size(); ++k) {
+        uint32_t m = masks[k];
+        for (int t = tile_bits - 1; t >= 0 && popcount64(m) < REG_BITS; --t)
+            if (!((m >> t) & 1)) m |= 1u << t;
+        int w = 0;
+        for (int t = 0; t < tile_bits && w < REG_BITS; ++t)
+            if ((m >> t) & 1) out[k].reg[w++] = t;
+    }
+    return out;
+}
+
+// A gate's targets as tile indices for cut_groups: `need` restricted to dense gates (has_targets), 0 for the others.
+inline uint32_t need_in_tile(uint64_t need, uint64_t tile) {
+    uint32_t m = 0;
+    for (int b = 0; b < 64; ++b)
+        if ((need >> b) & 1) {
+            const int t = tile_index(b, tile);
+            if (t >= 0) m |= 1u << t;
+        }
+    return m;
+}
+
+inline int count_groups(const std::vector<Gate> &q, const std::vector<int> &gates, uint64_t tile) {
+    std::vector<uint32_t> need;
+    need.reserve(gates.size());
+    for (int i : gates) need.push_back(q[i].dense ? need_in_tile(q[i].need, tile) : 0u);
+    return static_cast<int>(cut_groups(need).size());
+}
+
 inline float pass_cost(const std::vector<Gate> &q, const std::vector<int> &gates, uint64_t tile) {
-    return PASS_BASE * active_fraction(q, gates, tile) + PASS_PER_GATE * static_cast<float>(gates.size());
+    return PASS_BASE * active_fraction(q, gates, tile) + PASS_PER_GROUP * static_cast<float>(count_groups(q, gates, tile)) +
+           PASS_PER_GATE * static_cast<float>(gates.size());
 }
 
 // The first pass of the queue q on an n-qubit register (n >= TILE_BITS): gate 0 and every later gate that can join it in

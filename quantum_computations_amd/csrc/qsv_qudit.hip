@@ -24,6 +24,16 @@ __device__ __forceinline__ amp_t cfma(cplx m, amp_t a, amp_t acc) {
     return amp_t{fma(m.re, a.x, fma(-m.im, a.y, acc.x)), fma(m.re, a.y, fma(m.im, a.x, acc.y))};
 }
 
+// acc + m * a with every product and every sum rounded on its own, in the order written: the arithmetic of the
+// reference's resampling, which weights and adds the four corners of a cell one after the other (gates.py:74-80 through
+// RegularGridInterpolator; a NumPy `out += w * v` per table column).  A fused chain rounds each partial sum once
+// instead of twice, and where the four terms of a row nearly cancel the two differ by many ulps of what is left.
+__device__ __forceinline__ amp_t cadd_rounded(amp_t acc, cplx m, amp_t a) {
+#pragma clang fp contract(off)
+    const double re = m.re * a.x - m.im * a.y, im = m.re * a.y + m.im * a.x;
+    return amp_t{acc.x + re, acc.y + im};
+}
+
 // ----------------------------------------------------------------------------------------------------
 // out[l, i, r] = sum_j M[i, j] in[l, j, r]   (L, d_in, R) -> (L, d_out, R)
 //
@@ -188,7 +198,7 @@ __global__ __launch_bounds__(QSV_BLOCK) void k_mode2_gather(const amp_t *__restr
             const int32_t c = cols[row + k];
             if (c < 0) continue;  // padding entry
             const cplx w = {vals[2 * (row + k)], vals[2 * (row + k) + 1]};
-            acc = cfma(w, in[base + (c / d) * s0 + (c % d) * s1], acc);
+            acc = cadd_rounded(acc, w, in[base + (c / d) * s0 + (c % d) * s1]);
         }
         out[o] = acc;
     }

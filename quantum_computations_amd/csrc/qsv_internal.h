@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "qsv.h"
+#include "qsv_layout.h"
 
 // One amplitude = complex128 = one 16-byte vector: exactly one dwordx4 per lane, 1 KiB per wave64 access.
 typedef double amp_t __attribute__((ext_vector_type(2)));
@@ -51,18 +52,10 @@ struct DiagArgs {
     double d[8];
 };
 
-// One 1- or 2-qubit gate as the per-gate launcher runs it (qsvk_run_op): the classification of qsv_apply_* (diagonal,
-// phase, CX / controlled-U, SWAP as a pair exchange, dense) with everything held by value, so that it can wait in a queue.
-enum { QSV_OP_DENSE = 0, QSV_OP_PAIR = 1, QSV_OP_DIAG = 2, QSV_OP_PHASE = 3 };
-constexpr int QSV_OP_MAX_CTRL = 40;
-struct QsvOp {
-    int kind = QSV_OP_DENSE;
-    int k = 0;                        // target legs (dense, diag: 1 or 2; pair: 2; phase: 0)
-    int bits[2] = {-1, -1};           // target bits, leg 0 first (leg 0 = most significant matrix index bit)
-    int nctrl = 0;
-    int cbits[QSV_OP_MAX_CTRL] = {};  // control bits (phase: the bits that must all be 1)
-    double m[32] = {};                // dense: 2^k x 2^k row-major complex; diag: 2^k complex; phase: (re, im)
-};
+// One queued 1- or 2-qubit gate (qsv_layout.h, where the pass records are made from it).
+using QsvOp = qsv_layout::Op;
+enum { QSV_OP_DENSE = qsv_layout::OP_DENSE, QSV_OP_PAIR = qsv_layout::OP_PAIR, QSV_OP_DIAG = qsv_layout::OP_DIAG, QSV_OP_PHASE = qsv_layout::OP_PHASE };
+constexpr int QSV_OP_MAX_CTRL = qsv_layout::OP_MAX_CTRL;
 
 struct qsv_state {
     int device = 0;
@@ -97,12 +90,14 @@ struct qsv_state {
     int ubit = 8;
     int remap = -1;                   // tile order: -1 = per-kernel default, 0 = plain, R = regions
     int kq_variant = 0;               // k = 3..5 gates: 0 = per-case choice, 1 = wave shuffles (k_dense_big<K, KL>),
-                                      // 2 = no transpose (per-thread strided access), 3 = line-granular (k_dense_lds)
+                                      // 2 = no transpose (per-thread strided access), 3 = line-granular (k_dense_lds),
+                                      // 4 = workgroup tile (k_dense_tile), 5 = matrix cores for k = 5 (k_dense_mfma),
+                                      // 6 = tile-fed matrix cores for complex k = 5 (k_dense_mtile5)
     int last_passes = 0;              // k_seq_tile: LDS passes of the last gate list (diagnostics)
     int tile_sequence_gates = -1;     // qsv_apply_sequence: longest gate list applied on LDS tiles (-1 = built-in, 0 = never)
     int sequence_work = -1;           // qsv_apply_sequence: multiply-add limit per 32 amplitudes (-1 = built-in, 0 = never)
-    int complex_product = 0;          // complex 5- / 6-qubit blocks: 0 = three real multiplications per entry (3M),
-                                      // 4 = the four-multiplication form (measurement variant)
+    int complex_product = 0;          // complex 5- / 6-qubit blocks: 0 = three real multiplications per entry (3M) on the
+                                      // matrix cores, 3 = on the vector kernels too, 4 = four everywhere (measurement variants)
     int readout_variant = 0;          // measurement / insertion / permutation / table diagonals: 0 = streaming forms,
                                       // 1 = round-1 grid-stride forms
     int plane_kernel = 1;             // block-diagonal two-mode operators on the last two modes: 1 = workgroup-per-plane

@@ -14,6 +14,7 @@
 // (simulators/dv_simulator/gates.py:44-54, numpy_quantum.py:243-247).
 
 #include "qsv_internal.h"
+#include "qsv_layout.h"
 #include "qsv_plan.h"
 
 #include <algorithm>
@@ -22,6 +23,9 @@
 #include <cstring>
 #include <type_traits>
 #include <vector>
+
+using namespace qsv_layout;   // the argument and record types of the kernels, and the host-side tables the launchers fill them from
+static_assert(LANE_BITS == QSV_LANE_BITS && MAX_K == QSV_MAX_K && BLOCK == QSV_BLOCK, "qsv_layout.h and qsv_internal.h agree");
 
 namespace {
 
@@ -309,15 +313,6 @@ __global__ __launch_bounds__(QSV_BLOCK) void k_generic(amp_t *__restrict__ a, co
 // bits E_j instead, and the wave then swaps the roles of lane bit L_j and register bit e_j with KL butterfly
 // stages of wave64 shuffles (a distributed transpose): afterwards every thread holds one complete group.  The
 // same stages, applied to the outputs, restore the memory layout before the coalesced stores.
-struct BigArgs {
-    uint64_t W;
-    int32_t nins;
-    uint32_t pos[2 * QSV_MAX_K];  // ascending: high targets and stand-in bits
-    uint64_t or_mask;            // unused (0); lets deposit() serve this struct too
-    uint64_t w0;                 // first work item of this launch (registers beyond 2^32 work items take several)
-    uint32_t regions;            // tile order (see GateArgs::remap)
-    int32_t lbit[QSV_MAX_K];     // lane-bit position of low target j (register index bit j)
-};
 
 template <int D, int KL>
 __device__ __forceinline__ void wave_transpose(amp_t (&x)[D], const BigArgs &g, int lane) {
@@ -426,19 +421,6 @@ __global__ __launch_bounds__(QSV_BLOCK) void k_dense_big(amp_t *__restrict__ a, 
 // accumulator, so the thread holds the 2^K inputs (K = 5: 128 VGPRs) and nothing else: 3 waves per SIMD instead of
 // one, and the next wave's loads overlap this wave's arithmetic.
 // ----------------------------------------------------------------------------------------------------
-struct LdsArgs {
-    uint64_t W;
-    int32_t nins;
-    uint32_t pos[2 * QSV_MAX_K];  // ascending: high targets and stand-in bits
-    uint64_t or_mask;            // unused (0); lets deposit() serve this struct too
-    uint64_t w0;                 // first work item of this launch
-    uint32_t regions;            // tile order (see GateArgs::remap)
-    uint32_t amask;              // lane bits of the A targets
-    int32_t abit[3], aE[3];      // A target j: lane bit, stand-in bit
-    int32_t na;                  // number of A targets
-    uint32_t bdep[8];            // dep(v): the KB bits of v spread onto the lane bits of the B targets
-    uint32_t bmask;              // lane bits of the B targets
-};
 
 // The LDS rows are private to a wave (a wave exchanges data with itself only), and the LDS executes one wave's
 // instructions in order: no workgroup barrier is needed, only the compiler must keep the program order of the
@@ -531,12 +513,6 @@ __global__ __launch_bounds__(BLOCK) void k_dense_lds(amp_t *__restrict__ a, cons
 // register ARRAY must be indexed statically: one unrolled body per register bit (1-qubit gates) and per pair of register
 // bits (2-qubit gates, leg 0 canonicalised onto the higher bit by the host), selected by a wave-uniform switch.
 // ----------------------------------------------------------------------------------------------------
-struct SeqGate {
-    int32_t code;      // 0..4: 1-qubit gate on register bit `code`; 5 + p: 2-qubit gate on the p-th pair (hi, lo), hi > lo
-    int32_t pad[3];
-    double m[32];      // 2 x 2 or 4 x 4 row-major complex; 2-qubit: matrix index bit 1 <-> register bit hi
-};
-constexpr int SEQ_MAX_GATES = 48;
 static int seq_max_work() {
     static const int v = [] {
         const char *e = getenv("QSV_SEQUENCE_WORK");
@@ -2009,20 +1985,34 @@ int qsvk_adopt(qsv_state *st, uint64_t new_amps) {
     return QSV_OK;
 }
 
-// k = 3..5 on any register with at least k qubits.
-template <int K, int KL>
-static void launch_big_kernel(qsv_state *st, bool nt, dim3 gd, const BigArgs &g, const double *dev_m, const uint64_t *dev_off,
-                              bool m3 = false) {
-    const dim3 bd(QSV_BLOCK);
-    if constexpr (K == 5 && KL == 0) {
-        if (m3) {
-            if (nt) hipLaunchKernelGGL((k_dense_big<K, KL, true, true>), gd, bd, 0, st->stream, st->data, g, dev_m, dev_off);
-            else hipLaunchKernelGGL((k_dense_big<K, KL, false, true>), gd, bd, 0, st->stream, st->data, g, dev_m, dev_off);
-            return;
-        }
+// A runtime bool or small int as a compile-time constant for a generic lambda: f(std::true_type / std::false_type), or
+// f(std::integral_constant<int, v>) for v in LO..HI (any other value takes HI).  What f returns is passed on.
+template <class F>
+static auto with_bool(bool v, F &&f) {
+    return v ? f(std::true_type{}) : f(std::false_type{});
+}
+template <int LO, int HI, class F>
+static auto with_int(int v, F &&f) {
+    if constexpr (LO < HI) {
+        if (v != LO) return with_int<LO + 1, HI>(v, f);
     }
-    if (nt) hipLaunchKernelGGL((k_dense_big<K, KL, true>), gd, bd, 0, st->stream, st->data, g, dev_m, dev_off);
-    else hipLaunchKernelGGL((k_dense_big<K, KL, false>), gd, bd, 0, st->stream, st->data, g, dev_m, dev_off);
+    return f(std::integral_constant<int, LO>{});
+}
+
+// The dispatches of one launch of g.W work items, at most `limit` each: launch(count) with g.w0 set to the range's start.
+template <class Args, class Launch>
+static int launch_ranges(Args &g, uint64_t limit, Launch &&launch) {
+    for (const Range &r : dispatch_ranges(g.W, limit)) {
+        g.w0 = r.w0;
+        launch(r.count);
+        const int rc = check_launch();
+        if (rc) return rc;
+    }
+    return QSV_OK;
+}
+
+static uint32_t regions_or(const qsv_state *st, uint32_t by_default) {   // QSV_OPT_REMAP overrides a form's tile order
+    return st->remap >= 0 ? static_cast<uint32_t>(st->remap) : by_default;
 }
 
 // ---- k-qubit dense gate, targets on bits >= 3, staged through LDS: "tile" form -------------------------------------
@@ -2109,13 +2099,7 @@ __global__ __launch_bounds__((1 << K) / ROWS * 64) void k_dense_tile(amp_t *__re
 // a thread takes the 16 amplitudes of one group of the pass's four bits into registers, applies the pass's gates there
 // (seq_apply*: compile-time register indices behind a wave-uniform switch) and puts them back -- one LDS round trip and one
 // barrier per pass instead of one per gate.
-struct TilePass {
-    int32_t first, count;      // gates [first, first + count) of the SeqGate list (codes relative to the pass's four bits)
-    int32_t q[4];              // the pass's tile bits, ascending
-    int32_t pad[2];
-};
 
-constexpr int TILE_SEQ_BITS = 12, TILE_SEQ_ROWS = 1 << (TILE_SEQ_BITS - 6), TILE_SEQ_THREADS = 256, TILE_SEQ_MAX_PASSES = 24;
 constexpr int TILE_SEQ_ROWS_PER_WAVE = TILE_SEQ_ROWS / (TILE_SEQ_THREADS / 64);
 
 struct TileSeqArgs {
@@ -2285,10 +2269,6 @@ __global__ __launch_bounds__(QSV_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)
 // 1- and 2-qubit gates in the same form: one wave per input row (2 / 4 waves per workgroup), the matrix and the row
 // offsets in the kernel arguments.  On the benchmark circuit's placements 4-8 % faster than the register form (k_dense):
 // 1.28-1.34 ms against 1.31-1.48 per 1-qubit gate at n = 28, 1.36 against 1.48 on average over all pairs of bits >= 6.
-struct SmallGate {
-    double m[32];      // [row][col] (re, im), kernel index bit i <-> leg i
-    uint64_t off[4];   // amplitude offset of input / output row c
-};
 
 template <int K, bool NT>
 __device__ __forceinline__ void tile12_body(amp_t *__restrict__ a, const BigArgs &g, const SmallGate &sg) {
@@ -2324,197 +2304,38 @@ __global__ __launch_bounds__((1 << K) * 64) void k_dense_tile12_ctrl(amp_t *__re
     tile12_body<K, NT>(a, g, sg);
 }
 
-template <int K, int ROWS>
-static int launch_tile_kernel(qsv_state *st, bool nt, bool realm, dim3 gd, const BigArgs &g, const double *m,
-                              const uint64_t *dev_off, bool m3 = false) {
-    const dim3 bd((1 << K) / ROWS * 64);
-    if constexpr (K == 5) {
-        if (m3) {
-            if (nt) hipLaunchKernelGGL((k_dense_tile<K, ROWS, false, true, true>), gd, bd, 0, st->stream, st->data, g, m, dev_off);
-            else hipLaunchKernelGGL((k_dense_tile<K, ROWS, false, false, true>), gd, bd, 0, st->stream, st->data, g, m, dev_off);
-            return check_launch();
-        }
-    }
-    if (nt) {
-        if (realm) hipLaunchKernelGGL((k_dense_tile<K, ROWS, true, true>), gd, bd, 0, st->stream, st->data, g, m, dev_off);
-        else hipLaunchKernelGGL((k_dense_tile<K, ROWS, false, true>), gd, bd, 0, st->stream, st->data, g, m, dev_off);
-    } else {
-        if (realm) hipLaunchKernelGGL((k_dense_tile<K, ROWS, true, false>), gd, bd, 0, st->stream, st->data, g, m, dev_off);
-        else hipLaunchKernelGGL((k_dense_tile<K, ROWS, false, false>), gd, bd, 0, st->stream, st->data, g, m, dev_off);
-    }
-    return check_launch();
-}
-
-// Tile order of k_dense_tile / k_dense_tile12 by target placement.  Which DRAM channels the workgroups in flight hit
-// together depends on the target bits; no single order wins everywhere: contiguous windows (the d = 2^K modes of the CV
-// path) have a clear best order per position, scattered targets (fused qubit gates) are served well by 4 regions
-// (K = 3) / 2 (K = 4) / 8 (K = 5).
-// The rule is keyed on ABSOLUTE bit positions -- on the physical address bits a target toggles -- not on the distance
-// from the register's top bit: the same bits want the same order on registers of 25, 26, 27, 28, 29 and 31 qubits
-// (the shard sizes of the strong- and weak-scaling runs and of config 3; profiles/r03_tile_order_by_size.txt: bits 3-6
-// want 2 regions, 17 / 21 / 25 eight, 20 / 22 / 23 four at every size, and a pair (lo >= 17, 27) wants four regions
-// whether bit 27 is the top bit (n = 28) or not (n = 29, 31)).  Against the best of {0, 2, 4, 8, 16} regions per
-// placement the rule is within 0.7-2.5 % on the sum over the sampled placements at every size.
-static uint32_t tile_regions(int k, const std::vector<int> &sorted_bits) {
-    if (k == 1) {   // per target bit
-        const int b = sorted_bits[0];
-        return b <= 6 ? 2 : b == 7 ? 8 : b <= 16 ? 0 : b == 17 ? 8 : b <= 19 ? 0 : b == 20 ? 4 : b == 21 ? 8
-             : b <= 23 ? 4 : b == 25 ? 8 : 0;
-    }
-    if (k == 2) {   // pairs of bits >= 6 (lower targets stay on the register form)
-        const int lo = sorted_bits[0], hi = sorted_bits[1];
-        if (lo <= 8) {
-            // 8 regions, except where both strides are short: (7|8, <= 17), (6, <= 11) and (6..8, 24) run 3-12 % faster in
-            // plain order at every size
-            if ((lo >= 7 && hi <= 17) || (lo == 6 && hi <= 11) || hi == 24) return 0;
-            return 8;
-        }
-        if (hi == 20 && lo >= 12 && lo <= 16) return 0;
-        if (hi >= 20 && hi <= 21) return 8;
-        if (hi == 22) return lo >= 13 ? 4 : 8;
-        if (hi == 23 && lo >= 20) return 8;
-        if (hi == 24 && lo >= 18) return 4;
-        if (hi == 26 && lo == 22) return 4;
-        if ((hi == 27 && lo >= 17) || (hi == 28 && lo >= 20)) return 4;
-        return 0;
-    }
-    const int lo = sorted_bits.front(), top = sorted_bits.back();
-    const bool window = top - lo == static_cast<int>(sorted_bits.size()) - 1;
-    if (k == 3) {
-        if (!window) return 4;
-        return top <= 8 ? 4 : top <= 19 ? 2 : top <= 22 ? 8 : top <= 24 ? 2 : 0;
-    }
-    if (k == 4) {
-        if (!window) return 2;
-        return top <= 10 ? 4 : top <= 15 ? 2 : top <= 19 ? 0 : top == 20 ? 2 : top <= 23 ? 8 : 2;
-    }
-    if (!window) return 8;
-    return top <= 11 ? 8 : top <= 13 ? 4 : top <= 20 ? 0 : 2;
-}
 
 // the dispatches of one tile-form gate (registers beyond 2^24 tiles take several); `sub`: the reduced-traffic symbol
 static int launch_tile12_kernels(qsv_state *st, int k, bool sub, BigArgs g, const SmallGate &sg) {
     const bool nt = st->nontemporal != 0;
     snprintf(st->last_kernel, sizeof(st->last_kernel), "k_dense_tile12%s<%d, %s>", sub ? "_ctrl" : "", k, nt ? "true" : "false");
-    // columns per dispatch: a power of two, so that every dispatch of a split launch has a tile count the region
-    // order divides (with 2^24 - 1 tiles per dispatch a 31-qubit shard ran its 1-qubit gates in plain order: 12.0 ms
-    // on bits 3..6 against 10.9 for the register form, profiles/r03_tile_order_by_size.txt)
-    const uint64_t per_launch = (1ull << 23) * 64;
-    for (g.w0 = 0; g.w0 < g.W; g.w0 += per_launch) {
-        const dim3 gd(static_cast<unsigned>(std::min(per_launch, g.W - g.w0) / 64)), bd((1 << k) * 64);
-        if (sub) {
-            if (nt) hipLaunchKernelGGL((k_dense_tile12_ctrl<1, true>), gd, bd, 0, st->stream, st->data, g, sg);
-            else hipLaunchKernelGGL((k_dense_tile12_ctrl<1, false>), gd, bd, 0, st->stream, st->data, g, sg);
-        } else if (k == 1) {
-            if (nt) hipLaunchKernelGGL((k_dense_tile12<1, true>), gd, bd, 0, st->stream, st->data, g, sg);
-            else hipLaunchKernelGGL((k_dense_tile12<1, false>), gd, bd, 0, st->stream, st->data, g, sg);
-        } else {
-            if (nt) hipLaunchKernelGGL((k_dense_tile12<2, true>), gd, bd, 0, st->stream, st->data, g, sg);
-            else hipLaunchKernelGGL((k_dense_tile12<2, false>), gd, bd, 0, st->stream, st->data, g, sg);
-        }
-        const int rc = check_launch();
-        if (rc) return rc;
-    }
-    return QSV_OK;
-}
-
-// Does a dense 1- / 2-qubit gate take the tile form (k_dense_tile12*)?  Otherwise it runs on k_dense / k_dense_ctrl.  The
-// pass kernel (k_pass_tile) asks too: it sums each gate's products in the order of the kernel the gate would have run on.
-static bool tile12_takes(const qsv_state *st, int k, const int *bits, int nctrl, const int *cbits) {
-    if (k + nctrl > 2 * QSV_MAX_K || (nctrl && k != 1)) return false;   // controlled 4 x 4 gates only arise with a folded narrow control
-    for (int i = 0; i < nctrl; ++i)
-        if (cbits[i] < 3) return false;   // a control inside a 128-byte line cannot be skipped
-    const uint64_t W = st->amps >> (k + nctrl);
-    const int lowest = k == 1 ? bits[0] : std::min(bits[0], bits[1]);
-    // 2-qubit gates with a target inside a wavefront (bits 3..5) are better off with k_dense<1, 1> (1.29-1.37 ms)
-    return !(lowest < (k == 1 ? 3 : QSV_LANE_BITS) || W < 64 || W % 64);
+    return launch_ranges(g, DISPATCH_TILES * 64, [&](uint64_t columns) {
+        const dim3 gd(static_cast<unsigned>(columns / 64)), bd((1 << k) * 64);
+        with_bool(nt, [&](auto NT) {
+            if (sub) hipLaunchKernelGGL((k_dense_tile12_ctrl<1, NT.value>), gd, bd, 0, st->stream, st->data, g, sg);
+            else if (k == 1) hipLaunchKernelGGL((k_dense_tile12<1, NT.value>), gd, bd, 0, st->stream, st->data, g, sg);
+            else hipLaunchKernelGGL((k_dense_tile12<2, NT.value>), gd, bd, 0, st->stream, st->data, g, sg);
+        });
+    });
 }
 
 static int launch_tile12(qsv_state *st, int k, const int *bits, int nctrl, const int *cbits, const double *m_user) {
-    const int D = 1 << k;
-    if (!tile12_takes(st, k, bits, nctrl, cbits)) return QSV_UNHANDLED_KQ;
-    const uint64_t W = st->amps >> (k + nctrl);
-    SmallGate sg;
+    if (!tile12_takes(st->amps, k, bits, nctrl, cbits)) return QSV_UNHANDLED_KQ;
+    SmallGate sg;    // kernel index bit i <-> leg i
     std::memset(&sg, 0, sizeof(sg));
-    int ui[4];
-    for (int c = 0; c < D; ++c) {
-        ui[c] = 0;
-        for (int leg = 0; leg < k; ++leg) {
-            if ((c >> leg) & 1) sg.off[c] |= 1ull << bits[leg];
-            ui[c] |= ((c >> leg) & 1) << (k - 1 - leg);
-        }
-    }
-    for (int r = 0; r < D; ++r)
-        for (int c = 0; c < D; ++c) {
-            sg.m[2 * (r * D + c)] = m_user[2 * (ui[r] * D + ui[c])];
-            sg.m[2 * (r * D + c) + 1] = m_user[2 * (ui[r] * D + ui[c]) + 1];
-        }
+    const std::vector<uint64_t> off = offsets(std::vector<int>(bits, bits + k));
+    std::copy(off.begin(), off.end(), sg.off);
+    write_matrix(MAT_COMPLEX, 1 << k, m_user, user_index(k, bits, bits).data(), sg.m);
     std::vector<int> sorted(bits, bits + k);
     std::sort(sorted.begin(), sorted.end());
     std::vector<int> ins(sorted);
     ins.insert(ins.end(), cbits, cbits + nctrl);
-    std::sort(ins.begin(), ins.end());
-    BigArgs g;
-    std::memset(&g, 0, sizeof(g));
-    g.W = W;
-    g.nins = k + nctrl;
-    for (int j = 0; j < k + nctrl; ++j) g.pos[j] = static_cast<uint32_t>(ins[j]);
-    for (int i = 0; i < nctrl; ++i) g.or_mask |= 1ull << cbits[i];
+    uint64_t or_mask = 0;
+    for (int i = 0; i < nctrl; ++i) or_mask |= 1ull << cbits[i];
+    BigArgs g = with_enumeration<BigArgs>(enumeration(st->amps >> (k + nctrl), ins, or_mask));
     // controlled launches (CX on 40 random control / target pairs: 0.686 ms with 8 regions, 0.734 for k_dense_ctrl)
-    g.regions = st->remap >= 0 ? static_cast<uint32_t>(st->remap) : nctrl ? 8 : tile_regions(k, sorted);
+    g.regions = regions_or(st, nctrl ? 8 : tile_regions(k, sorted));
     return launch_tile12_kernels(st, k, nctrl != 0, g, sg);
-}
-
-template <int K>
-static int dispatch_big(qsv_state *st, int KL, bool nt, dim3 gd, const BigArgs &g, const double *dev_m, const uint64_t *dev_off,
-                        bool m3 = false) {
-    switch (KL) {
-        case 0: launch_big_kernel<K, 0>(st, nt, gd, g, dev_m, dev_off, m3); break;
-        case 1: launch_big_kernel<K, 1>(st, nt, gd, g, dev_m, dev_off); break;
-        case 2: launch_big_kernel<K, 2>(st, nt, gd, g, dev_m, dev_off); break;
-        case 3: launch_big_kernel<K, 3>(st, nt, gd, g, dev_m, dev_off); break;
-        case 4:
-            if constexpr (K >= 4) launch_big_kernel<K, 4>(st, nt, gd, g, dev_m, dev_off);
-            break;
-        default:
-            if constexpr (K >= 5) launch_big_kernel<K, 5>(st, nt, gd, g, dev_m, dev_off);
-            break;
-    }
-    return check_launch();
-}
-
-
-
-template <int K, int KB, int BLOCK>
-static void launch_lds_kernel(qsv_state *st, bool nt, bool realm, dim3 gd, const LdsArgs &g, const double *dev_m,
-                              const uint64_t *dev_off, bool m3 = false) {
-    const dim3 bd(BLOCK);
-    if constexpr (K == 5) {
-        if (m3) {
-            if (nt) hipLaunchKernelGGL((k_dense_lds<K, KB, true, false, BLOCK, true>), gd, bd, 0, st->stream, st->data, g, dev_m, dev_off);
-            else hipLaunchKernelGGL((k_dense_lds<K, KB, false, false, BLOCK, true>), gd, bd, 0, st->stream, st->data, g, dev_m, dev_off);
-            return;
-        }
-    }
-    if (nt) {
-        if (realm) hipLaunchKernelGGL((k_dense_lds<K, KB, true, true, BLOCK>), gd, bd, 0, st->stream, st->data, g, dev_m, dev_off);
-        else hipLaunchKernelGGL((k_dense_lds<K, KB, true, false, BLOCK>), gd, bd, 0, st->stream, st->data, g, dev_m, dev_off);
-    } else {
-        if (realm) hipLaunchKernelGGL((k_dense_lds<K, KB, false, true, BLOCK>), gd, bd, 0, st->stream, st->data, g, dev_m, dev_off);
-        else hipLaunchKernelGGL((k_dense_lds<K, KB, false, false, BLOCK>), gd, bd, 0, st->stream, st->data, g, dev_m, dev_off);
-    }
-}
-
-template <int K, int BLOCK>
-static int dispatch_lds(qsv_state *st, int KB, bool nt, bool realm, dim3 gd, const LdsArgs &g, const double *dev_m,
-                        const uint64_t *dev_off, bool m3 = false) {
-    switch (KB) {
-        case 0: launch_lds_kernel<K, 0, BLOCK>(st, nt, realm, gd, g, dev_m, dev_off, m3); break;
-        case 1: launch_lds_kernel<K, 1, BLOCK>(st, nt, realm, gd, g, dev_m, dev_off, m3); break;
-        case 2: launch_lds_kernel<K, 2, BLOCK>(st, nt, realm, gd, g, dev_m, dev_off, m3); break;
-        default: launch_lds_kernel<K, 3, BLOCK>(st, nt, realm, gd, g, dev_m, dev_off, m3); break;
-    }
-    return check_launch();
 }
 
 static bool mtile_default() {
@@ -2522,212 +2343,97 @@ static bool mtile_default() {
     return on;
 }
 
-// k = 3..5 on any register with at least k qubits.  bits[j] = bit position of matrix leg j (leg 0 most significant).
-static int launch_dense_big(qsv_state *st, int k, const int *bits, const double *m_user) {
+// k = 3..6 in the form f (choose_form: FORM_MTILE5, FORM_TILE, FORM_LDS or FORM_BIG).  bits[j] = bit position of matrix
+// leg j (leg 0 most significant).
+static int launch_dense_big(qsv_state *st, int k, const int *bits, const double *m_user, const FormChoice &f) {
     const int D = 1 << k;
-    std::vector<int> high, low;
-    for (int j = 0; j < k; ++j) (bits[j] >= QSV_LANE_BITS ? high : low).push_back(bits[j]);
-    std::sort(low.begin(), low.end());  // bits 0..2 (inside a 128-byte line) first, then bits 3..5
-    int KL = static_cast<int>(low.size());
-    // stand-in bits for the low targets: the lowest free bits >= 6 (needs n >= k + 6)
-    std::vector<int> standin;
-    for (int b = QSV_LANE_BITS; b < st->n && static_cast<int>(standin.size()) < KL; ++b)
-        if (std::find(high.begin(), high.end(), b) == high.end()) standin.push_back(b);
-    bool all_from_bit3 = true;
-    for (int j = 0; j < k; ++j) all_from_bit3 = all_from_bit3 && bits[j] >= 3;
-    const bool tile_ok = k >= 3 && k <= 5 && all_from_bit3 && (st->amps >> k) >= 64 && (st->amps >> k) % 64 == 0;
-    bool real_matrix = true;
-    for (int i = 0; i < D * D && real_matrix; ++i) real_matrix = m_user[2 * i + 1] == 0.0;
-    // shipped choice: k = 3, 4, and k = 5 with a real matrix (a complex 32 x 32 product per column keeps the FP64 pipe busy
-    // for 0.9 of the 1.4 ms the memory traffic takes; the tile form's extra LDS round trip then costs more than it hides.
-    // A persistent form with two LDS tiles and the next tile's loads in flight during the arithmetic was measured too:
-    // 1.86 ms -- two workgroups per CU leave the FMA chains exposed to the scalar-load and LDS latencies)
-    // complex 5-qubit blocks on bits >= 3: the tile-fed matrix-core kernel (k_dense_mtile5; QSV_OPT_KQ_VARIANT = 6 forces it)
-    const bool use_mtile = tile_ok && k == 5 && !real_matrix && st->complex_product != 4 &&
-                           (st->kq_variant == 6 || (st->kq_variant == 0 && mtile_default()));
-    const bool use_tile = use_mtile || (tile_ok && (st->kq_variant == 4 || (st->kq_variant == 0 && (k <= 4 || real_matrix))));
-    const bool transposed = KL > 0 && static_cast<int>(standin.size()) == KL && st->kq_variant != 2 && !use_tile;
-    if (!transposed) {  // all targets high, or a register too small to transpose: lanes = lowest free bits
-        high.assign(bits, bits + k);
-        low.clear();
-        standin.clear();
-        KL = 0;
-    }
-    const int KH = k - KL;
-    // Which form (MI355X, n = 28, profiles/r02_sweep_kq_kernels.txt): k = 5 with low targets -> the line-granular
-    // kernel (4.9-5.2 TB/s at every placement; the shuffle form drops to 2.1-4.4 there); k = 5 real matrices ->
-    // the same kernel's two-FMA arithmetic (5.4-5.8 TB/s); k = 3, 4 and k = 5 on high bits -> the shuffle form
-    // (its butterflies are cheap up to 16 amplitudes per thread: 5.6-6.0 TB/s).  QSV_OPT_KQ_VARIANT overrides.
-    const bool fits = (st->amps >> k) >= 64 && (st->amps >> k) % 64 == 0;
-    const bool use_lds = !use_tile && fits && (k == 6 || st->kq_variant == 3 ||
-                                  (st->kq_variant == 0 && k == 5 && (KL > 0 || real_matrix)));
-    if (k == 6 && !use_lds) return QSV_UNHANDLED_KQ;  // only the line-granular kernel is built for 64 x 64 matrices
-    int KB = 0;
-    for (int b : low) KB += b < 3;
+    const bool tile = f.form == FORM_TILE, lds = f.form == FORM_LDS;
     // register index c = (h << KL) | t: h bit i <-> high[i], t bit j <-> low[j] (stored at stand-in bit standin[j])
-    std::vector<uint64_t> off(D, 0);
-    for (int c = 0; c < D; ++c) {
-        for (int i = 0; i < KH; ++i)
-            if ((c >> (KL + i)) & 1) off[c] |= 1ull << high[i];
-        for (int j = 0; j < KL; ++j)
-            if ((c >> j) & 1) off[c] |= 1ull << ((use_lds && low[j] >= 3) ? low[j] : standin[j]);
-    }
-    auto user_index = [&](int c) {  // kernel register index -> index of the caller's matrix
-        int u = 0;
-        for (int leg = 0; leg < k; ++leg) {
-            int v = 0;
-            for (int i = 0; i < KH; ++i)
-                if (high[i] == bits[leg]) v = (c >> (KL + i)) & 1;
-            for (int j = 0; j < KL; ++j)
-                if (low[j] == bits[leg]) v = (c >> j) & 1;
-            u |= v << (k - 1 - leg);
-        }
-        return u;
-    };
-    const bool realm = (use_lds || use_tile) && real_matrix;
-    // complex 5-qubit blocks in three real multiplications per entry (row_product_3m): a measurement variant only
-    // (QSV_OPT_COMPLEX_PRODUCT = 3).  On the vector pipe it does not pay (profiles/r03_complex_product.txt): a quarter
-    // fewer FMAs, but a third plane of matrix rows through the scalar cache and xr + xi in 64 more registers -- 1.64-1.71
-    // ms against 1.61-1.77 for k_dense_big<5, 0>, 1.80-1.99 against 1.66-1.73 for k_dense_lds with targets inside a line
-    // (two waves per SIMD instead of three).  These kernels are not waiting for the FP64 pipe.  On the matrix cores (k = 6)
-    // the same trick is worth 13 %: see launch_dense_mfma.
-    const bool m3 = !use_mtile && k == 5 && !real_matrix && st->complex_product == 3 && (use_tile || use_lds || KL == 0);
-    std::vector<double> m(realm ? static_cast<size_t>(D) * D : (m3 ? 3ull : 2ull) * D * D);
-    std::vector<int> ui(D);
-    for (int c = 0; c < D; ++c) ui[c] = user_index(c);
-    for (int r = 0; r < D; ++r)
-        for (int c = 0; c < D; ++c) {
-            const int ur = ui[r], uc = ui[c];
-            if (realm) {
-                m[r * D + c] = m_user[2 * (ur * D + uc)];
-            } else if (m3 && !use_tile) {   // a row = three planes of D doubles: Ar | Ai | Ar + Ai
-                const double re = m_user[2 * (ur * D + uc)], im = m_user[2 * (ur * D + uc) + 1];
-                m[3 * D * r + c] = re;
-                m[3 * D * r + D + c] = im;
-                m[3 * D * r + 2 * D + c] = re + im;
-            } else if (m3) {                // tile form: (Ar, Ai, Ar + Ai) per entry, regrouped below
-                const double re = m_user[2 * (ur * D + uc)], im = m_user[2 * (ur * D + uc) + 1];
-                m[3 * (r * D + c)] = re;
-                m[3 * (r * D + c) + 1] = im;
-                m[3 * (r * D + c) + 2] = re + im;
-            } else {
-                m[2 * (r * D + c)] = m_user[2 * (ur * D + uc)];
-                m[2 * (r * D + c) + 1] = m_user[2 * (ur * D + uc) + 1];
-            }
-        }
-    std::vector<int> ins(high);
-    ins.insert(ins.end(), standin.begin(), standin.end());
-    std::sort(ins.begin(), ins.end());
-    const uint64_t W = st->amps >> k;
-    if (use_tile && !use_mtile) {  // matrix slice of wave q, input c: ROWS consecutive entries  [q][c][i] = m[q ROWS + i][c]
-        const int rows = k == 5 ? 8 : k == 4 ? 4 : 2, per = realm ? 1 : m3 ? 3 : 2;
-        std::vector<double> mt(m.size());
-        for (int r = 0; r < D; ++r)
-            for (int c = 0; c < D; ++c)
-                for (int e = 0; e < per; ++e)
-                    mt[per * ((static_cast<size_t>(r / rows) * D + c) * rows + r % rows) + e] = m[per * (r * D + c) + e];
-        m.swap(mt);
-    }
+    const Split s = f.transposed ? split_targets(k, bits, st->n) : untransposed(k, bits);
+    const int KL = static_cast<int>(s.low.size()), KB = s.KB;
+    const std::vector<uint64_t> off = offsets(address_bits(s, lds));
+    const std::vector<int> ui = user_index(k, bits, kernel_bits(s).data()), ins = inserted_bits(s);
+    // k_dense_tile: the matrix slice of wave q, input c, is ROWS consecutive entries  [q][c][i] = m[q ROWS + i][c]
+    const int rows = !tile ? 0 : k == 5 ? 8 : k == 4 ? 4 : 2;
+    const std::vector<double> m = matrix(f.realm ? MAT_REAL : !f.m3 ? MAT_COMPLEX : tile ? MAT_3M_ENTRIES : MAT_3M_ROWS, D, m_user,
+                                         ui.data(), rows);
     // matrix and offsets ride the staging ring to the device: queued on the stream in front of the kernel, no host wait
     StageRef staged;
     int rc = qsvk_stage(st, m.data(), sizeof(double) * m.size(), off.data(), sizeof(uint64_t) * D, &staged);
     if (rc) return rc;
     const double *dev_m = reinterpret_cast<const double *>(staged.dev);
     const uint64_t *dev_off = reinterpret_cast<const uint64_t *>(staged.dev + qsv_pad16(sizeof(double) * m.size()));
-    if (use_mtile) {
-        BigArgs g;
-        std::memset(&g, 0, sizeof(g));
-        g.W = W;
-        g.nins = static_cast<int>(ins.size());
-        for (size_t j = 0; j < ins.size(); ++j) g.pos[j] = static_cast<uint32_t>(ins[j]);
-        const bool nt = st->nontemporal != 0;
-        g.regions = st->remap >= 0 ? static_cast<uint32_t>(st->remap) : tile_regions(k, ins);
+    const Enumeration e = enumeration(st->amps >> k, ins);
+    bool nt = st->nontemporal != 0;  // tile and line-granular forms: every wave-instruction touches whole 128-byte lines
+    if (f.form == FORM_MTILE5) {
+        BigArgs g = with_enumeration<BigArgs>(e);
+        g.regions = regions_or(st, tile_regions(k, ins));
         snprintf(st->last_kernel, sizeof(st->last_kernel), "k_dense_mtile5<%s>", nt ? "true" : "false");
         int cus = 256;
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, st->device);  // 256 if the query fails
-        const unsigned grid = static_cast<unsigned>(std::min<uint64_t>(W / 64, 2ull * cus));
-        if (nt) hipLaunchKernelGGL(k_dense_mtile5<true>, dim3(grid), dim3(QSV_BLOCK), 0, st->stream, st->data, g, dev_m, dev_off);
-        else hipLaunchKernelGGL(k_dense_mtile5<false>, dim3(grid), dim3(QSV_BLOCK), 0, st->stream, st->data, g, dev_m, dev_off);
-        const int rc2 = check_launch();
-        if (rc2) return rc2;
-        return qsvk_stage_done(st, staged);
-    }
-    if (use_tile) {
-        const int rows = k == 5 ? 8 : k == 4 ? 4 : 2;
-        BigArgs g;
-        std::memset(&g, 0, sizeof(g));
-        g.W = W;
-        g.nins = static_cast<int>(ins.size());
-        for (size_t j = 0; j < ins.size(); ++j) g.pos[j] = static_cast<uint32_t>(ins[j]);
-        const bool nt = st->nontemporal != 0;  // every wave-instruction touches whole 128-byte lines
-        g.regions = st->remap >= 0 ? static_cast<uint32_t>(st->remap) : tile_regions(k, ins);
-        snprintf(st->last_kernel, sizeof(st->last_kernel), "k_dense_tile<%d, %d, %s, %s%s>", k, rows, realm ? "true" : "false",
-                 nt ? "true" : "false", m3 ? ", true" : "");
-        const uint64_t per_launch = (1ull << 23) * 64;  // columns per dispatch (a power of two: see launch_tile12_kernels)
-        for (g.w0 = 0; g.w0 < g.W; g.w0 += per_launch) {
-            const dim3 gd(static_cast<unsigned>(std::min(per_launch, g.W - g.w0) / 64));
-            const int rc2 = k == 5 ? launch_tile_kernel<5, 8>(st, nt, realm, gd, g, dev_m, dev_off, m3)
-                          : k == 4 ? launch_tile_kernel<4, 4>(st, nt, realm, gd, g, dev_m, dev_off)
-                                   : launch_tile_kernel<3, 2>(st, nt, realm, gd, g, dev_m, dev_off);
-            if (rc2) return rc2;
-        }
-        return qsvk_stage_done(st, staged);
-    }
-    if (use_lds) {
-        LdsArgs g;
-        std::memset(&g, 0, sizeof(g));
-        g.W = W;
-        g.nins = static_cast<int>(ins.size());
-        for (size_t j = 0; j < ins.size(); ++j) g.pos[j] = static_cast<uint32_t>(ins[j]);
-        for (int j = 0; j < KL; ++j) {
-            if (low[j] >= 3) {
-                g.abit[g.na] = low[j];
-                g.aE[g.na] = standin[j];
-                g.amask |= 1u << low[j];
-                ++g.na;
-            } else {
-                g.bmask |= 1u << low[j];
-            }
-        }
-        for (int v = 0; v < (1 << KB); ++v)
-            for (int j = 0; j < KB; ++j)
-                if ((v >> j) & 1) g.bdep[v] |= 1u << low[j];
-        const bool nt = st->nontemporal != 0;  // every wave-instruction touches whole 128-byte lines
+        const dim3 gd(static_cast<unsigned>(std::min<uint64_t>(e.W / 64, 2ull * cus))), bd(QSV_BLOCK);
+        with_bool(nt, [&](auto NT) { hipLaunchKernelGGL(k_dense_mtile5<NT.value>, gd, bd, 0, st->stream, st->data, g, dev_m, dev_off); });
+        rc = check_launch();
+    } else if (tile) {
+        BigArgs g = with_enumeration<BigArgs>(e);
+        g.regions = regions_or(st, tile_regions(k, ins));
+        snprintf(st->last_kernel, sizeof(st->last_kernel), "k_dense_tile<%d, %d, %s, %s%s>", k, rows, f.realm ? "true" : "false",
+                 nt ? "true" : "false", f.m3 ? ", true" : "");
+        rc = launch_ranges(g, DISPATCH_TILES * 64, [&](uint64_t columns) {
+            const dim3 gd(static_cast<unsigned>(columns / 64));
+            with_int<3, 5>(k, [&](auto K) { with_bool(f.realm, [&](auto REAL) { with_bool(nt, [&](auto NT) {
+                constexpr int ROWS = K.value == 5 ? 8 : K.value == 4 ? 4 : 2;
+                const dim3 bd((1 << K.value) / ROWS * 64);
+                if constexpr (K.value == 5 && !REAL.value) {
+                    if (f.m3) {
+                        hipLaunchKernelGGL((k_dense_tile<5, ROWS, false, NT.value, true>), gd, bd, 0, st->stream, st->data, g, dev_m, dev_off);
+                        return;
+                    }
+                }
+                hipLaunchKernelGGL((k_dense_tile<K.value, ROWS, REAL.value, NT.value>), gd, bd, 0, st->stream, st->data, g, dev_m, dev_off);
+            }); }); });
+        });
+    } else if (lds) {
+        LdsArgs g = with_enumeration<LdsArgs>(e);
+        set_low_fields(g, low_fields(s));
+        g.regions = regions_or(st, 8);
         snprintf(st->last_kernel, sizeof(st->last_kernel), "k_dense_lds<%d, %d, %s, %s%s>", k, KB, nt ? "true" : "false",
-                 realm ? "true" : "false", m3 ? ", 256, true" : "");
-        g.regions = st->remap >= 0 ? static_cast<uint32_t>(st->remap) : 8;
-        const uint64_t per_launch = 0x00ffffffull * QSV_BLOCK;  // an AQL dispatch counts work-items in 32 bits
-        for (g.w0 = 0; g.w0 < g.W; g.w0 += per_launch) {
-            const dim3 gd(grid_for(std::min(per_launch, g.W - g.w0), QSV_BLOCK, 0));
-            const int rc2 = k == 3 ? dispatch_lds<3, QSV_BLOCK>(st, KB, nt, realm, gd, g, dev_m, dev_off)
-                          : k == 4 ? dispatch_lds<4, QSV_BLOCK>(st, KB, nt, realm, gd, g, dev_m, dev_off)
-                          : k == 5 ? dispatch_lds<5, QSV_BLOCK>(st, KB, nt, realm, gd, g, dev_m, dev_off, m3)
-                                   : dispatch_lds<6, QSV_BLOCK>(st, KB, nt, realm, gd, g, dev_m, dev_off);
-            if (rc2) return rc2;
-        }
-        return qsvk_stage_done(st, staged);
+                 f.realm ? "true" : "false", f.m3 ? ", 256, true" : "");
+        rc = launch_ranges(g, DISPATCH_ITEMS, [&](uint64_t items) {
+            const dim3 gd(grid_for(items, QSV_BLOCK, 0)), bd(QSV_BLOCK);
+            with_int<3, 6>(k, [&](auto K) { with_int<0, 3>(KB, [&](auto B) { with_bool(f.realm, [&](auto REAL) { with_bool(nt, [&](auto NT) {
+                if constexpr (K.value == 5 && !REAL.value) {
+                    if (f.m3) {
+                        hipLaunchKernelGGL((k_dense_lds<5, B.value, NT.value, false, QSV_BLOCK, true>), gd, bd, 0, st->stream, st->data, g, dev_m, dev_off);
+                        return;
+                    }
+                }
+                hipLaunchKernelGGL((k_dense_lds<K.value, B.value, NT.value, REAL.value, QSV_BLOCK>), gd, bd, 0, st->stream, st->data, g, dev_m, dev_off);
+            }); }); }); });
+        });
+    } else {
+        BigArgs g = with_enumeration<BigArgs>(e);
+        for (int j = 0; j < KL; ++j) g.lbit[j] = s.low[j];
+        // partial-line nontemporal accesses are slow: use them only when every access is a full 1 KiB per wave
+        bool coalesced = true;
+        for (int b : ins) coalesced = coalesced && b >= QSV_LANE_BITS;
+        nt = nt && coalesced;
+        snprintf(st->last_kernel, sizeof(st->last_kernel), "k_dense_big<%d, %d, %s%s>", k, KL, nt ? "true" : "false", f.m3 ? ", true" : "");
+        g.regions = regions_or(st, 8);
+        rc = launch_ranges(g, DISPATCH_ITEMS, [&](uint64_t items) {
+            const dim3 gd(grid_for(items, QSV_BLOCK, 0)), bd(QSV_BLOCK);
+            with_int<3, 5>(k, [&](auto K) { with_int<0, K.value>(KL, [&](auto T) { with_bool(nt, [&](auto NT) {
+                if constexpr (K.value == 5 && T.value == 0) {
+                    if (f.m3) {
+                        hipLaunchKernelGGL((k_dense_big<5, 0, NT.value, true>), gd, bd, 0, st->stream, st->data, g, dev_m, dev_off);
+                        return;
+                    }
+                }
+                hipLaunchKernelGGL((k_dense_big<K.value, T.value, NT.value>), gd, bd, 0, st->stream, st->data, g, dev_m, dev_off);
+            }); }); });
+        });
     }
-    BigArgs g;
-    std::memset(&g, 0, sizeof(g));
-    for (int j = 0; j < KL; ++j) g.lbit[j] = low[j];
-    g.W = W;
-    g.nins = static_cast<int>(ins.size());
-    for (size_t j = 0; j < ins.size(); ++j) g.pos[j] = static_cast<uint32_t>(ins[j]);
-    // partial-line nontemporal accesses are slow: use them only when every access is a full 1 KiB per wave
-    bool coalesced = true;
-    for (int b : ins) coalesced = coalesced && b >= QSV_LANE_BITS;
-    const bool nt = st->nontemporal != 0 && coalesced;
-    snprintf(st->last_kernel, sizeof(st->last_kernel), "k_dense_big<%d, %d, %s%s>", k, KL, nt ? "true" : "false", m3 ? ", true" : "");
-    g.regions = st->remap >= 0 ? static_cast<uint32_t>(st->remap) : 8;
-    const uint64_t per_launch = 0x00ffffffull * QSV_BLOCK;  // an AQL dispatch counts work-items in 32 bits
-    for (g.w0 = 0; g.w0 < g.W; g.w0 += per_launch) {
-        const dim3 gd(grid_for(std::min(per_launch, g.W - g.w0), QSV_BLOCK, 0));
-        const int rc2 = k == 3 ? dispatch_big<3>(st, KL, nt, gd, g, dev_m, dev_off)
-                      : k == 4 ? dispatch_big<4>(st, KL, nt, gd, g, dev_m, dev_off)
-                               : dispatch_big<5>(st, KL, nt, gd, g, dev_m, dev_off, m3);
-        if (rc2) return rc2;
-    }
-    return qsvk_stage_done(st, staged);
+    return rc ? rc : qsvk_stage_done(st, staged);
 }
 
 
@@ -2744,126 +2450,55 @@ int qsvk_sequence5(qsv_state *st, const int *bits, int n_gates, const int *arity
     if (work > (st->sequence_work >= 0 ? st->sequence_work : seq_max_work())) return QSV_UNHANDLED_KQ;
     const uint64_t W = st->amps >> k;
     if (W < 64 || W % 64) return QSV_UNHANDLED_KQ;
-    std::vector<int> high, low;
-    for (int j = 0; j < k; ++j) (bits[j] >= QSV_LANE_BITS ? high : low).push_back(bits[j]);
-    std::sort(low.begin(), low.end());
-    const int KL = static_cast<int>(low.size());
-    std::vector<int> standin;
-    for (int b = QSV_LANE_BITS; b < st->n && static_cast<int>(standin.size()) < KL; ++b)
-        if (std::find(high.begin(), high.end(), b) == high.end()) standin.push_back(b);
-    if (static_cast<int>(standin.size()) != KL) return QSV_UNHANDLED_KQ;
-    const int KH = k - KL;
-    int KB = 0;
-    for (int b : low) KB += b < 3;
-    // register index c = (h << KL) | t: h bit i <-> high[i], t bit j <-> low[j] (as launch_dense_big)
-    std::vector<uint64_t> off(D, 0);
-    for (int c = 0; c < D; ++c) {
-        for (int i = 0; i < KH; ++i)
-            if ((c >> (KL + i)) & 1) off[c] |= 1ull << high[i];
-        for (int j = 0; j < KL; ++j)
-            if ((c >> j) & 1) off[c] |= 1ull << (low[j] >= 3 ? low[j] : standin[j]);
-    }
-    auto reg_bit = [&](int phys) {
-        for (int j = 0; j < KL; ++j)
-            if (low[j] == phys) return j;
-        for (int i = 0; i < KH; ++i)
-            if (high[i] == phys) return KL + i;
-        return -1;
-    };
+    // register index c = (h << KL) | t: h bit i <-> high[i], t bit j <-> low[j] (as launch_dense_big's line-granular form)
+    const Split s = split_targets(k, bits, st->n);
+    if (!s.enough) return QSV_UNHANDLED_KQ;
+    const std::vector<int> kb = kernel_bits(s);
+    auto reg_bit = [&](int leg) { return static_cast<int>(std::find(kb.begin(), kb.end(), bits[leg]) - kb.begin()); };
     std::vector<SeqGate> rec(n_gates);
     const double *m = mats;
     for (int gi = 0; gi < n_gates; ++gi) {
-        SeqGate &r = rec[gi];
-        std::memset(&r, 0, sizeof(r));
+        const int l0 = legs[2 * gi], l1 = legs[2 * gi + 1];
         if (arity[gi] == 1) {
-            const int leg = legs[2 * gi];
-            if (leg < 0 || leg >= k) return qsv_fail(QSV_EINVAL, "gate sequence: leg outside the block");
-            r.code = reg_bit(bits[leg]);
-            std::memcpy(r.m, m, sizeof(double) * 8);
-            m += 8;
+            if (l0 < 0 || l0 >= k) return qsv_fail(QSV_EINVAL, "gate sequence: leg outside the block");
+            rec[gi] = seq_record(1, reg_bit(l0), 0, m);
         } else if (arity[gi] == 2) {
-            const int l0 = legs[2 * gi], l1 = legs[2 * gi + 1];
             if (l0 < 0 || l0 >= k || l1 < 0 || l1 >= k || l0 == l1) return qsv_fail(QSV_EINVAL, "gate sequence: legs outside the block");
-            const int j0 = reg_bit(bits[l0]), j1 = reg_bit(bits[l1]);
-            const int hi = std::max(j0, j1), lo = std::min(j0, j1);
-            r.code = 5 + hi * (hi - 1) / 2 + lo;
-            for (int rr = 0; rr < 4; ++rr)
-                for (int cc = 0; cc < 4; ++cc) {
-                    // record index bit 1 <-> register bit hi; the caller's index bit 1 <-> leg 0
-                    const int ur = j0 > j1 ? rr : ((rr & 1) << 1) | (rr >> 1), uc = j0 > j1 ? cc : ((cc & 1) << 1) | (cc >> 1);
-                    r.m[2 * (rr * 4 + cc)] = m[2 * (ur * 4 + uc)];
-                    r.m[2 * (rr * 4 + cc) + 1] = m[2 * (ur * 4 + uc) + 1];
-                }
-            m += 32;
+            rec[gi] = seq_record(2, reg_bit(l0), reg_bit(l1), m);
         } else {
             return QSV_UNHANDLED_KQ;
         }
+        m += arity[gi] == 1 ? 8 : 32;
     }
-    std::vector<int> ins(high);
-    ins.insert(ins.end(), standin.begin(), standin.end());
-    std::sort(ins.begin(), ins.end());
+    const std::vector<uint64_t> off = offsets(address_bits(s, true));
     StageRef staged;
     int rc = qsvk_stage(st, rec.data(), sizeof(SeqGate) * rec.size(), off.data(), sizeof(uint64_t) * D, &staged);
     if (rc) return rc;
     const SeqGate *dev_g = reinterpret_cast<const SeqGate *>(staged.dev);
     const uint64_t *dev_off = reinterpret_cast<const uint64_t *>(staged.dev + qsv_pad16(sizeof(SeqGate) * rec.size()));
     const bool nt = st->nontemporal != 0;
-    const uint64_t per_launch = 0x00ffffffull * QSV_BLOCK;
-    if (KL == 0) {
-        BigArgs g;
-        std::memset(&g, 0, sizeof(g));
-        g.W = W;
-        g.nins = static_cast<int>(ins.size());
-        for (size_t j = 0; j < ins.size(); ++j) g.pos[j] = static_cast<uint32_t>(ins[j]);
-        g.regions = st->remap >= 0 ? static_cast<uint32_t>(st->remap) : 8;
+    const Enumeration e = enumeration(W, inserted_bits(s));
+    if (s.low.empty()) {
+        BigArgs g = with_enumeration<BigArgs>(e);
+        g.regions = regions_or(st, 8);
         snprintf(st->last_kernel, sizeof(st->last_kernel), "k_seq_big<%s>", nt ? "true" : "false");
-        for (g.w0 = 0; g.w0 < g.W; g.w0 += per_launch) {
-            const dim3 gd(grid_for(std::min(per_launch, g.W - g.w0), QSV_BLOCK, 0)), bd(QSV_BLOCK);
-            if (nt) hipLaunchKernelGGL(k_seq_big<true>, gd, bd, 0, st->stream, st->data, g, dev_g, n_gates, dev_off);
-            else hipLaunchKernelGGL(k_seq_big<false>, gd, bd, 0, st->stream, st->data, g, dev_g, n_gates, dev_off);
-            rc = check_launch();
-            if (rc) return rc;
-        }
-        return qsvk_stage_done(st, staged);
+        rc = launch_ranges(g, DISPATCH_ITEMS, [&](uint64_t items) {
+            const dim3 gd(grid_for(items, QSV_BLOCK, 0)), bd(QSV_BLOCK);
+            with_bool(nt, [&](auto NT) { hipLaunchKernelGGL(k_seq_big<NT.value>, gd, bd, 0, st->stream, st->data, g, dev_g, n_gates, dev_off); });
+        });
+    } else {
+        LdsArgs g = with_enumeration<LdsArgs>(e);
+        set_low_fields(g, low_fields(s));
+        g.regions = regions_or(st, 8);
+        snprintf(st->last_kernel, sizeof(st->last_kernel), "k_seq_lds<%d, %s>", s.KB, nt ? "true" : "false");
+        rc = launch_ranges(g, DISPATCH_ITEMS, [&](uint64_t items) {
+            const dim3 gd(grid_for(items, QSV_BLOCK, 0)), bd(QSV_BLOCK);
+            with_int<0, 3>(s.KB, [&](auto B) { with_bool(nt, [&](auto NT) {
+                hipLaunchKernelGGL((k_seq_lds<B.value, NT.value>), gd, bd, 0, st->stream, st->data, g, dev_g, n_gates, dev_off);
+            }); });
+        });
     }
-    LdsArgs g;
-    std::memset(&g, 0, sizeof(g));
-    g.W = W;
-    g.nins = static_cast<int>(ins.size());
-    for (size_t j = 0; j < ins.size(); ++j) g.pos[j] = static_cast<uint32_t>(ins[j]);
-    for (int j = 0; j < KL; ++j) {
-        if (low[j] >= 3) {
-            g.abit[g.na] = low[j];
-            g.aE[g.na] = standin[j];
-            g.amask |= 1u << low[j];
-            ++g.na;
-        } else {
-            g.bmask |= 1u << low[j];
-        }
-    }
-    for (int v = 0; v < (1 << KB); ++v)
-        for (int j = 0; j < KB; ++j)
-            if ((v >> j) & 1) g.bdep[v] |= 1u << low[j];
-    g.regions = st->remap >= 0 ? static_cast<uint32_t>(st->remap) : 8;
-    snprintf(st->last_kernel, sizeof(st->last_kernel), "k_seq_lds<%d, %s>", KB, nt ? "true" : "false");
-    for (g.w0 = 0; g.w0 < g.W; g.w0 += per_launch) {
-        const dim3 gd(grid_for(std::min(per_launch, g.W - g.w0), QSV_BLOCK, 0)), bd(QSV_BLOCK);
-#define QSV_LAUNCH_SEQ(KBV)                                                                                           \
-    do {                                                                                                              \
-        if (nt) hipLaunchKernelGGL((k_seq_lds<KBV, true>), gd, bd, 0, st->stream, st->data, g, dev_g, n_gates, dev_off); \
-        else hipLaunchKernelGGL((k_seq_lds<KBV, false>), gd, bd, 0, st->stream, st->data, g, dev_g, n_gates, dev_off);   \
-    } while (0)
-        switch (KB) {
-            case 0: QSV_LAUNCH_SEQ(0); break;
-            case 1: QSV_LAUNCH_SEQ(1); break;
-            case 2: QSV_LAUNCH_SEQ(2); break;
-            default: QSV_LAUNCH_SEQ(3); break;
-        }
-#undef QSV_LAUNCH_SEQ
-        rc = check_launch();
-        if (rc) return rc;
-    }
-    return qsvk_stage_done(st, staged);
+    return rc ? rc : qsvk_stage_done(st, staged);
 }
 
 // A fused block of k = 1..6 qubits as the list of its source gates on LDS tiles (k_seq_tile).  Arguments as
@@ -2872,90 +2507,17 @@ int qsvk_sequence5(qsv_state *st, const int *bits, int n_gates, const int *arity
 int qsvk_sequence_tile(qsv_state *st, int k, const int *bits, int n_gates, const int *arity, const int *legs,
                        const double *mats) {
     if (k < 1 || k > 6 || n_gates < 1 || n_gates > SEQ_MAX_GATES || st->n < TILE_SEQ_BITS) return QSV_UNHANDLED_KQ;
-    // the tile's bits: the targets and the lowest other bits, 12 in all, ascending
-    std::vector<int> tile_bits(bits, bits + k);
-    for (int b = 0; b < st->n && static_cast<int>(tile_bits.size()) < TILE_SEQ_BITS; ++b)
-        if (std::find(bits, bits + k, b) == bits + k) tile_bits.push_back(b);
-    std::sort(tile_bits.begin(), tile_bits.end());
-    auto position = [&](int bit) { return static_cast<int>(std::find(tile_bits.begin(), tile_bits.end(), bit) - tile_bits.begin()); };
-    // passes: consecutive gates whose legs fit four tile bits together
-    struct Draft {
-        std::vector<int> q;      // tile bits of the pass
-        std::vector<int> gate;   // indices into the gate list
-    };
-    std::vector<Draft> drafts;
-    std::vector<std::array<int, 2>> where(n_gates);
-    for (int gi = 0; gi < n_gates; ++gi) {
-        if (arity[gi] != 1 && arity[gi] != 2) return QSV_UNHANDLED_KQ;
-        for (int j = 0; j < 2; ++j) {
-            const int leg = legs[2 * gi + (j < arity[gi] ? j : 0)];
-            if (leg < 0 || leg >= k) return qsv_fail(QSV_EINVAL, "gate sequence: leg outside the block");
-            where[gi][j] = position(bits[leg]);
-        }
-        if (arity[gi] == 2 && where[gi][0] == where[gi][1]) return qsv_fail(QSV_EINVAL, "gate sequence: legs outside the block");
-        std::vector<int> merged = drafts.empty() ? std::vector<int>() : drafts.back().q;
-        for (int j = 0; j < arity[gi]; ++j)
-            if (std::find(merged.begin(), merged.end(), where[gi][j]) == merged.end()) merged.push_back(where[gi][j]);
-        if (drafts.empty() || merged.size() > 4) {
-            drafts.push_back(Draft{});
-            merged.assign(where[gi].begin(), where[gi].begin() + arity[gi]);
-        }
-        drafts.back().q = merged;
-        drafts.back().gate.push_back(gi);
-    }
-    if (drafts.size() > static_cast<size_t>(TILE_SEQ_MAX_PASSES)) return QSV_UNHANDLED_KQ;
-    std::vector<TilePass> passes(drafts.size());
-    std::vector<SeqGate> rec(n_gates);
-    std::vector<size_t> mat_at(n_gates);
-    {
-        size_t at = 0;
-        for (int gi = 0; gi < n_gates; ++gi) {
-            mat_at[gi] = at;
-            at += arity[gi] == 1 ? 8 : 32;
-        }
-    }
-    int next = 0;
-    for (size_t p = 0; p < drafts.size(); ++p) {
-        Draft &d = drafts[p];
-        for (int b = 0; d.q.size() < 4; ++b)          // fewer than four bits in use: any other tile bits complete the group
-            if (std::find(d.q.begin(), d.q.end(), b) == d.q.end()) d.q.push_back(b);
-        std::sort(d.q.begin(), d.q.end());
-        TilePass &ps = passes[p];
-        std::memset(&ps, 0, sizeof(ps));
-        ps.first = next;
-        ps.count = static_cast<int32_t>(d.gate.size());
-        for (int j = 0; j < 4; ++j) ps.q[j] = d.q[j];
-        for (int gi : d.gate) {
-            SeqGate &r = rec[next++];
-            std::memset(&r, 0, sizeof(r));
-            const double *m = mats + mat_at[gi];
-            auto local = [&](int tile_bit) { return static_cast<int>(std::find(d.q.begin(), d.q.end(), tile_bit) - d.q.begin()); };
-            if (arity[gi] == 1) {
-                r.code = local(where[gi][0]);
-                std::memcpy(r.m, m, sizeof(double) * 8);
-            } else {
-                const int j0 = local(where[gi][0]), j1 = local(where[gi][1]);
-                const int hi = std::max(j0, j1), lo = std::min(j0, j1);
-                r.code = 5 + hi * (hi - 1) / 2 + lo;
-                for (int rr = 0; rr < 4; ++rr)
-                    for (int cc = 0; cc < 4; ++cc) {
-                        // record index bit 1 <-> register bit hi; the caller's index bit 1 <-> leg 0
-                        const int ur = j0 > j1 ? rr : ((rr & 1) << 1) | (rr >> 1), uc = j0 > j1 ? cc : ((cc & 1) << 1) | (cc >> 1);
-                        r.m[2 * (rr * 4 + cc)] = m[2 * (ur * 4 + uc)];
-                        r.m[2 * (rr * 4 + cc) + 1] = m[2 * (ur * 4 + uc) + 1];
-                    }
-            }
-        }
-    }
-    std::vector<uint64_t> off(TILE_SEQ_ROWS, 0);
-    for (int row = 0; row < TILE_SEQ_ROWS; ++row)
-        for (int j = 0; j < TILE_SEQ_BITS - 6; ++j)
-            if ((row >> j) & 1) off[row] |= 1ull << tile_bits[6 + j];
+    const TileCut cut = cut_tile_passes(st->n, k, bits, n_gates, arity, legs, mats);
+    if (cut.status == TileCut::UNHANDLED) return QSV_UNHANDLED_KQ;
+    if (cut.status == TileCut::LEG_OUTSIDE) return qsv_fail(QSV_EINVAL, "gate sequence: leg outside the block");
+    if (cut.status == TileCut::LEGS_EQUAL) return qsv_fail(QSV_EINVAL, "gate sequence: legs outside the block");
+    const std::vector<int> &tile_bits = cut.tile_bits;
+    const std::vector<uint64_t> off = offsets(std::vector<int>(tile_bits.begin() + 6, tile_bits.end()));   // [rows]
     // one image: [gates | passes | row offsets]
-    const size_t gates_bytes = qsv_pad16(sizeof(SeqGate) * rec.size()), passes_bytes = qsv_pad16(sizeof(TilePass) * passes.size());
+    const size_t gates_bytes = qsv_pad16(sizeof(SeqGate) * cut.rec.size()), passes_bytes = qsv_pad16(sizeof(TilePass) * cut.passes.size());
     std::vector<char> image(gates_bytes + passes_bytes, 0);
-    std::memcpy(image.data(), rec.data(), sizeof(SeqGate) * rec.size());
-    std::memcpy(image.data() + gates_bytes, passes.data(), sizeof(TilePass) * passes.size());
+    std::memcpy(image.data(), cut.rec.data(), sizeof(SeqGate) * cut.rec.size());
+    std::memcpy(image.data() + gates_bytes, cut.passes.data(), sizeof(TilePass) * cut.passes.size());
     StageRef staged;
     int rc = qsvk_stage(st, image.data(), image.size(), off.data(), sizeof(uint64_t) * off.size(), &staged);
     if (rc) return rc;
@@ -2964,12 +2526,9 @@ int qsvk_sequence_tile(qsv_state *st, int k, const int *bits, int n_gates, const
     const uint64_t *dev_off = reinterpret_cast<const uint64_t *>(staged.dev + qsv_pad16(image.size()));
     TileSeqArgs ta;
     std::memset(&ta, 0, sizeof(ta));
-    BigArgs &g = ta.g;
-    g.W = st->amps >> TILE_SEQ_BITS;      // tiles: the index with every tile bit taken out
-    g.nins = TILE_SEQ_BITS;
-    for (int j = 0; j < TILE_SEQ_BITS; ++j) g.pos[j] = static_cast<uint32_t>(tile_bits[j]);
+    ta.g = with_enumeration<BigArgs>(enumeration(st->amps >> TILE_SEQ_BITS, tile_bits));   // tiles: the index with every tile bit taken out
     for (int j = 0; j < 6; ++j) ta.lane_bit[j] = static_cast<uint32_t>(tile_bits[j]);
-    g.regions = st->remap >= 0 ? static_cast<uint32_t>(st->remap) : 8;
+    ta.g.regions = regions_or(st, 8);
     const bool nt = st->nontemporal != 0;
     const size_t lds = sizeof(amp_t) << TILE_SEQ_BITS;
     static bool raised = false;
@@ -2981,17 +2540,13 @@ int qsvk_sequence_tile(qsv_state *st, int k, const int *bits, int n_gates, const
         raised = true;
     }
     snprintf(st->last_kernel, sizeof(st->last_kernel), "k_seq_tile<%s>", nt ? "true" : "false");
-    st->last_passes = static_cast<int>(passes.size());
-    const uint64_t per_launch = 1ull << 23;       // tiles per dispatch (a power of two: the tile order stays whole)
-    for (g.w0 = 0; g.w0 < g.W; g.w0 += per_launch) {
-        const uint64_t tiles = std::min(per_launch, g.W - g.w0);
+    const int n_passes = static_cast<int>(cut.passes.size());
+    st->last_passes = n_passes;
+    rc = launch_ranges(ta.g, DISPATCH_TILES, [&](uint64_t tiles) {
         const dim3 gd(static_cast<unsigned>(tiles)), bd(TILE_SEQ_THREADS);
-        if (nt) hipLaunchKernelGGL(k_seq_tile<true>, gd, bd, lds, st->stream, st->data, ta, dev_g, dev_p, static_cast<int>(passes.size()), dev_off);
-        else hipLaunchKernelGGL(k_seq_tile<false>, gd, bd, lds, st->stream, st->data, ta, dev_g, dev_p, static_cast<int>(passes.size()), dev_off);
-        rc = check_launch();
-        if (rc) return rc;
-    }
-    return qsvk_stage_done(st, staged);
+        with_bool(nt, [&](auto NT) { hipLaunchKernelGGL(k_seq_tile<NT.value>, gd, bd, lds, st->stream, st->data, ta, dev_g, dev_p, n_passes, dev_off); });
+    });
+    return rc ? rc : qsvk_stage_done(st, staged);
 }
 
 // ---- deferred gates: one PASS of queued 1- and 2-qubit gates over LDS-resident tiles ----------------------------------
@@ -3011,27 +2566,6 @@ int qsvk_sequence_tile(qsv_state *st, int k, const int *bits, int n_gates, const
 // the expression and the summation order of the per-gate kernel it would have run on (tile12_body: products summed from
 // zero in kernel-index order; dense_body: low-lane combinations outer, high rows inner; k_diag: one complex product), so
 // the amplitudes are bit for bit those of the per-gate path.  A pair exchange moves registers.
-enum {
-    PASS_D2 = 0, PASS_D2X = 1, PASS_D4 = 2, PASS_D4X = 3, PASS_D4HL = 4,   // dense on 2 / 4 amplitudes, by summation form
-    PASS_PAIR = 5,                                                          // exchange of (a, b) = (1, 0) and (0, 1)
-    PASS_DIAG_T = 6, PASS_DIAG_R1 = 7, PASS_DIAG_R2 = 8, PASS_DIAG_M = 9    // diagonal, by where its selector bits sit
-};
-struct PassGate {
-    int32_t form;        // PASS_*
-    int32_t code;        // the body of the form: register bit P of kernel bit 0 (D2*, DIAG_R1, DIAG_M), or 4 P0 + P1 for
-                         // the register bits of kernel bits 0 and 1 (D4*), of the two legs (PAIR) or P0 < P1 (DIAG_R2)
-    uint32_t rc;         // controls on register bits, as a mask of the register index 0..15
-    uint32_t tc;         // controls on thread bits, as a mask of tile indices
-    int32_t tz0, tz1;    // DIAG_T: tile indices of the thread bits s0, s1 that select d[(s0 << 1) | s1]; DIAG_M: tz0 = the
-                         // thread bit s of d[(register bit << 1) | s]
-    uint64_t omask;      // register bits outside the tile that must be 1 (the same for every amplitude of a tile)
-    double m[32];        // dense: D x D kernel-order matrix, (re, im) interleaved; diagonal: d[0..3] as the form reads them
-};
-struct PassGroup {
-    int32_t first, count;   // gates [first, first + count) of the pass
-    int32_t q[4];           // the group's register bits as tile indices, ascending
-    uint64_t gates;         // bit i = gate i of the pass belongs to the group
-};
 constexpr int PASS_TILE = 1 << qsv_plan::TILE_BITS, PASS_ROWS = PASS_TILE / 64, PASS_THREADS = 256;
 constexpr int PASS_ROWS_PER_WAVE = PASS_ROWS / (PASS_THREADS / 64);
 static_assert(PASS_TILE == PASS_THREADS << qsv_plan::REG_BITS, "one thread per setting of the tile bits outside the registers");
@@ -3268,268 +2802,78 @@ int qsvk_pass(qsv_state *st, const QsvOp *const *ops, int count, uint64_t tile_h
     if (count < 1 || count > qsv_plan::MAX_PASS_GATES || st->n < qsv_plan::TILE_BITS || (tile_high & low) ||
         __builtin_popcountll(tile_high) != qsv_plan::HIGH_BITS || (tile_high >> st->n))
         return qsv_fail(QSV_EINVAL, "internal: malformed gate pass");
-    int tile_bits[qsv_plan::TILE_BITS];
-    int local_of[64];
-    for (int b = 0; b < 64; ++b) {
-        local_of[b] = qsv_plan::tile_index(b, tile_high);
-        if (local_of[b] >= 0) tile_bits[local_of[b]] = b;
-    }
-    // first what each gate is, in tile indices (leg[]: dense, kernel bit 0 first; pair: both legs; diagonal: the bits that
-    // select d[(s0 << 1) | s1], leg[1] < 0: d[s0], leg[0] < 0: one factor for all); then the groups; then each gate's
-    // record relative to the register bits of its group
-    std::vector<PassGate> rec(count);
-    std::vector<std::array<int, 2>> leg(count, std::array<int, 2>{-1, -1});
-    std::vector<uint32_t> cmask(count, 0), need(count, 0);
-    for (int i = 0; i < count; ++i) {
-        const QsvOp &op = *ops[i];
-        PassGate &pg = rec[i];
-        std::memset(&pg, 0, sizeof(pg));
-        uint64_t ctrl = 0;
-        for (int c = 0; c < op.nctrl; ++c) ctrl |= 1ull << op.cbits[c];
-        const qsv_plan::ControlMasks cm = qsv_plan::control_masks(ctrl, tile_high);
-        cmask[i] = cm.inside;
-        pg.omask = cm.outside;
-        for (int j = 0; j < op.k; ++j)
-            if (local_of[op.bits[j]] < 0) return qsv_fail(QSV_EINVAL, "internal: gate target outside its pass's tile");
-        if (op.kind == QSV_OP_DIAG || op.kind == QSV_OP_PHASE) {
-            pg.form = PASS_DIAG_T;
-            if (op.kind == QSV_OP_PHASE) {           // k_diag with d0 = d1 = the phase (qsvk_phase)
-                for (int e = 0; e < 4; ++e) {
-                    pg.m[2 * e] = op.m[0];
-                    pg.m[2 * e + 1] = op.m[1];
-                }
-            } else {
-                leg[i][0] = local_of[op.bits[0]];
-                if (op.k == 2) leg[i][1] = local_of[op.bits[1]];
-                std::memcpy(pg.m, op.m, sizeof(double) * (2u << op.k));
-            }
-            continue;
-        }
-        if (op.kind == QSV_OP_PAIR) {               // qsvk_pair_exchange: (a, b) = (1, 0) <-> (0, 1)
-            pg.form = PASS_PAIR;
-            leg[i] = {local_of[op.bits[0]], local_of[op.bits[1]]};
-            need[i] = (1u << leg[i][0]) | (1u << leg[i][1]);
-            continue;
-        }
-        // dense: kernel index bit i <-> register bit kb[i], matrix re-indexed as the per-gate launcher does
-        const int k = op.k, D = 1 << k;
-        int kb[2] = {op.bits[0], op.bits[1]};
-        int form;
-        if (tile12_takes(st, k, op.bits, op.nctrl, op.cbits)) {      // launch_tile12: kernel bit leg <-> bits[leg]
-            form = k == 1 ? PASS_D2 : PASS_D4;
-        } else {                                                     // qsvk_dense: low targets first, then high ones
-            int low_b[2], high_b[2], nl = 0, nh = 0;
-            for (int j = 0; j < k; ++j) {
-                if (op.bits[j] >= QSV_LANE_BITS) high_b[nh++] = op.bits[j];
-                else low_b[nl++] = op.bits[j];
-            }
-            for (int j = 0; j < nl; ++j) kb[j] = low_b[j];
-            for (int j = 0; j < nh; ++j) kb[nl + j] = high_b[j];
-            form = nl == 0 ? (k == 1 ? PASS_D2 : PASS_D4) : nh == 0 ? (k == 1 ? PASS_D2X : PASS_D4X) : PASS_D4HL;
-        }
-        pg.form = form;
-        auto user_index = [&](int kidx) {        // matrix index of kernel index kidx (leg 0 = most significant)
-            int u = 0;
-            for (int i2 = 0; i2 < k; ++i2) {
-                const int bitval = (kidx >> i2) & 1;
-                for (int j = 0; j < k; ++j)
-                    if (op.bits[j] == kb[i2]) u |= bitval << (k - 1 - j);
-            }
-            return u;
-        };
-        for (int r = 0; r < D; ++r)
-            for (int c = 0; c < D; ++c) {
-                const int ur = user_index(r), uc = user_index(c);
-                pg.m[2 * (r * D + c)] = op.m[2 * (ur * D + uc)];
-                pg.m[2 * (r * D + c) + 1] = op.m[2 * (ur * D + uc) + 1];
-            }
-        for (int i2 = 0; i2 < k; ++i2) {
-            leg[i][i2] = local_of[kb[i2]];
-            need[i] |= 1u << leg[i][i2];
-        }
-    }
-    const std::vector<qsv_plan::Group> cut = qsv_plan::cut_groups(need);
-    std::vector<PassGroup> grp(cut.size());
-    for (size_t p = 0; p < cut.size(); ++p) {
-        PassGroup &gr = grp[p];
-        std::memset(&gr, 0, sizeof(gr));
-        gr.first = cut[p].first;
-        gr.count = cut[p].count;
-        int reg_of[qsv_plan::TILE_BITS];       // register bit of a tile index, -1: a thread bit
-        for (int t = 0; t < qsv_plan::TILE_BITS; ++t) reg_of[t] = -1;
-        for (int j = 0; j < qsv_plan::REG_BITS; ++j) {
-            gr.q[j] = cut[p].reg[j];
-            reg_of[gr.q[j]] = j;
-        }
-        for (int i = gr.first; i < gr.first + gr.count; ++i) {
-            PassGate &pg = rec[i];
-            gr.gates |= 1ull << i;
-            for (int t = 0; t < qsv_plan::TILE_BITS; ++t)
-                if ((cmask[i] >> t) & 1) {
-                    if (reg_of[t] >= 0) pg.rc |= 1u << reg_of[t];
-                    else pg.tc |= 1u << t;
-                }
-            const int l0 = leg[i][0], l1 = leg[i][1];
-            if (pg.form == PASS_DIAG_T) {
-                const int r0 = l0 >= 0 ? reg_of[l0] : -1, r1 = l1 >= 0 ? reg_of[l1] : -1;
-                auto swap_d1_d2 = [&pg]() {          // d[(s0 << 1) | s1] -> d[(s1 << 1) | s0]
-                    std::swap(pg.m[2], pg.m[4]);
-                    std::swap(pg.m[3], pg.m[5]);
-                };
-                if (l0 < 0) {                        // a phase: the same factor whatever the bits
-                    pg.tz0 = pg.tz1 = 0;
-                } else if (l1 < 0) {
-                    if (r0 >= 0) {
-                        pg.form = PASS_DIAG_R1;
-                        pg.code = r0;
-                    } else {                         // d[s0] as d[(s0 << 1) | s0]
-                        pg.m[6] = pg.m[2];
-                        pg.m[7] = pg.m[3];
-                        pg.tz0 = pg.tz1 = l0;
-                    }
-                } else if (r0 >= 0 && r1 >= 0) {
-                    pg.form = PASS_DIAG_R2;
-                    if (r0 > r1) swap_d1_d2();
-                    pg.code = std::min(r0, r1) * 4 + std::max(r0, r1);
-                } else if (r0 >= 0 || r1 >= 0) {     // d[(register bit << 1) | thread bit]
-                    pg.form = PASS_DIAG_M;
-                    if (r0 < 0) swap_d1_d2();
-                    pg.code = r0 >= 0 ? r0 : r1;
-                    pg.tz0 = r0 >= 0 ? l1 : l0;
-                } else {
-                    pg.tz0 = l0;
-                    pg.tz1 = l1;
-                }
-                continue;
-            }
-            const int r0 = reg_of[l0], r1 = l1 >= 0 ? reg_of[l1] : 0;
-            if (r0 < 0 || r1 < 0) return qsv_fail(QSV_EINVAL, "internal: gate target outside its group's register bits");
-            if (pg.form == PASS_PAIR) pg.code = std::min(r0, r1) * 4 + std::max(r0, r1);
-            else if (pg.form == PASS_D2 || pg.form == PASS_D2X) pg.code = r0;
-            else pg.code = r0 * 4 + r1;
-        }
-    }
+    const PassRecords pr = pass_records(ops, count, tile_high, st->amps);
+    if (pr.status == PassRecords::TARGET_OUTSIDE_TILE) return qsv_fail(QSV_EINVAL, "internal: gate target outside its pass's tile");
+    if (pr.status == PassRecords::TARGET_OUTSIDE_GROUP) return qsv_fail(QSV_EINVAL, "internal: gate target outside its group's register bits");
     StageRef staged;
-    int rc = qsvk_stage(st, rec.data(), sizeof(PassGate) * rec.size(), grp.data(), sizeof(PassGroup) * grp.size(), &staged);
+    int rc = qsvk_stage(st, pr.rec.data(), sizeof(PassGate) * pr.rec.size(), pr.grp.data(), sizeof(PassGroup) * pr.grp.size(), &staged);
     if (rc) return rc;
     const PassGate *dev_g = reinterpret_cast<const PassGate *>(staged.dev);
-    const PassGroup *dev_p = reinterpret_cast<const PassGroup *>(staged.dev + qsv_pad16(sizeof(PassGate) * rec.size()));
-    const int n_groups = static_cast<int>(grp.size());
+    const PassGroup *dev_p = reinterpret_cast<const PassGroup *>(staged.dev + qsv_pad16(sizeof(PassGate) * pr.rec.size()));
+    const int n_groups = static_cast<int>(pr.grp.size());
+    const std::vector<int> tile_bits(pr.tile_bits, pr.tile_bits + qsv_plan::TILE_BITS);
     PassArgs pa;
     std::memset(&pa, 0, sizeof(pa));
-    BigArgs &g = pa.g;
-    g.W = st->amps >> qsv_plan::TILE_BITS;      // tiles: the index with every tile bit taken out
-    g.nins = qsv_plan::TILE_BITS;
-    for (int j = 0; j < qsv_plan::TILE_BITS; ++j) g.pos[j] = static_cast<uint32_t>(tile_bits[j]);
-    for (int row = 0; row < PASS_ROWS; ++row)
-        for (int j = 0; j < qsv_plan::HIGH_BITS; ++j)
-            if ((row >> j) & 1) pa.row_off[row] |= 1ull << tile_bits[QSV_LANE_BITS + j];
-    g.regions = st->remap >= 0 ? static_cast<uint32_t>(st->remap) : 8;
+    pa.g = with_enumeration<BigArgs>(enumeration(st->amps >> qsv_plan::TILE_BITS, tile_bits));   // tiles: the index with every tile bit taken out
+    const std::vector<uint64_t> row_off = offsets(std::vector<int>(tile_bits.begin() + QSV_LANE_BITS, tile_bits.end()));
+    std::copy(row_off.begin(), row_off.end(), pa.row_off);
+    pa.g.regions = regions_or(st, 8);
     const bool nt = st->nontemporal != 0;
     snprintf(st->last_kernel, sizeof(st->last_kernel), "k_pass_tile<%s>", nt ? "true" : "false");
-    const uint64_t per_launch = 1ull << 23;       // tiles per dispatch (a power of two: the tile order stays whole)
-    for (g.w0 = 0; g.w0 < g.W; g.w0 += per_launch) {
-        const dim3 gd(static_cast<unsigned>(std::min(per_launch, g.W - g.w0))), bd(PASS_THREADS);
-        if (nt) hipLaunchKernelGGL(k_pass_tile<true>, gd, bd, 0, st->stream, st->data, pa, dev_g, count, dev_p, n_groups);
-        else hipLaunchKernelGGL(k_pass_tile<false>, gd, bd, 0, st->stream, st->data, pa, dev_g, count, dev_p, n_groups);
-        rc = check_launch();
-        if (rc) return rc;
-    }
-    return qsvk_stage_done(st, staged);
+    rc = launch_ranges(pa.g, DISPATCH_TILES, [&](uint64_t tiles) {
+        const dim3 gd(static_cast<unsigned>(tiles)), bd(PASS_THREADS);
+        with_bool(nt, [&](auto NT) { hipLaunchKernelGGL(k_pass_tile<NT.value>, gd, bd, 0, st->stream, st->data, pa, dev_g, count, dev_p, n_groups); });
+    });
+    return rc ? rc : qsvk_stage_done(st, staged);
 }
 
 // k = 5 (complex matrices) and k = 6 on the matrix cores (k_dense_mfma).  bits[j] = bit position of matrix leg j (leg 0
 // most significant).
-static int launch_dense_mfma(qsv_state *st, int k, const int *bits, const double *m_user) {
+static int launch_dense_mfma(qsv_state *st, int k, const int *bits, const double *m_user, const FormChoice &f) {
     const int D = 1 << k;
     // A wave's 16 lanes li are the 16 lowest free index values and its 4 lanes lk the two lowest target bits, so a
     // wave-instruction covers whole 128-byte lines wherever the targets sit, unless bits 0, 1 AND 2 are all targets
     // (then it covers half lines, and the other half follows in the next instruction of the same wave): 2.9-3.1 ms at
     // every placement.  (Round 2 first moved low targets away with a qubit permutation before and after: 6.2 ms.)
-    const std::vector<int> tb(bits, bits + k);
-    std::vector<int> sorted(tb);
+    std::vector<int> sorted(bits, bits + k);
     std::sort(sorted.begin(), sorted.end());
     // register / matrix index c: bit i <-> sorted[i]
-    std::vector<uint64_t> off(D, 0);
-    for (int c = 0; c < D; ++c)
-        for (int i = 0; i < k; ++i)
-            if ((c >> i) & 1) off[c] |= 1ull << sorted[i];
-    auto user_index = [&](int c) {
-        int u = 0;
-        for (int leg = 0; leg < k; ++leg)
-            for (int i = 0; i < k; ++i)
-                if (sorted[i] == tb[leg]) u |= ((c >> i) & 1) << (k - 1 - leg);
-        return u;
-    };
-    bool real_matrix = true;
-    for (int i = 0; i < D * D && real_matrix; ++i) real_matrix = m_user[2 * i + 1] == 0.0;
-    std::vector<double> m(real_matrix ? D * D : 2 * D * D);  // [plane][col][row]
-    std::vector<int> ui(D);
-    for (int c = 0; c < D; ++c) ui[c] = user_index(c);
-    for (int r = 0; r < D; ++r)
-        for (int c = 0; c < D; ++c) {
-            const int ur = ui[r], uc = ui[c];
-            m[c * D + r] = m_user[2 * (ur * D + uc)];
-            if (!real_matrix) m[D * D + c * D + r] = m_user[2 * (ur * D + uc) + 1];
-        }
+    const std::vector<uint64_t> off = offsets(sorted);
+    const std::vector<double> m = matrix(f.realm ? MAT_COLUMNS_REAL : MAT_COLUMNS, D, m_user, user_index(k, bits, sorted.data()).data());
     StageRef staged;
     int rc = qsvk_stage(st, m.data(), sizeof(double) * m.size(), off.data(), sizeof(uint64_t) * D, &staged);
     if (rc) return rc;
     const double *dev_m = reinterpret_cast<const double *>(staged.dev);
     const uint64_t *dev_off = reinterpret_cast<const uint64_t *>(staged.dev + qsv_pad16(sizeof(double) * m.size()));
-    Mfma6Args g;
-    std::memset(&g, 0, sizeof(g));
-    g.W = st->amps >> k;
-    g.nins = k;
-    for (int i = 0; i < k; ++i) g.pos[i] = static_cast<uint32_t>(sorted[i]);
+    const Mfma6Args g = with_enumeration<Mfma6Args>(enumeration(st->amps >> k, sorted));
     const bool nt = st->nontemporal != 0;
-    const size_t lds = sizeof(double) * (real_matrix ? 1 : 2) * D * D + sizeof(uint64_t) * D;
+    const size_t lds = sizeof(double) * m.size() + sizeof(uint64_t) * D;
     int cus = 256;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, st->device);  // 256 if the query fails
     const uint64_t wave_tiles = g.W / 16;
-    const unsigned grid = static_cast<unsigned>(std::min<uint64_t>((wave_tiles + 3) / 4, ((k == 6 && !real_matrix) ? 2ull : 3ull) * cus));
-    const bool m3 = !real_matrix && st->complex_product != 4;   // three real MFMAs per complex entry
+    const unsigned grid = static_cast<unsigned>(std::min<uint64_t>((wave_tiles + 3) / 4, ((k == 6 && !f.realm) ? 2ull : 3ull) * cus));
     snprintf(st->last_kernel, sizeof(st->last_kernel), "k_dense_mfma<%d, %s, %s%s>", k, nt ? "true" : "false",
-             real_matrix ? "true" : "false", m3 ? ", true" : "");
-#define QSV_LAUNCH_MFMA(KK, N, ...)                                                                                \
-    do {                                                                                                           \
-        QSV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_dense_mfma<KK, N, __VA_ARGS__>),              \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));           \
-        hipLaunchKernelGGL((k_dense_mfma<KK, N, __VA_ARGS__>), dim3(grid), dim3(QSV_BLOCK), lds, st->stream,       \
-                           st->data, g, dev_m, dev_off);                                                           \
-    } while (0)
-    if (k == 6 && m3) {
-        if (nt) QSV_LAUNCH_MFMA(6, true, false, true);
-        else QSV_LAUNCH_MFMA(6, false, false, true);
-    } else if (k == 6) {
-        if (nt) { if (real_matrix) QSV_LAUNCH_MFMA(6, true, true); else QSV_LAUNCH_MFMA(6, true, false); }
-        else { if (real_matrix) QSV_LAUNCH_MFMA(6, false, true); else QSV_LAUNCH_MFMA(6, false, false); }
-    } else if (m3) {
-        if (nt) QSV_LAUNCH_MFMA(5, true, false, true);
-        else QSV_LAUNCH_MFMA(5, false, false, true);
-    } else {
-        if (nt) { if (real_matrix) QSV_LAUNCH_MFMA(5, true, true); else QSV_LAUNCH_MFMA(5, true, false); }
-        else { if (real_matrix) QSV_LAUNCH_MFMA(5, false, true); else QSV_LAUNCH_MFMA(5, false, false); }
-    }
-#undef QSV_LAUNCH_MFMA
-    rc = check_launch();
-    if (rc) return rc;
-    return qsvk_stage_done(st, staged);
+             f.realm ? "true" : "false", f.m3 ? ", true" : "");
+    auto launch = [&](auto kernel) -> int {
+        QSV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(QSV_BLOCK), lds, st->stream, st->data, g, dev_m, dev_off);
+        return check_launch();
+    };
+    rc = with_int<5, 6>(k, [&](auto K) { return with_bool(f.realm, [&](auto REAL) { return with_bool(nt, [&](auto NT) {
+        if constexpr (!REAL.value) {
+            if (f.m3) return launch(k_dense_mfma<K.value, NT.value, false, true>);
+        }
+        return launch(k_dense_mfma<K.value, NT.value, REAL.value>);
+    }); }); });
+    return rc ? rc : qsvk_stage_done(st, staged);
 }
 
 int qsvk_generic(qsv_state *st, int k, const int *bits, const double *m_user) {
     if (k < 1 || k > QSV_MAX_K) return qsv_fail(QSV_EINVAL, "generic gate: k must be in 1..6");
-    // matrix-core form: the 2^(n-k) groups must fill whole waves of 16
-    const bool mfma_ok = st->n >= k && (st->amps >> k) >= 16;
-    if (k == 6 && mfma_ok && st->kq_variant == 0) return launch_dense_mfma(st, 6, bits, m_user);
-    if (k == 5 && mfma_ok && st->kq_variant == 5) return launch_dense_mfma(st, 5, bits, m_user);
-    // (k = 5 on the matrix cores is a measurement variant only: on the benchmark circuit's fused blocks it wins where its
-    // wave-instructions cover >= 512 contiguous bytes and the other targets are low (1.50 against 1.66 ms), loses with
-    // targets above bit 18 (1.8-1.9 against 1.65), and over the whole circuit ties with the vector kernels: 28.3 ms both)
-    if (k >= 3 && k <= 6 && st->n >= k) {
-        const int rc_big = launch_dense_big(st, k, bits, m_user);
-        if (rc_big != QSV_UNHANDLED_KQ) return rc_big;
-    }
+    const FormChoice f = choose_form(st->n, st->amps, k, bits, is_real(1 << k, m_user),
+                                     FormOptions{st->kq_variant, st->complex_product, mtile_default()});
+    if (f.form == FORM_MFMA) return launch_dense_mfma(st, k, bits, m_user, f);
+    if (f.form != FORM_GATHER) return launch_dense_big(st, k, bits, m_user, f);
     const size_t bytes = sizeof(double) * 2ull << (2 * k);
     StageRef staged;
     int rc = qsvk_stage(st, m_user, bytes, nullptr, 0, &staged);
@@ -3584,40 +2928,14 @@ int qsvk_dense(qsv_state *st, int k, const int *bits, int nctrl, const int *cbit
     const int KH = static_cast<int>(high.size()), KL = static_cast<int>(low.size());
     int rc = fill_enumeration(st, g, high, nctrl, cbits);
     if (rc) return rc;
-    for (int h = 0; h < (1 << KH); ++h) {
-        uint64_t o = 0;
-        for (int i = 0; i < KH; ++i)
-            if ((h >> i) & 1) o |= 1ull << high[i];
-        g.hoff[h] = o;
-    }
+    const std::vector<uint64_t> hoff = offsets(high), lxor = offsets(low);
+    std::copy(hoff.begin(), hoff.end(), g.hoff);
+    std::copy(lxor.begin(), lxor.end(), g.lxor);   // lane xor mask of low-bit combination x
     for (int j = 0; j < KL; ++j) g.lbit[j] = low[j];
-    for (int x = 0; x < (1 << KL); ++x) {
-        int mask = 0;
-        for (int j = 0; j < KL; ++j)
-            if ((x >> j) & 1) mask |= 1 << low[j];
-        g.lxor[x] = mask;
-    }
     // kernel order: index = (h << KL) | l, h bit i <-> high[i], l bit i <-> low[i]
-    const int D = 1 << k;
-    auto user_index = [&](int kidx) {
-        const int h = kidx >> KL, l = kidx & ((1 << KL) - 1);
-        int u = 0;
-        for (int j = 0; j < k; ++j) {
-            int bitval = 0;
-            for (int i = 0; i < KH; ++i)
-                if (high[i] == bits[j]) bitval = (h >> i) & 1;
-            for (int i = 0; i < KL; ++i)
-                if (low[i] == bits[j]) bitval = (l >> i) & 1;
-            u |= bitval << (k - 1 - j);
-        }
-        return u;
-    };
-    for (int r = 0; r < D; ++r)
-        for (int c = 0; c < D; ++c) {
-            const int ur = user_index(r), uc = user_index(c);
-            g.m[2 * (r * D + c)] = m_user[2 * (ur * D + uc)];
-            g.m[2 * (r * D + c) + 1] = m_user[2 * (ur * D + uc) + 1];
-        }
+    std::vector<int> kb(low);
+    kb.insert(kb.end(), high.begin(), high.end());
+    write_matrix(MAT_COMPLEX, 1 << k, m_user, user_index(k, bits, kb.data()).data(), g.m);
     return dispatch_dense(st, KH, KL, g);
 }
 
@@ -3633,13 +2951,8 @@ int qsvk_pair_exchange(qsv_state *st, int bit_a, int bit_b) {
         sg.m[4] = 1.0;   // m[1][0]
         sg.off[0] = 1ull << bit_a;
         sg.off[1] = 1ull << bit_b;
-        BigArgs t;
-        std::memset(&t, 0, sizeof(t));
-        t.W = quarter;
-        t.nins = 2;
-        t.pos[0] = static_cast<uint32_t>(std::min(bit_a, bit_b));
-        t.pos[1] = static_cast<uint32_t>(std::max(bit_a, bit_b));
-        t.regions = st->remap >= 0 ? static_cast<uint32_t>(st->remap) : 8;
+        BigArgs t = with_enumeration<BigArgs>(enumeration(quarter, {bit_a, bit_b}));
+        t.regions = regions_or(st, 8);
         return launch_tile12_kernels(st, 1, true, t, sg);
     }
     GateArgs g;
@@ -3975,13 +3288,7 @@ int qsvk_reduced_density(qsv_state *st, int k, const int *bits, double *rho_out)
     QSV_HIP(hipMemcpyAsync(raw.data(), d_out, b_out, hipMemcpyDeviceToHost, st->stream));
     QSV_HIP(hipStreamSynchronize(st->stream));
     // kernel order (row bit i <-> sorted[i]) -> caller order (bit k-1-j <-> bits[j])
-    auto user_index = [&](int c) {
-        int u = 0;
-        for (int leg = 0; leg < k; ++leg)
-            for (int i = 0; i < k; ++i)
-                if (sorted[i] == bits[leg]) u |= ((c >> i) & 1) << (k - 1 - leg);
-        return u;
-    };
+    const std::vector<int> ui = user_index(k, bits, sorted.data());
     for (int r = 0; r < D; ++r)
         for (int c = 0; c < D; ++c) {
             double vr, vi;
@@ -4011,7 +3318,7 @@ int qsvk_reduced_density(qsv_state *st, int k, const int *bits, double *rho_out)
                 vr = raw[2 * (r * D + c)];
                 vi = raw[2 * (r * D + c) + 1];
             }
-            const int ur = user_index(r), uc = user_index(c);
+            const int ur = ui[r], uc = ui[c];
             rho_out[2 * (ur * D + uc)] = vr;
             rho_out[2 * (ur * D + uc) + 1] = vi;
         }

@@ -1,0 +1,195 @@
+// TEST INFRASTRUCTURE: prints what qsv_layout.h computes for requests read from stdin (tests/test_layout_host.py).
+//
+// One request per input line, one answer line per request; numbers are decimal integers, doubles are printed as %a.
+//   split n k bits..                         -> enough KB | high.. | low.. | standin..
+//   order n k transposed a_in_place bits..   -> kernel_bits.. | address_bits.. | inserted_bits..
+//   offsets nb addr_bit..                    -> off[0 .. 2^nb)
+//   ui k bits.. kernel_bit..                 -> ui[0 .. 2^k)
+//   matrix layout D rows ui.. m_user..       -> the doubles written (m_user: 2 D D doubles)
+//   enum W or_mask nins inserted..           -> W or_mask nins pos..
+//   low n k bits..                           -> amask bmask na | abit.. | aE.. | bdep[0..8)
+//   seq arity j0 j1 m..                      -> code m[0..32)
+//   takes n k nctrl bits.. cbits..           -> 0 / 1
+//   tilecut n k ngates bits.. {arity leg0 leg1 m..}..  -> status | tile_bits.. | passes {first count q0..q3}.. | {code m[0..32)}..
+//   limits                                   -> DISPATCH_TILES DISPATCH_ITEMS TILE_SEQ_MAX_PASSES
+//   ranges W limit                           -> {w0 count}..
+//   form n k real variant complex_product mtile bits..  -> form transposed realm m3
+//   pass n tile_high count {kind k b0 b1 nctrl cbits.. m[0..32)}..
+//                                            -> status | tile_bits.. | groups {first count q0..q3 gates}.. | {form code rc tc tz0 tz1 omask m[0..32)}..
+#include <cstdio>
+#include <iostream>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "qsv_layout.h"
+
+using namespace qsv_layout;
+
+static std::vector<int> ints(std::istream &in, int count) {
+    std::vector<int> v(count > 0 ? count : 0);
+    for (int &x : v) in >> x;
+    return v;
+}
+static std::vector<double> doubles(std::istream &in, size_t count) {
+    std::vector<double> v(count);
+    for (double &x : v) in >> x;
+    return v;
+}
+template <class V>
+static void put_ints(const V &v) {
+    for (auto x : v) std::printf(" %lld", static_cast<long long>(x));
+}
+static void put_doubles(const double *m, size_t count) {
+    for (size_t i = 0; i < count; ++i) std::printf(" %a", m[i]);
+}
+
+int main() {
+    std::string line;
+    while (std::getline(std::cin, line)) {
+        std::istringstream in(line);
+        std::string what;
+        if (!(in >> what)) continue;
+        if (what == "split" || what == "low") {
+            int n, k;
+            in >> n >> k;
+            const std::vector<int> bits = ints(in, k);
+            const Split s = split_targets(k, bits.data(), n);
+            if (what == "split") {
+                std::printf("%d %d |", s.enough ? 1 : 0, s.KB);
+                put_ints(s.high);
+                std::printf(" |");
+                put_ints(s.low);
+                std::printf(" |");
+                put_ints(s.standin);
+            } else {
+                if (!s.enough) return 3;
+                const LowFields f = low_fields(s);
+                LdsArgs g = with_enumeration<LdsArgs>(enumeration(1, inserted_bits(s)));
+                set_low_fields(g, f);
+                std::printf("%u %u %d |", g.amask, g.bmask, g.na);
+                put_ints(std::vector<int>(g.abit, g.abit + g.na));
+                std::printf(" |");
+                put_ints(std::vector<int>(g.aE, g.aE + g.na));
+                std::printf(" |");
+                put_ints(std::vector<uint32_t>(g.bdep, g.bdep + 8));
+            }
+        } else if (what == "order") {
+            int n, k, transposed, a_in_place;
+            in >> n >> k >> transposed >> a_in_place;
+            const std::vector<int> bits = ints(in, k);
+            const Split s = transposed ? split_targets(k, bits.data(), n) : untransposed(k, bits.data());
+            if (!s.enough) return 3;
+            put_ints(kernel_bits(s));
+            std::printf(" |");
+            put_ints(address_bits(s, a_in_place != 0));
+            std::printf(" |");
+            put_ints(inserted_bits(s));
+        } else if (what == "offsets") {
+            int nb;
+            in >> nb;
+            put_ints(offsets(ints(in, nb)));
+        } else if (what == "ui") {
+            int k;
+            in >> k;
+            const std::vector<int> bits = ints(in, k), kb = ints(in, k);
+            put_ints(user_index(k, bits.data(), kb.data()));
+        } else if (what == "matrix") {
+            int layout, D, rows;
+            in >> layout >> D >> rows;
+            const std::vector<int> ui = ints(in, D);
+            const std::vector<double> m_user = doubles(in, 2ull * D * D);
+            const std::vector<double> m = matrix(static_cast<MatrixLayout>(layout), D, m_user.data(), ui.data(), rows);
+            std::printf("%d", is_real(D, m_user.data()) ? 1 : 0);
+            put_doubles(m.data(), m.size());
+        } else if (what == "enum") {
+            unsigned long long W, or_mask;
+            int nins;
+            in >> W >> or_mask >> nins;
+            const BigArgs g = with_enumeration<BigArgs>(enumeration(W, ints(in, nins), or_mask));
+            std::printf("%llu %llu %d", static_cast<unsigned long long>(g.W), static_cast<unsigned long long>(g.or_mask), g.nins);
+            put_ints(std::vector<uint32_t>(g.pos, g.pos + g.nins));
+        } else if (what == "seq") {
+            int arity, j0, j1;
+            in >> arity >> j0 >> j1;
+            const std::vector<double> m = doubles(in, arity == 1 ? 8 : 32);
+            const SeqGate r = seq_record(arity, j0, j1, m.data());
+            std::printf("%d", r.code);
+            put_doubles(r.m, 32);
+        } else if (what == "takes") {
+            int n, k, nctrl;
+            in >> n >> k >> nctrl;
+            const std::vector<int> bits = ints(in, k), cbits = ints(in, nctrl);
+            std::printf("%d", tile12_takes(1ull << n, k, bits.data(), nctrl, cbits.data()) ? 1 : 0);
+        } else if (what == "tilecut") {
+            int n, k, ngates;
+            in >> n >> k >> ngates;
+            const std::vector<int> bits = ints(in, k);
+            std::vector<int> arity(ngates), legs(2 * ngates);
+            std::vector<double> mats;
+            for (int g = 0; g < ngates; ++g) {
+                in >> arity[g] >> legs[2 * g] >> legs[2 * g + 1];
+                const std::vector<double> m = doubles(in, arity[g] == 1 ? 8 : 32);
+                mats.insert(mats.end(), m.begin(), m.end());
+            }
+            const TileCut cut = cut_tile_passes(n, k, bits.data(), ngates, arity.data(), legs.data(), mats.data());
+            std::printf("%d |", static_cast<int>(cut.status));
+            if (cut.status == TileCut::OK) {
+                put_ints(cut.tile_bits);
+                std::printf(" | %zu", cut.passes.size());
+                for (const TilePass &p : cut.passes) std::printf(" %d %d %d %d %d %d", p.first, p.count, p.q[0], p.q[1], p.q[2], p.q[3]);
+                std::printf(" |");
+                for (const SeqGate &r : cut.rec) {
+                    std::printf(" %d", r.code);
+                    put_doubles(r.m, 32);
+                }
+            }
+        } else if (what == "limits") {
+            std::printf("%llu %llu %d", static_cast<unsigned long long>(DISPATCH_TILES),
+                        static_cast<unsigned long long>(DISPATCH_ITEMS), TILE_SEQ_MAX_PASSES);
+        } else if (what == "ranges") {
+            unsigned long long W, limit;
+            in >> W >> limit;
+            for (const Range &r : dispatch_ranges(W, limit))
+                std::printf(" %llu %llu", static_cast<unsigned long long>(r.w0), static_cast<unsigned long long>(r.count));
+        } else if (what == "form") {
+            int n, k, real, variant, cp, mtile;
+            in >> n >> k >> real >> variant >> cp >> mtile;
+            const std::vector<int> bits = ints(in, k);
+            const FormChoice f = choose_form(n, 1ull << n, k, bits.data(), real != 0, FormOptions{variant, cp, mtile != 0});
+            std::printf("%d %d %d %d", static_cast<int>(f.form), f.transposed ? 1 : 0, f.realm ? 1 : 0, f.m3 ? 1 : 0);
+        } else if (what == "pass") {
+            int n, count;
+            unsigned long long tile_high;
+            in >> n >> tile_high >> count;
+            std::vector<Op> ops(count);
+            std::vector<const Op *> ptr;
+            for (Op &op : ops) {
+                in >> op.kind >> op.k >> op.bits[0] >> op.bits[1] >> op.nctrl;
+                if (op.nctrl < 0 || op.nctrl > OP_MAX_CTRL) return 2;
+                for (int c = 0; c < op.nctrl; ++c) in >> op.cbits[c];
+                for (double &x : op.m) in >> x;
+                ptr.push_back(&op);
+            }
+            const PassRecords pr = pass_records(ptr.data(), count, tile_high, 1ull << n);
+            std::printf("%d |", static_cast<int>(pr.status));
+            if (pr.status == PassRecords::OK) {
+                put_ints(std::vector<int>(pr.tile_bits, pr.tile_bits + qsv_plan::TILE_BITS));
+                std::printf(" | %zu", pr.grp.size());
+                for (const PassGroup &g : pr.grp)
+                    std::printf(" %d %d %d %d %d %d %llu", g.first, g.count, g.q[0], g.q[1], g.q[2], g.q[3], static_cast<unsigned long long>(g.gates));
+                std::printf(" |");
+                for (const PassGate &g : pr.rec) {
+                    std::printf(" %d %d %u %u %d %d %llu", g.form, g.code, g.rc, g.tc, g.tz0, g.tz1, static_cast<unsigned long long>(g.omask));
+                    put_doubles(g.m, 32);
+                }
+            }
+        } else {
+            return 2;
+        }
+        if (!in && !in.eof()) return 2;
+        std::printf("\n");
+    }
+    std::fflush(stdout);
+    return 0;
+}

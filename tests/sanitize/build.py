@@ -33,7 +33,7 @@ def build(verbose: bool = False) -> Path:
     if not CLANG.exists():
         raise RuntimeError(f"{CLANG} not found: the sanitized host build needs the ROCm clang")
     OUT.mkdir(exist_ok=True)
-    headers = [CSRC / "qsv_internal.h", CSRC / "qsv_linalg.h", REPO / "include" / "qsv.h"]
+    headers = [CSRC / "qsv_internal.h", CSRC / "qsv_linalg.h", CSRC / "qsv_plan.h", CSRC / "qsv_layout.h", REPO / "include" / "qsv.h"]
     objs = []
 
     def run(cmd):

@@ -204,6 +204,17 @@ int qsv_inner(qsv_state *a, qsv_state *b, double *re, double *im);
 /* <psi| P |psi> for the Pauli string P = paulis[0] on qubits[0] (x) paulis[1] on qubits[1] ... ('I','X','Y','Z'):
  * npq.expect (numpy_quantum.py:194-201) for tensor products of npq.PAULIS without building the 2^N operator. */
 int qsv_expect_pauli(qsv_state *st, int k, const int *qubits, const char *paulis, double *re, double *im);
+/* <psi| H |psi> for H = sum_t c_t P_t, every P_t a Pauli string as in qsv_expect_pauli (same letters, same qubit
+ * order): term t is paulis[j] on qubits[j] for j in [term_offsets[t], term_offsets[t+1]), at most 64 letters, qubits
+ * distinct within a term; coeffs holds n_terms interleaved complex c_t (NULL: all 1).  Terms that flip the same
+ * qubits (equal X/Y positions: all Z-only terms and the identity; XX and YY on one pair) share passes over the
+ * register: each pass reads every amplitude once, forms conj(psi[i ^ xmask]) psi[i] once per pair and accumulates up
+ * to 8 terms from it, where qsv_expect_pauli reads the register twice per term.  All passes of a call are launched back
+ * to back with one synchronisation at the end.  term_values (may be NULL) receives the n_terms real numbers
+ * <psi|P_t|psi> in the caller's order, (re, im) = sum_t c_t <psi|P_t|psi>, passes (may be NULL) the number of kernel
+ * launches made.  The whole list is validated before the first launch; n_terms = 0 gives 0 and no launch. */
+int qsv_expect_pauli_sum(qsv_state *st, int n_terms, const int *term_offsets, const int *qubits, const char *paulis,
+                         const double *coeffs, double *term_values, double *re, double *im, uint64_t *passes);
 /* Reduced density matrix of the k <= 6 qubits `qubits` (all others traced out) in one read pass over the register:
  * rho[i][j] = sum_rest psi[i, rest] conj(psi[j, rest]), written row-major as 4^k complex numbers, qubits[0] the most
  * significant bit of i and j.  What a caller of the reference gets from npq.ket2dm (numpy_quantum.py:110-113)

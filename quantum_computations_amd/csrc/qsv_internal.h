@@ -9,6 +9,7 @@
 
 #include "qsv.h"
 #include "qsv_layout.h"
+#include "qsv_pauli_plan.h"
 
 // One amplitude = complex128 = one 16-byte vector: exactly one dwordx4 per lane, 1 KiB per wave64 access.
 typedef double amp_t __attribute__((ext_vector_type(2)));
@@ -154,6 +155,8 @@ int qsvk_norm2(qsv_state *st, double *out);
 int qsvk_inner(qsv_state *a, qsv_state *b, double *re, double *im);
 int qsvk_probabilities(qsv_state *st, const uint64_t *indices, int count, double *out);
 int qsvk_expect_pauli(qsv_state *st, uint64_t xmask, uint64_t zmask, int n_y, double *re, double *im);
+// every pass of a qsv_expect_pauli_sum plan: values[index of the term in the caller's list] = <psi|P|psi>, one synchronisation
+int qsvk_expect_pauli_groups(qsv_state *st, const std::vector<qsv_pauli_plan::Pass> &passes, double *values);
 int qsvk_reduced_density(qsv_state *st, int k, const int *bits, double *rho_out);
 int qsvk_expect_density(qsv_state *ket, qsv_state *rho, double *re, double *im);
 int qsvk_sample(qsv_state *st, int shots, const double *u, uint64_t *out);

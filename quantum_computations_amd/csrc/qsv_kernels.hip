@@ -941,6 +941,75 @@ __global__ __launch_bounds__(QSV_BLOCK) void k_expect_pauli(const amp_t *__restr
     }
 }
 
+// One planned pass of qsv_expect_pauli_sum (qsv_pauli_plan.h): up to T Pauli strings with one shared xmask.
+struct PauliPassArgs {
+    uint64_t items;      // pairs (amps / 2), or amps for the diagonal group
+    uint64_t xmask;
+    int32_t pivot;       // lowest set bit of xmask (unused by the diagonal form)
+    uint32_t odd;        // bit t: term t has odd nY and accumulates Im c instead of Re c
+    uint64_t zmask[qsv_pauli_plan::PAULI_TERMS_PER_PASS];   // 0 beyond the pass's terms
+};
+
+// partials[block * T + t] = this block's share of sum_i s_t(i) Re c(i) (Im c(i) for odd nY) over the visited i:
+// every i for the diagonal group (c = |psi[i]|^2), the i with a clear pivot bit otherwise (c = conj(psi[i ^ xmask]) psi[i],
+// each amplitude read once).  The product is formed once per item; a term costs a sign and one double accumulator.
+// PAULI_ITEMS independent items are loaded before any is used, so a thread keeps 2 x PAULI_ITEMS 16-byte loads in flight.
+constexpr int PAULI_ITEMS = 4;
+
+template <int T, bool DIAG>
+__global__ __launch_bounds__(QSV_BLOCK) void k_expect_pauli_group(const amp_t *__restrict__ a, const PauliPassArgs g,
+                                                                 double *__restrict__ partials) {
+    double acc[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) acc[t] = 0.0;
+    auto add = [&](uint64_t i, double re, double im) {
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const double v = (!DIAG && ((g.odd >> t) & 1u)) ? im : re;
+            acc[t] += (__popcll(i & g.zmask[t]) & 1) ? -v : v;
+        }
+    };
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    uint64_t w = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x;
+    for (; w + (PAULI_ITEMS - 1) * stride < g.items; w += PAULI_ITEMS * stride) {
+        uint64_t i[PAULI_ITEMS];
+        amp_t x[PAULI_ITEMS], y[PAULI_ITEMS];
+#pragma unroll
+        for (int u = 0; u < PAULI_ITEMS; ++u) {
+            i[u] = DIAG ? w + u * stride : insert_zero(w + u * stride, g.pivot);
+            y[u] = a[i[u]];
+            if constexpr (!DIAG) x[u] = a[i[u] ^ g.xmask];
+        }
+#pragma unroll
+        for (int u = 0; u < PAULI_ITEMS; ++u) {
+            if constexpr (DIAG) add(i[u], y[u].x * y[u].x + y[u].y * y[u].y, 0.0);
+            else add(i[u], x[u].x * y[u].x + x[u].y * y[u].y, x[u].x * y[u].y - x[u].y * y[u].x);   // conj(x) * y
+        }
+    }
+    for (; w < g.items; w += stride) {
+        const uint64_t i = DIAG ? w : insert_zero(w, g.pivot);
+        const amp_t y = a[i];
+        if constexpr (DIAG) {
+            add(i, y.x * y.x + y.y * y.y, 0.0);
+        } else {
+            const amp_t x = a[i ^ g.xmask];
+            add(i, x.x * y.x + x.y * y.y, x.x * y.y - x.y * y.x);
+        }
+    }
+    __shared__ double sums[QSV_BLOCK / 64][T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        const double s = wave_sum(acc[t]);
+        if ((threadIdx.x & 63) == 0) sums[threadIdx.x >> 6][t] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < T) {
+        double s = 0.0;
+        for (int wv = 0; wv < QSV_BLOCK / 64; ++wv) s += sums[wv][threadIdx.x];
+        partials[static_cast<uint64_t>(blockIdx.x) * T + threadIdx.x] = s;
+    }
+}
+
 // Sampling, pass 1: chunk_sums[c] = sum of |amp|^2 over chunk c (SAMPLE_CHUNK consecutive amplitudes per workgroup).
 constexpr int SAMPLE_CHUNK = 4096;
 
@@ -3349,6 +3418,71 @@ int qsvk_expect_pauli(qsv_state *st, uint64_t xmask, uint64_t zmask, int n_y, do
         case 1: *re = -si; *im = sr; break;
         case 2: *re = -sr; *im = -si; break;
         default: *re = si; *im = -sr; break;
+    }
+    return QSV_OK;
+}
+
+// values[p.index[t]] = <psi|P|psi> of every term of every pass.  The launches go out back to back on the register's
+// stream, each with its own slice of the scratch buffer (one partial per workgroup and term); one copy and one
+// synchronisation at the end, then the host sums each term's partials in index order (deterministic).
+int qsvk_expect_pauli_groups(qsv_state *st, const std::vector<qsv_pauli_plan::Pass> &passes, double *values) {
+    if (passes.empty()) return QSV_OK;
+    struct Slice { size_t offset; int grid, width; };
+    std::vector<Slice> slices;
+    size_t doubles = 0;
+    for (const qsv_pauli_plan::Pass &p : passes) {
+        const int count = static_cast<int>(p.zmask.size());
+        if (count < 1 || count > qsv_pauli_plan::PAULI_TERMS_PER_PASS) return qsv_fail(QSV_EINVAL, "bad Pauli pass");
+        const uint64_t items = p.pivot < 0 ? st->amps : st->amps / 2;
+        const int grid = grid_for(items, QSV_BLOCK * 2 * PAULI_ITEMS, QSV_REDUCE_BLOCKS);
+        const int width = count <= 1 ? 1 : count <= 2 ? 2 : count <= 4 ? 4 : 8;
+        slices.push_back({doubles, grid, width});
+        doubles += static_cast<size_t>(grid) * width;
+    }
+    int rc = qsvk_ensure_matrix(st, sizeof(double) * doubles);
+    if (rc) return rc;
+    for (size_t k = 0; k < passes.size(); ++k) {
+        const qsv_pauli_plan::Pass &p = passes[k];
+        PauliPassArgs g;
+        std::memset(&g, 0, sizeof(g));
+        g.items = p.pivot < 0 ? st->amps : st->amps / 2;
+        g.xmask = p.xmask;
+        g.pivot = p.pivot < 0 ? 0 : p.pivot;
+        for (size_t t = 0; t < p.zmask.size(); ++t) {
+            g.zmask[t] = p.zmask[t];
+            if (p.n_y[t] & 1) g.odd |= 1u << t;
+        }
+        double *out = st->dev_matrix + slices[k].offset;
+        const dim3 gd(slices[k].grid), bd(QSV_BLOCK);
+#define QSV_PAULI_LAUNCH(W)                                                                                       \
+    do {                                                                                                          \
+        if (p.pivot < 0) hipLaunchKernelGGL((k_expect_pauli_group<W, true>), gd, bd, 0, st->stream, st->data, g, out);   \
+        else hipLaunchKernelGGL((k_expect_pauli_group<W, false>), gd, bd, 0, st->stream, st->data, g, out);       \
+    } while (0)
+        switch (slices[k].width) {
+            case 1: QSV_PAULI_LAUNCH(1); break;
+            case 2: QSV_PAULI_LAUNCH(2); break;
+            case 4: QSV_PAULI_LAUNCH(4); break;
+            default: QSV_PAULI_LAUNCH(8); break;
+        }
+#undef QSV_PAULI_LAUNCH
+        rc = check_launch();
+        if (rc) {
+            (void)hipStreamSynchronize(st->stream);
+            return rc;
+        }
+    }
+    std::vector<double> host(doubles);
+    QSV_HIP(hipMemcpyAsync(host.data(), st->dev_matrix, sizeof(double) * doubles, hipMemcpyDeviceToHost, st->stream));
+    QSV_HIP(hipStreamSynchronize(st->stream));
+    for (size_t k = 0; k < passes.size(); ++k) {
+        const qsv_pauli_plan::Pass &p = passes[k];
+        const Slice &s = slices[k];
+        for (size_t t = 0; t < p.zmask.size(); ++t) {
+            double sum = 0.0;
+            for (int b = 0; b < s.grid; ++b) sum += host[s.offset + static_cast<size_t>(b) * s.width + t];
+            values[p.index[t]] = qsv_pauli_plan::pair_scale(p.pivot, p.n_y[t]) * sum;
+        }
     }
     return QSV_OK;
 }

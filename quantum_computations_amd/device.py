@@ -308,6 +308,31 @@ class DeviceState:
         _lib.call("qsv_expect_pauli", self._h, len(qubits), _ints(qubits), paulis.encode(), C.byref(re), C.byref(im))
         return complex(re.value, im.value)
 
+    def expect_pauli_sum(self, terms, *, return_terms: bool = False):
+        """``<psi| H |psi>`` for ``H = sum_t c_t P_t``; ``terms`` is an iterable of ``(coefficient, letters, qubits)``
+        with letters and qubits as in ``expect_pauli``.  Terms that flip the same qubits share passes over the
+        register (all Z-only terms need one pass per eight terms; XX and YY on a pair share one), each pass reads
+        every amplitude once, and the whole sum costs one synchronisation.  Returns the complex value, or
+        ``(value, per-term real expectation values in the caller's order)`` with ``return_terms=True``."""
+        offsets, qubits, letters, coeffs = [0], [], [], []
+        for coefficient, paulis, qs in terms:
+            qs = [int(q) for q in qs]
+            if len(paulis) != len(qs):
+                raise ValueError("one Pauli letter per qubit")
+            qubits += qs
+            letters.append(str(paulis))
+            offsets.append(len(qubits))
+            coeffs.append(complex(coefficient))
+        count = len(coeffs)
+        cbuf = np.ascontiguousarray(coeffs, dtype=np.complex128).view(np.float64)
+        values = np.zeros(count, dtype=np.float64)
+        re, im = C.c_double(), C.c_double()
+        _lib.call("qsv_expect_pauli_sum", self._h, count, _ints(offsets), _ints(qubits), "".join(letters).encode(),
+                  cbuf.ctypes.data_as(C.POINTER(C.c_double)), values.ctypes.data_as(C.POINTER(C.c_double)),
+                  C.byref(re), C.byref(im), None)
+        value = complex(re.value, im.value)
+        return (value, values) if return_terms else value
+
     def sample(self, shots: int, rng=None) -> np.ndarray:
         """``shots`` computational-basis outcomes drawn from |amplitude|^2 (inverse-CDF on the device; the uniforms
         come from ``rng``, a ``numpy.random.Generator``, default the global ``np.random`` state).  No collapse."""

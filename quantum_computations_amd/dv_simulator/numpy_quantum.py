@@ -229,6 +229,67 @@ def expecth(oper: np.ndarray, state: np.ndarray):
     return expect(oper, state).real
 
 
+class PauliSum:
+    """``H = sum_t c_t P_t`` on ``n_qubits`` qubits; ``terms`` is a list of ``(coefficient, letters, qubits)`` with one
+    letter of I / X / Y / Z per listed qubit (qubit 0 is the leftmost factor, as everywhere in ``npq``)."""
+
+    def __init__(self, n_qubits: int, terms=()):
+        self.n_qubits = int(n_qubits)
+        self.terms = []
+        for coefficient, letters, qubits in terms:
+            letters, qubits = str(letters), [int(q) for q in qubits]
+            if len(letters) != len(qubits):
+                raise ValueError("one Pauli letter per qubit")
+            if len(set(qubits)) != len(qubits):
+                raise ValueError("Indices must be distinct.")
+            if any(q < 0 or q >= self.n_qubits for q in qubits):
+                raise ValueError(f"qubit index out of range for a {self.n_qubits}-qubit register")
+            if any(not is_pauli(letter) for letter in letters):
+                raise PauliError("Pauli letters must be I, X, Y or Z")
+            self.terms.append((complex(coefficient), letters, qubits))
+
+    def __add__(self, other: "PauliSum") -> "PauliSum":
+        if not isinstance(other, PauliSum):
+            return NotImplemented
+        if other.n_qubits != self.n_qubits:
+            raise ValueError("Pauli sums on registers of different sizes")
+        return PauliSum(self.n_qubits, self.terms + other.terms)
+
+    def __mul__(self, scalar) -> "PauliSum":
+        if not np.isscalar(scalar):
+            return NotImplemented
+        return PauliSum(self.n_qubits, [(scalar * c, letters, qubits) for c, letters, qubits in self.terms])
+
+    __rmul__ = __mul__
+
+    def __len__(self) -> int:
+        return len(self.terms)
+
+    def matrix(self) -> np.ndarray:
+        """The dense ``2^n x 2^n`` operator, by Kronecker products of ``PAULIS``; small n only."""
+        dim = 1 << self.n_qubits
+        total = np.zeros((dim, dim), dtype=complex)
+        for c, letters, qubits in self.terms:
+            factors = [IDTY] * self.n_qubits
+            for letter, q in zip(letters, qubits):
+                number = get_pauli_number(letter)
+                factors[q] = IDTY if number == 0 else PAULIS[number - 1]
+            total += c * tensor(*factors)
+        return total
+
+
+def expect_pauli_sum(hamiltonian: PauliSum, state) -> complex:
+    """``<state| H |state>`` for a ``PauliSum``, computed on the device in passes shared between the terms that flip
+    the same qubits (``DeviceState.expect_pauli_sum``).  A host ket is uploaded first: the product path has no CPU
+    fallback (``fidelity`` lifts host arrays the same way)."""
+    from ..device import DeviceState
+    if not isinstance(state, DeviceState):
+        state = DeviceState.from_numpy(np.asarray(state))
+    if state.num_qubits != hamiltonian.n_qubits:
+        raise TypeError("incompatible operator and state vector")
+    return state.expect_pauli_sum(hamiltonian.terms)
+
+
 # ---- sizes ----------------------------------------------------------------------------------------------------------
 def is_power_of_two(n: int) -> bool:
     return n > 0 and n & (n - 1) == 0

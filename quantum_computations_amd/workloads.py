@@ -212,3 +212,16 @@ def grover3_ops(tagged: list[int]) -> list[dict]:
     inserts = [{"name": "Insert", "indices": [q], "matrix": None, "state": "ZERO", "vector": npq.ZERO}
                for q in range(3)]
     return inserts + h3 + grover3_oracle_ops(tagged) + h3 + x3 + ccz_ops() + x3 + h3
+
+
+# ---- Hamiltonians as Pauli term lists: (coefficient, letters, qubits), what DeviceState.expect_pauli_sum takes -------
+def heisenberg_chain_terms(n: int, coupling: float = 1.0) -> list[tuple]:
+    """Open Heisenberg chain ``J sum_q (X_q X_q+1 + Y_q Y_q+1 + Z_q Z_q+1)``: 3 (n - 1) terms.  XX and YY of a pair
+    flip the same two qubits and share a pass; the n - 1 ZZ terms share the diagonal passes."""
+    return [(coupling, letters, [q, q + 1]) for q in range(n - 1) for letters in ("XX", "YY", "ZZ")]
+
+
+def ising_terms(n: int, h: float, coupling: float = 1.0) -> list[tuple]:
+    """Transverse-field Ising chain ``-J sum_q Z_q Z_q+1 - h sum_q X_q``: n - 1 couplings (one diagonal group) and n
+    field terms (one group each)."""
+    return [(-coupling, "ZZ", [q, q + 1]) for q in range(n - 1)] + [(-h, "X", [q]) for q in range(n)]

@@ -100,7 +100,8 @@ typedef struct qsv_state qsv_state;
  *  - A rejected call (QSV_EINVAL, ...) returns at once and leaves the queue as it was.
  *  - Every other entry point that takes the register flushes the queue first: sync, download, upload, copy (both
  *    registers), fill_random, scale, set_basis, norm2, inner, expect_*, probabilities, reduced_density, sample,
- *    measure*, collapse, insert, permute, apply_kq, apply_mcphase, apply_sequence, set_stream, set_option, device_ptr,
+ *    measure*, collapse, insert, permute, apply_kq, apply_mcphase, apply_sequence, apply_pauli_rotation(s) (never
+ *    queued themselves), set_stream, set_option, device_ptr,
  *    timer_*, event_*, last_kernel, and qsv_flush itself.  qsv_destroy drops what is pending.
  *  - A launch error during a flush is returned by the call that flushed; the rest of the queue is dropped.
  *  - Views (qsv_create_view, qsv_rebind_view) never defer, nor does a register once qsv_device_ptr has handed out its
@@ -178,6 +179,22 @@ int qsv_apply_kq(qsv_state *st, int k, const int *qubits, const double *m);
  * was applied, call qsv_apply_kq with the product matrix. */
 int qsv_apply_sequence(qsv_state *st, int k, const int *qubits, int n_gates, const int *arity, const int *legs,
                        const double *matrices, int *handled);
+/* psi <- exp(-i theta/2 P) psi, P = paulis[j] on qubits[j] ('I','X','Y','Z', either case), 0 <= k <= 64: the sign
+ * convention of RZ (exp(-i angle/2 Z)).  P|i> = i^{nY} (-1)^{popcount(i & zmask)} |i ^ xmask> and P^2 = 1, so the rotation
+ * is cos(theta/2) - i sin(theta/2) P: it mixes only the two amplitudes of each pair {i, i ^ xmask} (a diagonal phase for
+ * Z-only strings).  A string of any weight is one pass over the register at the traffic of a one-qubit gate, without a
+ * matrix.  The identity string, or k = 0, applies the global phase e^{-i theta/2}. */
+int qsv_apply_pauli_rotation(qsv_state *st, int k, const int *qubits, const char *paulis, double theta);
+/* psi <- R_{T-1} ... R_1 R_0 psi, R_t = exp(-i thetas[t]/2 P_t), term 0 applied first; layout of
+ * term_offsets / qubits / paulis as in qsv_expect_pauli_sum; passes (may be NULL) = kernel launches made.
+ * Consecutive rotations that are diagonal or flip the same qubits (equal X/Y positions) act inside the same pairs and
+ * share a pass of at most 8 rotations, applied in registers in the caller's order (csrc/qsv_pauli_rotation_plan.h): XX,
+ * YY and ZZ on one pair are one pass, T Z-strings are ceil(T / 8).  The list is never reordered.  The whole list is
+ * validated before the first launch; QSV_EINVAL leaves the register and the deferred queue as they were; QSV_ESTATE on a
+ * mode register; n_terms = 0 does nothing and launches nothing.  The launches go back to back on the register's stream
+ * with no host synchronisation. */
+int qsv_apply_pauli_rotations(qsv_state *st, int n_terms, const int *term_offsets, const int *qubits,
+                              const char *paulis, const double *thetas, uint64_t *passes);
 /* Qubit-axis permutation of the ket: permute_tensor_product (numpy_quantum.py:227-240); the qubit
  * at position j moves to position new_ordering[j]. */
 int qsv_permute(qsv_state *st, const int *new_ordering);

@@ -14,7 +14,7 @@ LIB_PATH = PKG_DIR / "libqsv.so"
 SOURCES = ["qsv_api.hip", "qsv_kernels.hip", "qsv_qudit.hip", "qsv_gemm.hip", "qsv_decomp.hip", "qsv_circuit.hip",
            "qsv_phase_space.hip", "qsv_sampling.hip", "qsv_canonical.hip"]
 HEADERS = [CSRC / "qsv_internal.h", CSRC / "qsv_linalg.h", CSRC / "qsv_plan.h", CSRC / "qsv_layout.h", CSRC / "qsv_pauli_plan.h",
-           REPO_ROOT / "include" / "qsv.h"]
+           CSRC / "qsv_pauli_rotation_plan.h", REPO_ROOT / "include" / "qsv.h"]
 ARCH = "gfx950"
 
 

@@ -962,6 +962,54 @@ int qsv_expect_pauli_sum(qsv_state *st, int n_terms, const int *term_offsets, co
     return QSV_OK;
 }
 
+int qsv_apply_pauli_rotations(qsv_state *st, int n_terms, const int *term_offsets, const int *qubits, const char *paulis,
+                              const double *thetas, uint64_t *passes) {
+    if (!valid(st)) return qsv_fail(QSV_EINVAL, "null pointer");
+    if (n_terms < 0) return qsv_fail(QSV_EINVAL, "negative number of Pauli terms");
+    if (n_terms > 0 && (!term_offsets || !thetas)) return qsv_fail(QSV_EINVAL, "null pointer");
+    if (st->kind != 0) return qsv_fail(QSV_ESTATE, "this call needs a qubit register");
+    // the whole list is checked and turned into masks before the queue is flushed or anything is launched
+    std::vector<qsv_pauli_plan::Term> terms(n_terms);
+    for (int t = 0; t < n_terms; ++t) {
+        const int first = term_offsets[t], k = term_offsets[t + 1] - first;
+        if (first < 0 || k < 0) return qsv_fail(QSV_EINVAL, "Pauli term offsets must start at or above 0 and never decrease");
+        if (k > 64) return qsv_fail(QSV_EINVAL, "bad Pauli string length");
+        if (k > 0 && (!qubits || !paulis)) return qsv_fail(QSV_EINVAL, "null pointer");
+        const int rc = check_qubits(st, k, k ? qubits + first : nullptr);
+        if (rc) return rc;
+        for (int j = 0; j < k; ++j) {
+            const uint64_t bit = 1ull << bit_of(st, qubits[first + j]);
+            switch (paulis[first + j]) {
+                case 'I': case 'i': break;
+                case 'X': case 'x': terms[t].xmask |= bit; break;
+                case 'Z': case 'z': terms[t].zmask |= bit; break;
+                case 'Y': case 'y': terms[t].xmask |= bit; terms[t].zmask |= bit; break;
+                default: return qsv_fail(QSV_EINVAL, "Pauli letters must be I, X, Y or Z");
+            }
+        }
+    }
+    if (passes) *passes = 0;
+    if (n_terms == 0) return QSV_OK;
+    QSV_FLUSH(st);
+    QSV_HIP(hipSetDevice(st->device));
+    std::vector<double> cs(n_terms), sn(n_terms);
+    for (int t = 0; t < n_terms; ++t) {
+        cs[t] = std::cos(0.5 * thetas[t]);
+        sn[t] = std::sin(0.5 * thetas[t]);
+    }
+    const std::vector<qsv_pauli_rotation_plan::Pass> plan = qsv_pauli_rotation_plan::plan(terms);
+    const int rc = qsvk_pauli_rotate_passes(st, plan, cs.data(), sn.data());
+    if (rc) return rc;
+    if (passes) *passes = plan.size();
+    return QSV_OK;
+}
+
+int qsv_apply_pauli_rotation(qsv_state *st, int k, const int *qubits, const char *paulis, double theta) {
+    if (k < 0 || k > 64) return qsv_fail(QSV_EINVAL, "bad Pauli string length");
+    const int offsets[2] = {0, k};
+    return qsv_apply_pauli_rotations(st, 1, offsets, qubits, paulis, &theta, nullptr);
+}
+
 int qsv_sample(qsv_state *st, int shots, const double *u, uint64_t *out) {
     if (!valid(st) || (shots > 0 && (!u || !out))) return qsv_fail(QSV_EINVAL, "null pointer");
     if (shots < 0 || shots > (1 << 24)) return qsv_fail(QSV_EINVAL, "shots must be in 0..2^24");

@@ -10,6 +10,7 @@
 #include "qsv.h"
 #include "qsv_layout.h"
 #include "qsv_pauli_plan.h"
+#include "qsv_pauli_rotation_plan.h"
 
 // One amplitude = complex128 = one 16-byte vector: exactly one dwordx4 per lane, 1 KiB per wave64 access.
 typedef double amp_t __attribute__((ext_vector_type(2)));
@@ -157,6 +158,9 @@ int qsvk_probabilities(qsv_state *st, const uint64_t *indices, int count, double
 int qsvk_expect_pauli(qsv_state *st, uint64_t xmask, uint64_t zmask, int n_y, double *re, double *im);
 // every pass of a qsv_expect_pauli_sum plan: values[index of the term in the caller's list] = <psi|P|psi>, one synchronisation
 int qsvk_expect_pauli_groups(qsv_state *st, const std::vector<qsv_pauli_plan::Pass> &passes, double *values);
+// every pass of a qsv_apply_pauli_rotations plan, in place and with no synchronisation; cs / sn = cos, sin(theta / 2) per term of the caller's list
+int qsvk_pauli_rotate_passes(qsv_state *st, const std::vector<qsv_pauli_rotation_plan::Pass> &passes, const double *cs,
+                             const double *sn);
 int qsvk_reduced_density(qsv_state *st, int k, const int *bits, double *rho_out);
 int qsvk_expect_density(qsv_state *ket, qsv_state *rho, double *re, double *im);
 int qsvk_sample(qsv_state *st, int shots, const double *u, uint64_t *out);

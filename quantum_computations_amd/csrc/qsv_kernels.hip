@@ -1010,6 +1010,86 @@ __global__ __launch_bounds__(QSV_BLOCK) void k_expect_pauli_group(const amp_t *_
     }
 }
 
+// One planned pass of qsv_apply_pauli_rotations (qsv_pauli_rotation_plan.h): up to T rotations exp(-i theta/2 P), each
+// diagonal or flipping the pass's xmask, applied in the caller's order to every pair {i, i ^ xmask}.
+struct PauliRotateArgs {
+    uint64_t items;      // pairs (amps / 2), or amps for a diagonal pass
+    uint64_t xmask;
+    int32_t pivot;       // highest set bit of xmask (unused by the diagonal form)
+    uint32_t diag;       // bit t: term t is diagonal (set beyond the pass's terms, which are padded with theta = 0)
+    uint32_t rot;        // bits 2t, 2t + 1: nY & 3 of term t
+    uint64_t zmask[qsv_pauli_rotation_plan::ROTATIONS_PER_PASS];
+    double cs[qsv_pauli_rotation_plan::ROTATIONS_PER_PASS];   // cos(theta / 2), computed on the host in double precision
+    double sn[qsv_pauli_rotation_plan::ROTATIONS_PER_PASS];   // sin(theta / 2)
+};
+
+// i^k v: a swap and signs of the real and imaginary part, never a multiplication (k is wave-uniform)
+__device__ __forceinline__ amp_t mul_i_pow(amp_t v, uint32_t k) {
+    amp_t r;
+    r.x = (k & 1u) ? v.y : v.x;
+    r.y = (k & 1u) ? v.x : v.y;
+    if (k == 1u || k == 2u) r.x = -r.x;
+    if (k >= 2u) r.y = -r.y;
+    return r;
+}
+
+// (c - i t) v
+__device__ __forceinline__ amp_t phase_amp(double c, double t, amp_t v) {
+    amp_t r;
+    r.x = fma(t, v.y, c * v.x);
+    r.y = fma(-t, v.x, c * v.y);
+    return r;
+}
+
+// The T terms of the pass on one work item, in the caller's order.  a = psi[i], b = psi[i ^ xmask] (unused when DIAG);
+// s(j) = (-1)^{popcount(j & zmask)} and s(i ^ xmask) = s(i) s(xmask).  What a term is (diagonal or not, its power of i,
+// whether its sign differs between the partners) is wave-uniform: scalar branches, no divergence.
+template <int T, bool DIAG>
+__device__ __forceinline__ void pauli_rotate_item(const PauliRotateArgs &g, uint64_t i, amp_t &a, amp_t &b) {
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        const uint64_t z = g.zmask[t];
+        const double c = g.cs[t], sn = g.sn[t];
+        const bool minus = __popcll(i & z) & 1;                   // s(i) = -1
+        if (DIAG || ((g.diag >> t) & 1u)) {
+            a = phase_amp(c, minus ? -sn : sn, a);
+            if constexpr (!DIAG) {
+                const bool differ = __popcll(g.xmask & z) & 1;
+                b = phase_amp(c, (minus != differ) ? -sn : sn, b);
+            }
+        } else if constexpr (!DIAG) {
+            const uint32_t n_y = (g.rot >> (2 * t)) & 3u, k = (n_y + 3u) & 3u;   // -i i^{nY} = i^k
+            const bool differ = n_y & 1u;                                       // s(i') = (-1)^{nY} s(i)
+            const double ta = (minus != differ) ? -sn : sn;   // sn s(i'), in front of b in a'
+            const double tb = minus ? -sn : sn;               // sn s(i),  in front of a in b'
+            const amp_t ra = mul_i_pow(a, k), rb = mul_i_pow(b, k);
+            a = amp_t{fma(ta, rb.x, c * a.x), fma(ta, rb.y, c * a.y)};
+            b = amp_t{fma(tb, ra.x, c * b.x), fma(tb, ra.y, c * b.y)};
+        }
+    }
+}
+
+// Work item w owns amplitude w (DIAG) or the pair {i, i ^ xmask} with i = insert_zero(w, pivot): it loads it, applies the
+// pass in registers and stores it -- in place, no barrier, no LDS.  One work item per thread, as in the gate kernels: a
+// pair item has its two 16-byte loads in flight together, and more items per thread were measured slower (DESIGN.md,
+// "Pauli rotations").  With the pivot at the highest flipped bit the i of a workgroup are consecutive (up to the one jump
+// over the pivot bit) and so are the partners, up to a permutation inside their range: for pivot >= 3 every wave access
+// covers whole 128-byte lines.  For a pivot on bits 0..2 the two halves of a line belong to the same thread or to a
+// neighbour; these passes use plain (cached) accesses so that the halves meet in L2 before the line is written back
+// (NT = false).  The loop only runs more than once beyond 2^32 work items (grid_for).
+template <int T, bool DIAG, bool NT>
+__global__ __launch_bounds__(QSV_BLOCK) void k_pauli_rotate_group(amp_t *__restrict__ psi, const PauliRotateArgs g) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * QSV_BLOCK;
+    for (uint64_t w = blockIdx.x * static_cast<uint64_t>(QSV_BLOCK) + threadIdx.x; w < g.items; w += stride) {
+        const uint64_t i = DIAG ? w : insert_zero(w, g.pivot);
+        amp_t a = ld<NT>(psi + i), b = amp_t{0.0, 0.0};
+        if constexpr (!DIAG) b = ld<NT>(psi + (i ^ g.xmask));
+        pauli_rotate_item<T, DIAG>(g, i, a, b);
+        st<NT>(psi + i, a);
+        if constexpr (!DIAG) st<NT>(psi + (i ^ g.xmask), b);
+    }
+}
+
 // Sampling, pass 1: chunk_sums[c] = sum of |amp|^2 over chunk c (SAMPLE_CHUNK consecutive amplitudes per workgroup).
 constexpr int SAMPLE_CHUNK = 4096;
 
@@ -3483,6 +3563,58 @@ int qsvk_expect_pauli_groups(qsv_state *st, const std::vector<qsv_pauli_plan::Pa
             for (int b = 0; b < s.grid; ++b) sum += host[s.offset + static_cast<size_t>(b) * s.width + t];
             values[p.index[t]] = qsv_pauli_plan::pair_scale(p.pivot, p.n_y[t]) * sum;
         }
+    }
+    return QSV_OK;
+}
+
+// Every pass of a qsv_apply_pauli_rotations plan, back to back on the register's stream with no host synchronisation.
+// cs / sn: cos(theta/2) and sin(theta/2) of every term, indexed as the caller's list.
+int qsvk_pauli_rotate_passes(qsv_state *st, const std::vector<qsv_pauli_rotation_plan::Pass> &passes, const double *cs,
+                             const double *sn) {
+    constexpr int CAP = qsv_pauli_rotation_plan::ROTATIONS_PER_PASS;
+    for (const qsv_pauli_rotation_plan::Pass &p : passes) {
+        const int count = static_cast<int>(p.index.size());
+        if (count < 1 || count > CAP || p.pivot >= st->n || (p.pivot < 0) != (p.xmask == 0) || p.xmask >= st->amps)
+            return qsv_fail(QSV_EINVAL, "bad Pauli rotation pass");
+        PauliRotateArgs g;
+        std::memset(&g, 0, sizeof(g));
+        g.items = p.pivot < 0 ? st->amps : st->amps / 2;
+        g.xmask = p.xmask;
+        g.pivot = p.pivot < 0 ? 0 : p.pivot;
+        for (int t = 0; t < CAP; ++t) {
+            const bool used = t < count;
+            g.zmask[t] = used ? p.zmask[t] : 0;
+            g.cs[t] = used ? cs[p.index[t]] : 1.0;
+            g.sn[t] = used ? sn[p.index[t]] : 0.0;
+            if (!used || p.term_xmask[t] == 0) g.diag |= 1u << t;
+            else g.rot |= static_cast<uint32_t>(p.n_y[t] & 3) << (2 * t);
+        }
+        const int width = count <= 1 ? 1 : count <= 2 ? 2 : count <= 4 ? 4 : 8;
+        // a pivot inside a 128-byte line: both halves of a line are written by one launch, let them meet in L2
+        const bool nt = st->nontemporal && (p.pivot < 0 || p.pivot >= 3);
+        const dim3 gd(grid_for(g.items, QSV_BLOCK, st->grid_cap)), bd(QSV_BLOCK);
+#define QSV_ROTATE_LAUNCH(W, D)                                                                                    \
+    do {                                                                                                           \
+        if (nt) hipLaunchKernelGGL((k_pauli_rotate_group<W, D, true>), gd, bd, 0, st->stream, st->data, g);        \
+        else hipLaunchKernelGGL((k_pauli_rotate_group<W, D, false>), gd, bd, 0, st->stream, st->data, g);          \
+    } while (0)
+#define QSV_ROTATE_WIDTH(W)                     \
+    do {                                        \
+        if (p.pivot < 0) QSV_ROTATE_LAUNCH(W, true); \
+        else QSV_ROTATE_LAUNCH(W, false);       \
+    } while (0)
+        switch (width) {
+            case 1: QSV_ROTATE_WIDTH(1); break;
+            case 2: QSV_ROTATE_WIDTH(2); break;
+            case 4: QSV_ROTATE_WIDTH(4); break;
+            default: QSV_ROTATE_WIDTH(8); break;
+        }
+#undef QSV_ROTATE_WIDTH
+#undef QSV_ROTATE_LAUNCH
+        snprintf(st->last_kernel, sizeof(st->last_kernel), "k_pauli_rotate_group<%d, %s, %s>", width, p.pivot < 0 ? "true" : "false",
+                 nt ? "true" : "false");
+        const int rc = check_launch();
+        if (rc) return rc;
     }
     return QSV_OK;
 }

@@ -333,6 +333,45 @@ class DeviceState:
         value = complex(re.value, im.value)
         return (value, values) if return_terms else value
 
+    def apply_pauli_rotation(self, theta: float, paulis: str, qubits) -> "DeviceState":
+        """In-place ``exp(-i theta/2 P) ket`` for the Pauli string ``P`` = ``paulis[j]`` on ``qubits[j]`` (the sign
+        convention of ``RZ``): one pass over the register whatever the weight of the string, no matrix."""
+        return self.apply_pauli_rotations([(theta, paulis, qubits)])
+
+    def apply_pauli_rotations(self, rotations) -> "DeviceState":
+        """An ordered list ``[(theta, letters, qubits), ...]`` of Pauli rotations, the first applied first.  Consecutive
+        rotations that are diagonal or flip the same qubits share a pass of at most eight (``XX``, ``YY``, ``ZZ`` on a
+        pair: one pass); the order is never changed.  ``ShardedState`` has no such method: out of scope there."""
+        self._pauli_rotations(rotations)
+        return self
+
+    def _pauli_rotations(self, rotations, qubit_offset: int = 0, conjugate: bool = False) -> int:
+        """Flatten and launch; returns the number of passes.  ``conjugate``: rotate by ``conj(P)`` = ``(-1)^nY P`` in
+        the opposite direction, on qubits moved by ``qubit_offset`` (the column side of a density matrix)."""
+        offsets, qubits, letters, thetas = [0], [], [], []
+        for theta, paulis, qs in rotations:
+            paulis, qs = str(paulis), [int(q) + qubit_offset for q in qs]
+            if len(paulis) != len(qs):
+                raise ValueError("one Pauli letter per qubit")
+            theta = float(theta)
+            if conjugate:
+                theta = -theta if paulis.upper().count("Y") % 2 == 0 else theta
+            qubits += qs
+            letters.append(paulis)
+            offsets.append(len(qubits))
+            thetas.append(theta)
+        passes = C.c_uint64()
+        tbuf = np.ascontiguousarray(thetas, dtype=np.float64)
+        _lib.call("qsv_apply_pauli_rotations", self._h, len(thetas), _ints(offsets), _ints(qubits), "".join(letters).encode(),
+                  tbuf.ctypes.data_as(C.POINTER(C.c_double)), C.byref(passes))
+        return passes.value
+
+    def evolve(self, terms, t: float, steps: int = 1, order: int = 1) -> "DeviceState":
+        """Trotterised ``exp(-i t H) ket`` for ``H = sum_t c_t P_t``, ``terms`` as for ``expect_pauli_sum`` (real
+        coefficients): ``npq.trotter_rotations`` turned into shared passes by ``apply_pauli_rotations``."""
+        from .dv_simulator import numpy_quantum as npq
+        return self.apply_pauli_rotations(npq.trotter_rotations(npq.PauliSum(self.num_qubits, terms), t, steps, order))
+
     def sample(self, shots: int, rng=None) -> np.ndarray:
         """``shots`` computational-basis outcomes drawn from |amplitude|^2 (inverse-CDF on the device; the uniforms
         come from ``rng``, a ``numpy.random.Generator``, default the global ``np.random`` state).  No collapse."""
@@ -451,6 +490,17 @@ class DensityState(DeviceState):
 
     def apply_sequence(self, indices, sources, matrix) -> "DensityState":
         return self.apply_matrix(matrix, indices)       # U rho U^dagger: both sides, as the dense block
+
+    def apply_pauli_rotations(self, rotations) -> "DensityState":
+        """``U rho U^dagger`` for the ordered rotation list: the list on the row qubits, then the same letters on the
+        column qubits ``n + q`` with angle ``-(-1)^nY theta`` (``conj(P) = (-1)^nY P``)."""
+        n = self.num_qubits
+        rotations = [(theta, str(paulis), [int(q) for q in qs]) for theta, paulis, qs in rotations]
+        if any(not 0 <= q < n for _, _, qs in rotations for q in qs):
+            raise ValueError(f"qubit index out of range for a {n}-qubit register")
+        self._pauli_rotations(rotations)
+        self._pauli_rotations(rotations, qubit_offset=n, conjugate=True)
+        return self
 
     def purity(self) -> float:
         """``tr(rho rho)`` for a hermitian ``rho`` (``npq.purity``): the squared norm of the flattened register."""

@@ -194,6 +194,62 @@ class RZ(SingleQubitGate):
         return super().__repr__() + f"({round(self.angle, REPR_DIGITS)})"
 
 
+class PauliRotation(Gate):
+    """``exp(-i angle/2 P)`` for the Pauli string ``P`` = ``letters[j]`` on qubit ``indices[j]`` (I / X / Y / Z), the sign
+    convention of ``RZ``.  On a ``DeviceState`` / ``DensityState`` (and on host arrays, which borrow one) it is one pass
+    over the register whatever its weight (``apply_pauli_rotation``).  ``matrix`` is the dense 2^k x 2^k operator for
+    k <= 6, so that fusion and registers without that method (``distributed.ShardedState``: out of scope) keep working
+    through the matrix path, and ``None`` above: no dense route exists there."""
+
+    MAX_DENSE = 6                    # qsv_apply_kq takes matrices on at most six qubits (include/qsv.h)
+    result_dtype = np.complex128     # what the gate contributes to NumPy's promotion when it has no matrix
+
+    def __init__(self, indices: list[int], letters: str, angle: float):
+        indices, letters = list(indices), str(letters)
+        if len(letters) != len(indices):
+            raise ValueError("one Pauli letter per qubit")
+        if any(not npq.is_pauli(letter) for letter in letters):
+            raise npq.PauliError("Pauli letters must be I, X, Y or Z")
+        k = len(indices)
+        matrix = None
+        if 1 <= k <= self.MAX_DENSE:
+            string = npq.PauliSum(k, [(1.0, letters, range(k))]).matrix()
+            matrix = np.cos(angle / 2) * np.eye(1 << k) - 1j * np.sin(angle / 2) * string
+        super().__init__(indices, matrix)
+        self.letters = letters
+        self.angle = angle
+
+    def __repr__(self):
+        return super().__repr__() + f"[{self.letters}]({round(self.angle, REPR_DIGITS)})"
+
+    def apply(self, state):
+        rotation = [(self.angle, self.letters, self.indices)]
+        if is_device_register(state):
+            if hasattr(state, "apply_pauli_rotation"):
+                return state.apply_pauli_rotation(self.angle, self.letters, self.indices)
+            if self.matrix is None:
+                raise ValueError(f"{type(state).__name__} has no apply_pauli_rotation and {self} has no dense matrix.")
+            return super().apply(state)
+        state = np.asarray(state)
+        if state.ndim not in (1, 2):
+            raise ValueError("State has wrong dimensions.")
+        flat = np.ascontiguousarray(state).reshape(-1)
+        dev = _borrow_register(flat)
+        size = DeviceState.num_qubits.fget(dev)
+        try:
+            if state.ndim == 2 and any(not 0 <= q < size // 2 for q in self.indices):
+                raise ValueError(f"qubit index out of range for a {size // 2}-qubit register")
+            dev._pauli_rotations(rotation)
+            if state.ndim == 2:      # U rho U^dagger: conj(U) on the column qubits, as DensityState does
+                dev._pauli_rotations(rotation, qubit_offset=size // 2, conjugate=True)
+            out = dev.to_numpy().reshape(state.shape)
+        except BaseException:
+            dev.close()
+            raise
+        _return_register(dev, size)
+        return out
+
+
 def _fixed_2q(name: str, matrix_of, doc: str, **extra):
     def __init__(self, first, second):
         TwoQubitGate.__init__(self, first, second, matrix_of())

@@ -290,6 +290,35 @@ def expect_pauli_sum(hamiltonian: PauliSum, state) -> complex:
     return state.expect_pauli_sum(hamiltonian.terms)
 
 
+def trotter_rotations(hamiltonian: PauliSum, t: float, steps: int = 1, order: int = 1) -> list:
+    """The Pauli rotations ``[(theta, letters, qubits), ...]`` of a Trotterised ``exp(-i t H)``, first applied first:
+    ``exp(-i c t / steps P) = exp(-i theta/2 P)`` with ``theta = 2 c t / steps``.  Order 1: the terms in ``H.terms``
+    order, ``steps`` times.  Order 2: per step a forward sweep with half angles, then the reverse sweep with half
+    angles.  What ``DeviceState.apply_pauli_rotations`` takes."""
+    steps = int(steps)
+    if steps < 1:
+        raise ValueError("steps must be at least 1")
+    if order not in (1, 2):
+        raise ValueError("Trotter order must be 1 or 2")
+    if any(c.imag != 0.0 for c, _, _ in hamiltonian.terms):
+        raise ValueError("time evolution needs real coefficients (a hermitian Pauli sum)")
+    sweep = [(2.0 * c.real * t / steps / order, letters, qubits) for c, letters, qubits in hamiltonian.terms]
+    return (sweep if order == 1 else sweep + sweep[::-1]) * steps
+
+
+def evolve(hamiltonian: PauliSum, state, t: float, steps: int = 1, order: int = 1):
+    """Trotterised ``exp(-i t H) state`` on the device (``DeviceState.evolve``).  A register is evolved in place and
+    returned; a host ket is uploaded first and the evolved ket is downloaded, as ``expect_pauli_sum`` lifts host arrays."""
+    from ..device import DeviceState
+    host = not isinstance(state, DeviceState)
+    if host:
+        state = DeviceState.from_numpy(np.asarray(state))
+    if state.num_qubits != hamiltonian.n_qubits:
+        raise TypeError("incompatible operator and state vector")
+    state.apply_pauli_rotations(trotter_rotations(hamiltonian, t, steps, order))
+    return state.to_numpy() if host else state
+
+
 # ---- sizes ----------------------------------------------------------------------------------------------------------
 def is_power_of_two(n: int) -> bool:
     return n > 0 and n & (n - 1) == 0

@@ -201,7 +201,7 @@ def _dtype_witness(gate, n_qubits: int) -> np.ndarray:
     if isinstance(gate, M):
         return np.empty(0, dtype=np.complex128)          # RZ(phi) RY(theta) is complex (gates.py:169)
     if gate.matrix is None:
-        return np.empty(0, dtype=np.float64)
+        return np.empty(0, dtype=getattr(gate, "result_dtype", np.float64))   # PauliRotation on more than six qubits is complex
     if isinstance(gate, Insert) or len(gate.indices) == n_qubits:
         return np.empty(0, dtype=gate.matrix.dtype)
     # expand_gate pads with the float64 identity (numpy_quantum.py:245)

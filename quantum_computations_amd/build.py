@@ -16,6 +16,21 @@ SOURCES = ["qsv_api.hip", "qsv_kernels.hip", "qsv_qudit.hip", "qsv_gemm.hip", "q
 HEADERS = [CSRC / "qsv_internal.h", CSRC / "qsv_linalg.h", CSRC / "qsv_plan.h", CSRC / "qsv_layout.h", CSRC / "qsv_pauli_plan.h",
            CSRC / "qsv_pauli_rotation_plan.h", REPO_ROOT / "include" / "qsv.h"]
 ARCH = "gfx950"
+# qsv_kernels.hip: leave regions whose branches are all wave-uniform as they are.  The structurizer otherwise rewrites
+# k_pass_tile's gate switch into a chain of guarded blocks that keeps a second copy of the 16 amplitudes of a thread (64
+# more VGPRs, 32 v_mov_b64 per gate).  The option changes control flow only, never arithmetic.
+EXTRA_FLAGS = {"qsv_kernels.hip": ["-mllvm", "-structurizecfg-skip-uniform-regions"]}
+
+
+def check_extra_flags() -> None:
+    """The options above are LLVM developer options: fail with a plain message where the compiler does not know one,
+    instead of in the middle of a long compile (or, worse, building the slower kernel by leaving it out)."""
+    for name, extra in EXTRA_FLAGS.items():
+        probe = subprocess.run([hipcc(), f"--offload-arch={ARCH}", *extra, "--cuda-device-only", "-x", "hip", "-c", "-",
+                                "-o", os.devnull], input="__global__ void k() {}\n", capture_output=True, text=True)
+        if probe.returncode != 0:
+            raise RuntimeError(f"{hipcc()} does not accept {' '.join(extra)} (needed for {name}, see DESIGN.md section 10):\n"
+                               + probe.stderr[-2000:])
 
 
 def hipcc() -> str:
@@ -34,6 +49,7 @@ def _stale(target: Path, deps: list[Path]) -> bool:
 
 def build_lib(force: bool = False, verbose: bool = False) -> Path:
     """Compile every HIP source for gfx950 and link libqsv.so next to the package."""
+    check_extra_flags()
     objs = []
     build_dir = PKG_DIR / "build"
     build_dir.mkdir(exist_ok=True)
@@ -43,7 +59,7 @@ def build_lib(force: bool = False, verbose: bool = False) -> Path:
         src = CSRC / name
         obj = build_dir / (name + ".o")
         if force or _stale(obj, [src] + HEADERS):
-            cmd = [hipcc(), *flags, "-c", str(src), "-o", str(obj)]
+            cmd = [hipcc(), *flags, *EXTRA_FLAGS.get(name, []), "-c", str(src), "-o", str(obj)]
             if verbose:
                 print(" ".join(cmd), flush=True)
             subprocess.run(cmd, check=True)

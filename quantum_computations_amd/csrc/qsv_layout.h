@@ -79,6 +79,7 @@ enum {
     PASS_PAIR = 5,                                                          // exchange of (a, b) = (1, 0) and (0, 1)
     PASS_DIAG_T = 6, PASS_DIAG_R1 = 7, PASS_DIAG_R2 = 8, PASS_DIAG_M = 9    // diagonal, by where its selector bits sit
 };
+enum { PASS_CTL_NONE = 0, PASS_CTL_REG = 1, PASS_CTL_THREAD = 2 };   // where a gate's controls inside the tile sit
 struct PassGate {
     int32_t form;        // PASS_*
     int32_t code;        // the body of the form: register bit P of kernel bit 0 (D2*, DIAG_R1, DIAG_M), or 4 P0 + P1 for
@@ -87,9 +88,14 @@ struct PassGate {
     uint32_t tc;         // controls on thread bits, as a mask of tile indices
     int32_t tz0, tz1;    // DIAG_T: tile indices of the thread bits s0, s1 that select d[(s0 << 1) | s1]; DIAG_M: tz0 = the
                          // thread bit s of d[(register bit << 1) | s]
-    uint64_t omask;      // register bits outside the tile that must be 1 (the same for every amplitude of a tile)
+    int32_t ctl;         // PASS_CTL_*: no control inside the tile, on register bits only (rc), or on thread bits (tc, and
+                         // maybe rc); the kernel has one body per class
+    int32_t pad0;
+    uint64_t omask;      // register bits outside the tile that must be 1 (the same for every amplitude of a tile); the
+                         // kernel reads PassRecords::omask, the same values packed, and not this field
     double m[32];        // dense: D x D kernel-order matrix, (re, im) interleaved; diagonal: d[0..3] as the form reads them
 };
+static_assert(sizeof(PassGate) == 40 + 32 * sizeof(double), "no padding but pad0");
 struct PassGroup {
     int32_t first, count;   // gates [first, first + count) of the pass
     int32_t q[4];           // the group's register bits as tile indices, ascending
@@ -530,6 +536,8 @@ struct PassRecords {
     int tile_bits[qsv_plan::TILE_BITS] = {};     // address bit of tile index 0..11
     std::vector<PassGate> rec;
     std::vector<PassGroup> grp;
+    std::vector<uint64_t> omask;                 // rec[i].omask, packed: the kernel reads them before any record
+    bool every_tile = false;                     // some gate has no control outside the tile: no tile is skipped
 };
 inline PassRecords pass_records(const Op *const *ops, int count, uint64_t tile_high, uint64_t amps) {
     PassRecords out;
@@ -553,6 +561,8 @@ inline PassRecords pass_records(const Op *const *ops, int count, uint64_t tile_h
         const qsv_plan::ControlMasks cm = qsv_plan::control_masks(ctrl, tile_high);
         cmask[i] = cm.inside;
         pg.omask = cm.outside;
+        out.omask.push_back(pg.omask);
+        out.every_tile = out.every_tile || pg.omask == 0;
         for (int j = 0; j < op.k; ++j)
             if (local_of[op.bits[j]] < 0) return out.status = PassRecords::TARGET_OUTSIDE_TILE, out;
         if (op.kind == OP_DIAG || op.kind == OP_PHASE) {
@@ -613,6 +623,7 @@ inline PassRecords pass_records(const Op *const *ops, int count, uint64_t tile_h
                     if (reg_of[t] >= 0) pg.rc |= 1u << reg_of[t];
                     else pg.tc |= 1u << t;
                 }
+            pg.ctl = pg.tc ? PASS_CTL_THREAD : pg.rc ? PASS_CTL_REG : PASS_CTL_NONE;
             const int l0 = leg[i][0], l1 = leg[i][1];
             if (pg.form == PASS_DIAG_T) {
                 const int r0 = l0 >= 0 ? reg_of[l0] : -1, r1 = l1 >= 0 ? reg_of[l1] : -1;

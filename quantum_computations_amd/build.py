@@ -11,26 +11,32 @@ PKG_DIR = Path(__file__).resolve().parent
 REPO_ROOT = PKG_DIR.parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = PKG_DIR / "libqsv.so"
-SOURCES = ["qsv_api.hip", "qsv_kernels.hip", "qsv_qudit.hip", "qsv_gemm.hip", "qsv_decomp.hip", "qsv_circuit.hip",
-           "qsv_phase_space.hip", "qsv_sampling.hip", "qsv_canonical.hip"]
-HEADERS = [CSRC / "qsv_internal.h", CSRC / "qsv_linalg.h", CSRC / "qsv_plan.h", CSRC / "qsv_layout.h", CSRC / "qsv_pauli_plan.h",
-           CSRC / "qsv_pauli_rotation_plan.h", REPO_ROOT / "include" / "qsv.h"]
+SOURCES = ["qsv_api.hip", "qsv_kernels.hip", "qsv_readout.hip", "qsv_pauli.hip", "qsv_qudit.hip", "qsv_gemm.hip", "qsv_decomp.hip",
+           "qsv_circuit.hip", "qsv_phase_space.hip", "qsv_sampling.hip", "qsv_canonical.hip"]
+HEADERS = [CSRC / "qsv_internal.h", CSRC / "qsv_device.h", CSRC / "qsv_linalg.h", CSRC / "qsv_plan.h", CSRC / "qsv_layout.h",
+           CSRC / "qsv_readout_layout.h", CSRC / "qsv_pauli_plan.h", CSRC / "qsv_pauli_rotation_plan.h", REPO_ROOT / "include" / "qsv.h"]
 ARCH = "gfx950"
-# qsv_kernels.hip: leave regions whose branches are all wave-uniform as they are.  The structurizer otherwise rewrites
-# k_pass_tile's gate switch into a chain of guarded blocks that keeps a second copy of the 16 amplitudes of a thread (64
+# Leave regions whose branches are all wave-uniform as they are.  The structurizer otherwise rewrites k_pass_tile's gate
+# switch (qsv_kernels.hip) into a chain of guarded blocks that keeps a second copy of the 16 amplitudes of a thread (64
 # more VGPRs, 32 v_mov_b64 per gate).  The option changes control flow only, never arithmetic.
-EXTRA_FLAGS = {"qsv_kernels.hip": ["-mllvm", "-structurizecfg-skip-uniform-regions"]}
+# qsv_readout.hip and qsv_pauli.hip take the option too.  Compiled with and without it (tools/device_code_diff.py), these
+# of their kernels come out differently --
+#   qsv_readout.hip: k_chunk_sums, k_sample_in_chunk, k_permute_s<1 / 2 / 4>, k_rdm<1 / 2 / 4>, k_rdm_tile<1 / 2 / 4>,
+#                    k_rdm_small (12 of 38);
+#   qsv_pauli.hip:   k_pauli_rotate_group<1 / 2 / 4 / 8, false, *> (8 of 25) --
+# every measurement on record of them was taken with it, and none without.
+_SKIP_UNIFORM = ["-mllvm", "-structurizecfg-skip-uniform-regions"]
+EXTRA_FLAGS = {"qsv_kernels.hip": _SKIP_UNIFORM, "qsv_readout.hip": _SKIP_UNIFORM, "qsv_pauli.hip": _SKIP_UNIFORM}
 
 
 def check_extra_flags() -> None:
     """The options above are LLVM developer options: fail with a plain message where the compiler does not know one,
     instead of in the middle of a long compile (or, worse, building the slower kernel by leaving it out)."""
-    for name, extra in EXTRA_FLAGS.items():
-        probe = subprocess.run([hipcc(), f"--offload-arch={ARCH}", *extra, "--cuda-device-only", "-x", "hip", "-c", "-",
-                                "-o", os.devnull], input="__global__ void k() {}\n", capture_output=True, text=True)
-        if probe.returncode != 0:
-            raise RuntimeError(f"{hipcc()} does not accept {' '.join(extra)} (needed for {name}, see DESIGN.md section 10):\n"
-                               + probe.stderr[-2000:])
+    probe = subprocess.run([hipcc(), f"--offload-arch={ARCH}", *_SKIP_UNIFORM, "--cuda-device-only", "-x", "hip", "-c", "-",
+                            "-o", os.devnull], input="__global__ void k() {}\n", capture_output=True, text=True)
+    if probe.returncode != 0:
+        raise RuntimeError(f"{hipcc()} does not accept {' '.join(_SKIP_UNIFORM)} (needed for {', '.join(EXTRA_FLAGS)}, see "
+                           "DESIGN.md section 10):\n" + probe.stderr[-2000:])
 
 
 def hipcc() -> str:

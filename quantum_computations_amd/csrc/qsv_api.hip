@@ -1,5 +1,6 @@
 // C ABI of libqsv.so (include/qsv.h): argument validation, qubit -> bit mapping, kernel selection.
-// The device work lives in qsv_kernels.hip (qubits) and qsv_qudit.hip (d-level modes).
+// The device work lives in qsv_kernels.hip (qubit gates), qsv_readout.hip (measurement, reshaping, reductions),
+// qsv_pauli.hip (Pauli sums and rotations) and qsv_qudit.hip (d-level modes).
 
 #include "qsv_internal.h"
 #include "qsv_plan.h"

@@ -11,6 +11,7 @@
 #include "qsv_layout.h"
 #include "qsv_pauli_plan.h"
 #include "qsv_pauli_rotation_plan.h"
+#include "qsv_readout_layout.h"
 
 // One amplitude = complex128 = one 16-byte vector: exactly one dwordx4 per lane, 1 KiB per wave64 access.
 typedef double amp_t __attribute__((ext_vector_type(2)));
@@ -101,7 +102,8 @@ struct qsv_state {
     int complex_product = 0;          // complex 5- / 6-qubit blocks: 0 = three real multiplications per entry (3M) on the
                                       // matrix cores, 3 = on the vector kernels too, 4 = four everywhere (measurement variants)
     int readout_variant = 0;          // measurement / insertion / permutation / table diagonals: 0 = streaming forms,
-                                      // 1 = round-1 grid-stride forms
+                                      // 1 = round-1 grid-stride forms; reduced density matrices: 0 = k_rdm_tile,
+                                      // 2 = round 2's k_rdm (1 and 2 are measurement variants)
     int plane_kernel = 1;             // block-diagonal two-mode operators on the last two modes: 1 = workgroup-per-plane
                                       // form (k_mode2_plane), 0 = plane-per-thread form (k_mode2_blocks<64>)
     char last_kernel[96] = "";        // name of the most recent gate kernel launched (qsv_last_kernel)
@@ -135,7 +137,8 @@ int qsv_fail(int code, const std::string &msg);
             return qsv_fail(QSV_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e));               \
     } while (0)
 
-// launchers (qsv_kernels.hip / qsv_qudit.hip); all enqueue on st->stream
+// launchers (qsv_kernels.hip: gates and state plumbing, qsv_readout.hip, qsv_pauli.hip, qsv_qudit.hip); all enqueue on
+// st->stream
 int qsvk_copy(amp_t *dst, const amp_t *src, uint64_t amps, hipStream_t stream);   // nontemporal copy kernel
 int qsvk_dense(qsv_state *st, int k, const int *bits, int nctrl, const int *cbits, const double *m_user);
 int qsvk_pair_exchange(qsv_state *st, int bit_a, int bit_b);  // SWAP on two high bits (moves 1/2 of the state)

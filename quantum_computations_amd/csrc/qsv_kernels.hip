@@ -1,4 +1,5 @@
-// Qubit-register kernels of libqsv.so, written for gfx950 (MI355X, wave64) only.
+// Gate kernels of the qubit register of libqsv.so, written for gfx950 (MI355X, wave64) only, with the state plumbing
+// (staging ring, spare buffer, copy).  Measurement, reshaping and reductions are qsv_readout.hip, Pauli strings qsv_pauli.hip.
 //
 // Every gate is one streaming pass over the complex128 register in HBM: the path is bandwidth-bound
 // (0.44-0.94 flop/B), so the kernels are organised around memory access, not arithmetic:
@@ -14,6 +15,7 @@
 // (simulators/dv_simulator/gates.py:44-54, numpy_quantum.py:243-247).
 
 #include "qsv_internal.h"
+#include "qsv_device.h"
 #include "qsv_layout.h"
 #include "qsv_plan.h"
 
@@ -28,84 +30,6 @@ using namespace qsv_layout;   // the argument and record types of the kernels, a
 static_assert(LANE_BITS == QSV_LANE_BITS && MAX_K == QSV_MAX_K && BLOCK == QSV_BLOCK, "qsv_layout.h and qsv_internal.h agree");
 
 namespace {
-
-struct cplx {
-    double re, im;
-};
-
-__device__ __forceinline__ amp_t cmul(cplx m, amp_t a) {
-    amp_t r;
-    r.x = m.re * a.x - m.im * a.y;
-    r.y = m.re * a.y + m.im * a.x;
-    return r;
-}
-
-// d * a for the diagonal kernels (k_diag, and k_pass_tile's diagonal gates), with the two fused multiply-adds spelled
-// out: left to the compiler, `re * a.y + im * a.x` is contracted one way or the other depending on the surrounding code,
-// and a deferred gate must round exactly as its per-gate launch does.  This is the form k_diag was compiled to.
-__device__ __forceinline__ amp_t cmul_diag(cplx d, amp_t a) {
-    amp_t r;
-    r.x = fma(a.x, d.re, -(a.y * d.im));
-    r.y = fma(a.x, d.im, a.y * d.re);
-    return r;
-}
-
-// acc + m * a, in two halves: the products with m.im first (inner), those with m.re on top (outer).  k_pass_tile issues
-// the halves of its last column apart; everything else calls cfma.
-__device__ __forceinline__ amp_t cfma_inner(cplx m, amp_t a, amp_t acc) {
-    amp_t r;
-    r.x = fma(-m.im, a.y, acc.x);
-    r.y = fma(m.im, a.x, acc.y);
-    return r;
-}
-__device__ __forceinline__ amp_t cfma_outer(cplx m, amp_t a, amp_t inner) {
-    amp_t r;
-    r.x = fma(m.re, a.x, inner.x);
-    r.y = fma(m.re, a.y, inner.y);
-    return r;
-}
-__device__ __forceinline__ amp_t cfma(cplx m, amp_t a, amp_t acc) {
-    return cfma_outer(m, a, cfma_inner(m, a, acc));
-}
-
-template <bool NT>
-__device__ __forceinline__ amp_t ld(const amp_t *p) {
-    if constexpr (NT)
-        return __builtin_nontemporal_load(p);
-    else
-        return *p;
-}
-
-template <bool NT>
-__device__ __forceinline__ void st(amp_t *p, amp_t v) {
-    if constexpr (NT)
-        __builtin_nontemporal_store(v, p);
-    else
-        *p = v;
-}
-
-__device__ __forceinline__ amp_t shfl_xor_amp(amp_t v, int lane_mask) {
-    amp_t r;
-    r.x = __shfl_xor(v.x, lane_mask, 64);
-    r.y = __shfl_xor(v.y, lane_mask, 64);
-    return r;
-}
-
-__device__ __forceinline__ uint64_t insert_zero(uint64_t w, int p) {
-    const uint64_t low = w & ((1ull << p) - 1ull);
-    return ((w >> p) << (p + 1)) | low;
-}
-
-// The positions are 32-bit words on purpose.  The argument struct lives in the kernarg segment; a run-time index into
-// a BYTE array there makes the compiler fetch the byte with a vector load (gfx950 has no sub-dword scalar loads)
-// followed by s_waitcnt vmcnt(0) in front of every amplitude load -- which also drains every amplitude load already in
-// flight (k_rdm ran at 1.3-2.3 TB/s that way; rocprof: 60-70 % of the wave cycles parked).  A dword array is indexed
-// with s_load_dword.
-template <class Args>
-__device__ __forceinline__ uint64_t deposit(uint64_t w, const Args &g) {
-    for (int j = 0; j < g.nins; ++j) w = insert_zero(w, static_cast<int>(g.pos[j]));
-    return w | g.or_mask;
-}
 
 // ----------------------------------------------------------------------------------------------------
 // Dense 1- and 2-qubit gates (optionally controlled).
@@ -665,7 +589,6 @@ __global__ __launch_bounds__(QSV_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)
 // The matrix sits in LDS column-major (real and imaginary planes), a complex product is four real MFMAs, a real
 // matrix needs two.  Loads and stores are four 256-byte runs per wave-instruction: whole 128-byte lines.
 // ----------------------------------------------------------------------------------------------------
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 struct Mfma6Args {
     uint64_t W;          // groups = amps / 64
@@ -807,385 +730,6 @@ __global__ __launch_bounds__(QSV_BLOCK) __attribute__((amdgpu_waves_per_eu(2, (K
     }
 }
 
-// ----------------------------------------------------------------------------------------------------
-// Reductions, measurement, insertion, permutation, fills.
-// ----------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// Block-wide sum of two doubles; result valid in thread 0.
-__device__ __forceinline__ void block_sum2(double &x, double &y) {
-    __shared__ double sx[QSV_BLOCK / 64], sy[QSV_BLOCK / 64];
-    x = wave_sum(x);
-    y = wave_sum(y);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        sx[wave] = x;
-        sy[wave] = y;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        x = 0.0;
-        y = 0.0;
-        for (int i = 0; i < QSV_BLOCK / 64; ++i) {
-            x += sx[i];
-            y += sy[i];
-        }
-    }
-}
-
-// partials[2*block + s] = sum over this block's pairs of |eig_s[0] a0 + eig_s[1] a1|^2
-__global__ __launch_bounds__(QSV_BLOCK) void k_measure_probs(const amp_t *__restrict__ a, uint64_t pairs, int bit,
-                                                            cplx e00, cplx e01, cplx e10, cplx e11,
-                                                            double *__restrict__ partials) {
-    double p0 = 0.0, p1 = 0.0;
-    const uint64_t s = 1ull << bit;
-    for (uint64_t w = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x; w < pairs;
-         w += static_cast<uint64_t>(gridDim.x) * blockDim.x) {
-        const uint64_t i0 = insert_zero(w, bit);
-        const amp_t a0 = a[i0], a1 = a[i0 + s];
-        const amp_t r0 = cfma(e01, a1, cmul(e00, a0));
-        const amp_t r1 = cfma(e11, a1, cmul(e10, a0));
-        p0 += r0.x * r0.x + r0.y * r0.y;
-        p1 += r1.x * r1.x + r1.y * r1.y;
-    }
-    block_sum2(p0, p1);
-    if (threadIdx.x == 0) {
-        partials[2 * blockIdx.x] = p0;
-        partials[2 * blockIdx.x + 1] = p1;
-    }
-}
-
-// out[w] = scale * (e0 a[i0] + e1 a[i1]): the (n-1)-qubit post-measurement ket.
-__global__ __launch_bounds__(QSV_BLOCK) void k_collapse(const amp_t *__restrict__ a, amp_t *__restrict__ out,
-                                                       uint64_t pairs, int bit, cplx e0, cplx e1, double scale) {
-    const uint64_t s = 1ull << bit;
-    for (uint64_t w = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x; w < pairs;
-         w += static_cast<uint64_t>(gridDim.x) * blockDim.x) {
-        const uint64_t i0 = insert_zero(w, bit);
-        amp_t r = cfma(e1, a[i0 + s], cmul(e0, a[i0]));
-        r.x *= scale;
-        r.y *= scale;
-        out[w] = r;
-    }
-}
-
-// out[j] = amp[bit(j)] * a[j with the bit removed]: kron(state, new) + move (gates.py:149-152).
-__global__ __launch_bounds__(QSV_BLOCK) void k_insert(const amp_t *__restrict__ a, amp_t *__restrict__ out,
-                                                     uint64_t out_amps, int bit, cplx c0, cplx c1) {
-    for (uint64_t j = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x; j < out_amps;
-         j += static_cast<uint64_t>(gridDim.x) * blockDim.x) {
-        const uint64_t low = j & ((1ull << bit) - 1ull);
-        const uint64_t src = ((j >> (bit + 1)) << bit) | low;
-        out[j] = cmul(((j >> bit) & 1ull) ? c1 : c0, a[src]);
-    }
-}
-
-struct PermArgs {
-    int32_t n;
-    uint8_t src_bit[64];  // bit j of the destination index comes from bit src_bit[j] of the source index
-};
-
-__global__ __launch_bounds__(QSV_BLOCK) void k_permute(const amp_t *__restrict__ a, amp_t *__restrict__ out,
-                                                      uint64_t amps, const PermArgs g) {
-    for (uint64_t j = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x; j < amps;
-         j += static_cast<uint64_t>(gridDim.x) * blockDim.x) {
-        uint64_t src = 0;
-        for (int b = 0; b < g.n; ++b) src |= ((j >> b) & 1ull) << g.src_bit[b];
-        out[j] = a[src];
-    }
-}
-
-__global__ __launch_bounds__(QSV_BLOCK) void k_norm2(const amp_t *__restrict__ a, uint64_t amps,
-                                                    double *__restrict__ partials) {
-    double s = 0.0, unused = 0.0;
-    for (uint64_t i = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x; i < amps;
-         i += static_cast<uint64_t>(gridDim.x) * blockDim.x) {
-        const amp_t v = a[i];
-        s += v.x * v.x + v.y * v.y;
-    }
-    block_sum2(s, unused);
-    if (threadIdx.x == 0) {
-        partials[2 * blockIdx.x] = s;
-        partials[2 * blockIdx.x + 1] = 0.0;
-    }
-}
-
-__global__ __launch_bounds__(QSV_BLOCK) void k_inner(const amp_t *__restrict__ a, const amp_t *__restrict__ b,
-                                                    uint64_t amps, double *__restrict__ partials) {
-    double re = 0.0, im = 0.0;
-    for (uint64_t i = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x; i < amps;
-         i += static_cast<uint64_t>(gridDim.x) * blockDim.x) {
-        const amp_t x = a[i], y = b[i];
-        re += x.x * y.x + x.y * y.y;  // conj(x) * y
-        im += x.x * y.y - x.y * y.x;
-    }
-    block_sum2(re, im);
-    if (threadIdx.x == 0) {
-        partials[2 * blockIdx.x] = re;
-        partials[2 * blockIdx.x + 1] = im;
-    }
-}
-
-// <psi| P |psi> for a Pauli string: P|i> = i^{nY} (-1)^{popcount(i & zmask)} |i ^ xmask>  (Y = i X Z).
-// partials[2b], [2b+1] = real and imaginary part of this block's share of sum_i conj(psi[i ^ xmask]) sign(i) psi[i];
-// the factor i^{nY} is applied on the host.
-__global__ __launch_bounds__(QSV_BLOCK) void k_expect_pauli(const amp_t *__restrict__ a, uint64_t amps,
-                                                           uint64_t xmask, uint64_t zmask,
-                                                           double *__restrict__ partials) {
-    double re = 0.0, im = 0.0;
-    for (uint64_t i = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x; i < amps;
-         i += static_cast<uint64_t>(gridDim.x) * blockDim.x) {
-        const amp_t x = a[i ^ xmask], y = a[i];
-        const double s = (__popcll(i & zmask) & 1) ? -1.0 : 1.0;
-        re += s * (x.x * y.x + x.y * y.y);  // conj(x) * y
-        im += s * (x.x * y.y - x.y * y.x);
-    }
-    block_sum2(re, im);
-    if (threadIdx.x == 0) {
-        partials[2 * blockIdx.x] = re;
-        partials[2 * blockIdx.x + 1] = im;
-    }
-}
-
-// One planned pass of qsv_expect_pauli_sum (qsv_pauli_plan.h): up to T Pauli strings with one shared xmask.
-struct PauliPassArgs {
-    uint64_t items;      // pairs (amps / 2), or amps for the diagonal group
-    uint64_t xmask;
-    int32_t pivot;       // lowest set bit of xmask (unused by the diagonal form)
-    uint32_t odd;        // bit t: term t has odd nY and accumulates Im c instead of Re c
-    uint64_t zmask[qsv_pauli_plan::PAULI_TERMS_PER_PASS];   // 0 beyond the pass's terms
-};
-
-// partials[block * T + t] = this block's share of sum_i s_t(i) Re c(i) (Im c(i) for odd nY) over the visited i:
-// every i for the diagonal group (c = |psi[i]|^2), the i with a clear pivot bit otherwise (c = conj(psi[i ^ xmask]) psi[i],
-// each amplitude read once).  The product is formed once per item; a term costs a sign and one double accumulator.
-// PAULI_ITEMS independent items are loaded before any is used, so a thread keeps 2 x PAULI_ITEMS 16-byte loads in flight.
-constexpr int PAULI_ITEMS = 4;
-
-template <int T, bool DIAG>
-__global__ __launch_bounds__(QSV_BLOCK) void k_expect_pauli_group(const amp_t *__restrict__ a, const PauliPassArgs g,
-                                                                 double *__restrict__ partials) {
-    double acc[T];
-#pragma unroll
-    for (int t = 0; t < T; ++t) acc[t] = 0.0;
-    auto add = [&](uint64_t i, double re, double im) {
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            const double v = (!DIAG && ((g.odd >> t) & 1u)) ? im : re;
-            acc[t] += (__popcll(i & g.zmask[t]) & 1) ? -v : v;
-        }
-    };
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
-    uint64_t w = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x;
-    for (; w + (PAULI_ITEMS - 1) * stride < g.items; w += PAULI_ITEMS * stride) {
-        uint64_t i[PAULI_ITEMS];
-        amp_t x[PAULI_ITEMS], y[PAULI_ITEMS];
-#pragma unroll
-        for (int u = 0; u < PAULI_ITEMS; ++u) {
-            i[u] = DIAG ? w + u * stride : insert_zero(w + u * stride, g.pivot);
-            y[u] = a[i[u]];
-            if constexpr (!DIAG) x[u] = a[i[u] ^ g.xmask];
-        }
-#pragma unroll
-        for (int u = 0; u < PAULI_ITEMS; ++u) {
-            if constexpr (DIAG) add(i[u], y[u].x * y[u].x + y[u].y * y[u].y, 0.0);
-            else add(i[u], x[u].x * y[u].x + x[u].y * y[u].y, x[u].x * y[u].y - x[u].y * y[u].x);   // conj(x) * y
-        }
-    }
-    for (; w < g.items; w += stride) {
-        const uint64_t i = DIAG ? w : insert_zero(w, g.pivot);
-        const amp_t y = a[i];
-        if constexpr (DIAG) {
-            add(i, y.x * y.x + y.y * y.y, 0.0);
-        } else {
-            const amp_t x = a[i ^ g.xmask];
-            add(i, x.x * y.x + x.y * y.y, x.x * y.y - x.y * y.x);
-        }
-    }
-    __shared__ double sums[QSV_BLOCK / 64][T];
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-        const double s = wave_sum(acc[t]);
-        if ((threadIdx.x & 63) == 0) sums[threadIdx.x >> 6][t] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < T) {
-        double s = 0.0;
-        for (int wv = 0; wv < QSV_BLOCK / 64; ++wv) s += sums[wv][threadIdx.x];
-        partials[static_cast<uint64_t>(blockIdx.x) * T + threadIdx.x] = s;
-    }
-}
-
-// One planned pass of qsv_apply_pauli_rotations (qsv_pauli_rotation_plan.h): up to T rotations exp(-i theta/2 P), each
-// diagonal or flipping the pass's xmask, applied in the caller's order to every pair {i, i ^ xmask}.
-struct PauliRotateArgs {
-    uint64_t items;      // pairs (amps / 2), or amps for a diagonal pass
-    uint64_t xmask;
-    int32_t pivot;       // highest set bit of xmask (unused by the diagonal form)
-    uint32_t diag;       // bit t: term t is diagonal (set beyond the pass's terms, which are padded with theta = 0)
-    uint32_t rot;        // bits 2t, 2t + 1: nY & 3 of term t
-    uint64_t zmask[qsv_pauli_rotation_plan::ROTATIONS_PER_PASS];
-    double cs[qsv_pauli_rotation_plan::ROTATIONS_PER_PASS];   // cos(theta / 2), computed on the host in double precision
-    double sn[qsv_pauli_rotation_plan::ROTATIONS_PER_PASS];   // sin(theta / 2)
-};
-
-// i^k v: a swap and signs of the real and imaginary part, never a multiplication (k is wave-uniform)
-__device__ __forceinline__ amp_t mul_i_pow(amp_t v, uint32_t k) {
-    amp_t r;
-    r.x = (k & 1u) ? v.y : v.x;
-    r.y = (k & 1u) ? v.x : v.y;
-    if (k == 1u || k == 2u) r.x = -r.x;
-    if (k >= 2u) r.y = -r.y;
-    return r;
-}
-
-// (c - i t) v
-__device__ __forceinline__ amp_t phase_amp(double c, double t, amp_t v) {
-    amp_t r;
-    r.x = fma(t, v.y, c * v.x);
-    r.y = fma(-t, v.x, c * v.y);
-    return r;
-}
-
-// The T terms of the pass on one work item, in the caller's order.  a = psi[i], b = psi[i ^ xmask] (unused when DIAG);
-// s(j) = (-1)^{popcount(j & zmask)} and s(i ^ xmask) = s(i) s(xmask).  What a term is (diagonal or not, its power of i,
-// whether its sign differs between the partners) is wave-uniform: scalar branches, no divergence.
-template <int T, bool DIAG>
-__device__ __forceinline__ void pauli_rotate_item(const PauliRotateArgs &g, uint64_t i, amp_t &a, amp_t &b) {
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-        const uint64_t z = g.zmask[t];
-        const double c = g.cs[t], sn = g.sn[t];
-        const bool minus = __popcll(i & z) & 1;                   // s(i) = -1
-        if (DIAG || ((g.diag >> t) & 1u)) {
-            a = phase_amp(c, minus ? -sn : sn, a);
-            if constexpr (!DIAG) {
-                const bool differ = __popcll(g.xmask & z) & 1;
-                b = phase_amp(c, (minus != differ) ? -sn : sn, b);
-            }
-        } else if constexpr (!DIAG) {
-            const uint32_t n_y = (g.rot >> (2 * t)) & 3u, k = (n_y + 3u) & 3u;   // -i i^{nY} = i^k
-            const bool differ = n_y & 1u;                                       // s(i') = (-1)^{nY} s(i)
-            const double ta = (minus != differ) ? -sn : sn;   // sn s(i'), in front of b in a'
-            const double tb = minus ? -sn : sn;               // sn s(i),  in front of a in b'
-            const amp_t ra = mul_i_pow(a, k), rb = mul_i_pow(b, k);
-            a = amp_t{fma(ta, rb.x, c * a.x), fma(ta, rb.y, c * a.y)};
-            b = amp_t{fma(tb, ra.x, c * b.x), fma(tb, ra.y, c * b.y)};
-        }
-    }
-}
-
-// Work item w owns amplitude w (DIAG) or the pair {i, i ^ xmask} with i = insert_zero(w, pivot): it loads it, applies the
-// pass in registers and stores it -- in place, no barrier, no LDS.  One work item per thread, as in the gate kernels: a
-// pair item has its two 16-byte loads in flight together, and more items per thread were measured slower (DESIGN.md,
-// "Pauli rotations").  With the pivot at the highest flipped bit the i of a workgroup are consecutive (up to the one jump
-// over the pivot bit) and so are the partners, up to a permutation inside their range: for pivot >= 3 every wave access
-// covers whole 128-byte lines.  For a pivot on bits 0..2 the two halves of a line belong to the same thread or to a
-// neighbour; these passes use plain (cached) accesses so that the halves meet in L2 before the line is written back
-// (NT = false).  The loop only runs more than once beyond 2^32 work items (grid_for).
-template <int T, bool DIAG, bool NT>
-__global__ __launch_bounds__(QSV_BLOCK) void k_pauli_rotate_group(amp_t *__restrict__ psi, const PauliRotateArgs g) {
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * QSV_BLOCK;
-    for (uint64_t w = blockIdx.x * static_cast<uint64_t>(QSV_BLOCK) + threadIdx.x; w < g.items; w += stride) {
-        const uint64_t i = DIAG ? w : insert_zero(w, g.pivot);
-        amp_t a = ld<NT>(psi + i), b = amp_t{0.0, 0.0};
-        if constexpr (!DIAG) b = ld<NT>(psi + (i ^ g.xmask));
-        pauli_rotate_item<T, DIAG>(g, i, a, b);
-        st<NT>(psi + i, a);
-        if constexpr (!DIAG) st<NT>(psi + (i ^ g.xmask), b);
-    }
-}
-
-// Sampling, pass 1: chunk_sums[c] = sum of |amp|^2 over chunk c (SAMPLE_CHUNK consecutive amplitudes per workgroup).
-constexpr int SAMPLE_CHUNK = 4096;
-
-__global__ __launch_bounds__(QSV_BLOCK) void k_chunk_sums(const amp_t *__restrict__ a, uint64_t amps,
-                                                         double *__restrict__ chunk_sums) {
-    const uint64_t chunks = (amps + SAMPLE_CHUNK - 1) / SAMPLE_CHUNK;
-    for (uint64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
-        double s = 0.0, unused = 0.0;
-        // thread t owns SAMPLE_CHUNK / QSV_BLOCK consecutive amplitudes: the same split pass 2 walks
-        constexpr int PER = SAMPLE_CHUNK / QSV_BLOCK;
-        const uint64_t first = c * SAMPLE_CHUNK + static_cast<uint64_t>(threadIdx.x) * PER;
-        for (int k = 0; k < PER; ++k)
-            if (first + k < amps) {
-                const amp_t v = a[first + k];
-                s += v.x * v.x + v.y * v.y;
-            }
-        __syncthreads();  // block_sum2 reuses its shared scratch across iterations
-        block_sum2(s, unused);
-        if (threadIdx.x == 0) chunk_sums[c] = s;
-    }
-}
-
-// Sampling, pass 2: one workgroup per shot walks its chunk and returns the first index whose running sum of
-// |amp|^2 exceeds `residual` (clamped to the chunk's last amplitude against rounding).
-__global__ __launch_bounds__(QSV_BLOCK) void k_sample_in_chunk(const amp_t *__restrict__ a, uint64_t amps,
-                                                              const uint64_t *__restrict__ chunk_of_shot,
-                                                              const double *__restrict__ residual_of_shot,
-                                                              uint64_t *__restrict__ out) {
-    __shared__ double part[QSV_BLOCK];
-    constexpr int PER = SAMPLE_CHUNK / QSV_BLOCK;
-    const uint64_t c = chunk_of_shot[blockIdx.x];
-    const double residual = residual_of_shot[blockIdx.x];
-    const uint64_t first = c * SAMPLE_CHUNK + static_cast<uint64_t>(threadIdx.x) * PER;
-    double mine[PER];
-    double s = 0.0;
-    for (int k = 0; k < PER; ++k) {
-        double p = 0.0;
-        if (first + k < amps) {
-            const amp_t v = a[first + k];
-            p = v.x * v.x + v.y * v.y;
-        }
-        mine[k] = p;
-        s += p;
-    }
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double run = 0.0;
-        int t = 0;
-        for (; t < QSV_BLOCK - 1; ++t) {
-            if (run + part[t] > residual) break;
-            run += part[t];
-        }
-        part[0] = run;                       // sum before thread t
-        part[1] = static_cast<double>(t);    // the thread that holds the crossing
-    }
-    __syncthreads();
-    const int owner = static_cast<int>(part[1]);
-    if (threadIdx.x == owner) {
-        double run = part[0];
-        int k = 0;
-        for (; k < PER - 1; ++k) {
-            if (run + mine[k] > residual) break;
-            run += mine[k];
-        }
-        uint64_t idx = first + k;
-        if (idx >= amps) idx = amps - 1;
-        out[blockIdx.x] = idx;
-    }
-}
-
-__global__ void k_gather_prob(const amp_t *__restrict__ a, const uint64_t *__restrict__ idx, int count,
-                              double *__restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) {
-        const amp_t v = a[idx[i]];
-        out[i] = v.x * v.x + v.y * v.y;
-    }
-}
-
-__global__ __launch_bounds__(QSV_BLOCK) void k_scale(amp_t *__restrict__ a, uint64_t amps, cplx c) {
-    for (uint64_t i = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x; i < amps;
-         i += static_cast<uint64_t>(gridDim.x) * blockDim.x)
-        a[i] = cmul(c, a[i]);
-}
-
 // Register-to-register copy (qsv_copy; also the "what does a plain copy reach on this box" leg of bench.py), every
 // wave-instruction a whole 1 KiB segment, nontemporal both ways (hipMemcpy D2D: 4.9 TB/s).  Forms (QSV_COPY_MODE, for
 // measurements; profiles/r03_copy_kernel.txt): 0 = four amplitudes per thread through registers, 1 = one amplitude per
@@ -1218,253 +762,6 @@ __global__ __launch_bounds__(QSV_BLOCK) void k_copy(amp_t *__restrict__ dst, con
     }
 }
 
-__global__ __launch_bounds__(QSV_BLOCK) void k_zero(amp_t *__restrict__ a, uint64_t amps, uint64_t one_at) {
-    for (uint64_t i = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x; i < amps;
-         i += static_cast<uint64_t>(gridDim.x) * blockDim.x)
-        a[i] = amp_t{i == one_at ? 1.0 : 0.0, 0.0};
-}
-
-// splitmix64: counter-based, so a sharded register can be filled shard by shard from global indices.
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-__global__ __launch_bounds__(QSV_BLOCK) void k_fill_random(amp_t *__restrict__ a, uint64_t amps, uint64_t seed,
-                                                          uint64_t index_offset, double *__restrict__ partials) {
-    double s = 0.0, unused = 0.0;
-    const uint64_t key = splitmix64(seed);
-    for (uint64_t i = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x; i < amps;
-         i += static_cast<uint64_t>(gridDim.x) * blockDim.x) {
-        const uint64_t g = i + index_offset;
-        const uint64_t r1 = splitmix64(key ^ (2 * g)), r2 = splitmix64(key ^ (2 * g + 1));
-        const double u1 = (static_cast<double>(r1 >> 11) + 0.5) * 0x1.0p-53;  // (0, 1)
-        const double u2 = (static_cast<double>(r2 >> 11) + 0.5) * 0x1.0p-53;
-        const double rad = sqrt(-2.0 * log(u1));
-        double sn, cs;
-        sincos(6.283185307179586476925286766559 * u2, &sn, &cs);
-        const amp_t v = {rad * cs, rad * sn};
-        a[i] = v;
-        s += v.x * v.x + v.y * v.y;
-    }
-    block_sum2(s, unused);
-    if (threadIdx.x == 0) {
-        partials[2 * blockIdx.x] = s;
-        partials[2 * blockIdx.x + 1] = 0.0;
-    }
-}
-
-
-// ----------------------------------------------------------------------------------------------------
-// Streaming forms of the read-out / reshaping kernels (registers of at least 2^14 amplitudes; the plain grid-stride
-// forms above stay for smaller ones).  Common shape: one work item = 64 consecutive amplitudes per wave-instruction,
-// ITEMS independent items per thread in flight, nontemporal accesses (every amplitude is touched once), and a target
-// bit below 6 is resolved inside the wave -- the partner amplitude comes from __shfl_xor, compaction / expansion by
-// one qubit is a lane gather -- so that every global access is a whole 1 KiB segment whatever the bit.
-// ----------------------------------------------------------------------------------------------------
-constexpr int RO_ITEMS = 4;          // the reductions (k_measure_probs_s): four items per thread and trip
-// amplitudes per thread of the kernels that move the register (collapse, insert, permute, table diagonals): one -- the
-// plain copy kernel reaches 6.55 TB/s with one amplitude per thread and 6.05 with four (profiles/r03_copy_kernel.txt),
-// and these kernels follow it (profiles/r03_readout_kernels.csv).  QSV_RO_ITEMS = 1 / 2 / 4 for measurements.
-// items for a launch over `count` amplitudes: an AQL dispatch counts work-items in 32 bits (2^24 - 1 workgroups of 256),
-// so registers beyond 2^32 amplitudes per launch take two or four per thread
-static int ro_fit_items(int items, uint64_t count) {
-    while (items < 4 && count / (static_cast<uint64_t>(QSV_BLOCK) * items) > 0x00ffffffull) items *= 2;
-    return items;
-}
-static int ro_move_items() {
-    static const int items = [] {
-        const char *e = getenv("QSV_RO_ITEMS");
-        const int v = e ? atoi(e) : 1;
-        return v == 2 || v == 4 ? v : 1;   // (the table diagonals take two: 6.2 TB/s against 5.85 with one or four)
-    }();
-    return items;
-}
-#define QSV_RO_DISPATCH(items, CALL)  \
-    do {                              \
-        if ((items) == 4) { constexpr int IT = 4; CALL; } \
-        else if ((items) == 2) { constexpr int IT = 2; CALL; } \
-        else { constexpr int IT = 1; CALL; } \
-    } while (0)
-constexpr int RO_MIN_QUBITS = 14;  // below this the plain grid-stride forms run (tiles of 2^10 amplitudes must divide)
-
-__device__ __forceinline__ amp_t shfl_amp(amp_t v, int src_lane) {
-    amp_t r;
-    r.x = __shfl(v.x, src_lane, 64);
-    r.y = __shfl(v.y, src_lane, 64);
-    return r;
-}
-
-// partials[2*block + s] = sum over this block's pairs of |eig_s[0] a0 + eig_s[1] a1|^2   (M.apply, gates.py:173-183)
-template <bool LOW>
-__global__ __launch_bounds__(QSV_BLOCK) void k_measure_probs_s(const amp_t *__restrict__ a, uint64_t amps, int bit,
-                                                               cplx e00, cplx e01, cplx e10, cplx e11,
-                                                               double *__restrict__ partials) {
-    double p0 = 0.0, p1 = 0.0;
-    const uint64_t s = 1ull << bit;
-    if constexpr (LOW) {
-        // natural order: a lane whose bit is 0 holds a0 and fetches a1 from its partner (and accumulates outcome 0),
-        // a lane whose bit is 1 holds a1, fetches a0 and accumulates outcome 1: no lane idles, no amplitude is read twice
-        const bool up = (threadIdx.x >> bit) & 1;
-        const cplx mine = up ? e11 : e00, theirs = up ? e10 : e01;
-        double acc = 0.0;
-        const uint64_t stride = static_cast<uint64_t>(gridDim.x) * QSV_BLOCK * RO_ITEMS;
-        for (uint64_t i0 = blockIdx.x * static_cast<uint64_t>(QSV_BLOCK) * RO_ITEMS + threadIdx.x; i0 < amps; i0 += stride) {
-            amp_t v[RO_ITEMS];
-#pragma unroll
-            for (int u = 0; u < RO_ITEMS; ++u) v[u] = __builtin_nontemporal_load(a + i0 + u * QSV_BLOCK);
-#pragma unroll
-            for (int u = 0; u < RO_ITEMS; ++u) {
-                const amp_t r = cfma(theirs, shfl_xor_amp(v[u], 1 << bit), cmul(mine, v[u]));
-                acc += r.x * r.x + r.y * r.y;
-            }
-        }
-        p0 = up ? 0.0 : acc;
-        p1 = up ? acc : 0.0;
-    } else {
-        const uint64_t pairs = amps >> 1;
-        const uint64_t stride = static_cast<uint64_t>(gridDim.x) * QSV_BLOCK * RO_ITEMS;
-        for (uint64_t w0 = blockIdx.x * static_cast<uint64_t>(QSV_BLOCK) * RO_ITEMS + threadIdx.x; w0 < pairs; w0 += stride) {
-            amp_t lo[RO_ITEMS], hi[RO_ITEMS];
-#pragma unroll
-            for (int u = 0; u < RO_ITEMS; ++u) {
-                const uint64_t i = insert_zero(w0 + u * QSV_BLOCK, bit);
-                lo[u] = __builtin_nontemporal_load(a + i);
-                hi[u] = __builtin_nontemporal_load(a + i + s);
-            }
-#pragma unroll
-            for (int u = 0; u < RO_ITEMS; ++u) {
-                const amp_t r0 = cfma(e01, hi[u], cmul(e00, lo[u]));
-                const amp_t r1 = cfma(e11, hi[u], cmul(e10, lo[u]));
-                p0 += r0.x * r0.x + r0.y * r0.y;
-                p1 += r1.x * r1.x + r1.y * r1.y;
-            }
-        }
-    }
-    block_sum2(p0, p1);
-    if (threadIdx.x == 0) {
-        partials[2 * blockIdx.x] = p0;
-        partials[2 * blockIdx.x + 1] = p1;
-    }
-}
-
-// out[w] = scale * (e0 a[i0] + e1 a[i0 + s]), i0 = w with a zero inserted at `bit`.
-template <bool LOW, int ITEMS>
-__global__ __launch_bounds__(QSV_BLOCK) void k_collapse_s(const amp_t *__restrict__ a, amp_t *__restrict__ out,
-                                                          uint64_t pairs, int bit, cplx e0, cplx e1, double scale) {
-    const cplx f0 = {e0.re * scale, e0.im * scale}, f1 = {e1.re * scale, e1.im * scale};
-    const uint64_t w0 = (blockIdx.x * static_cast<uint64_t>(QSV_BLOCK) + (threadIdx.x & ~63u)) * ITEMS + (threadIdx.x & 63);
-    if constexpr (LOW) {
-        // a wave turns 2 * ITEMS rows of 64 amplitudes into ITEMS rows of 64 results: the pair sum lands in the
-        // lanes whose bit is 0, and output lane l gathers it from lane insert_zero(l & 31, bit) of row l >> 5
-        const int lane = threadIdx.x & 63;
-        const int src = static_cast<int>(insert_zero(static_cast<uint64_t>(lane & 31), bit));
-        amp_t v[2 * ITEMS];
-#pragma unroll
-        for (int u = 0; u < 2 * ITEMS; ++u) v[u] = __builtin_nontemporal_load(a + 2 * (w0 - lane) + u * 64 + lane);
-#pragma unroll
-        for (int u = 0; u < ITEMS; ++u) {
-            const amp_t ra = cfma(f1, shfl_xor_amp(v[2 * u], 1 << bit), cmul(f0, v[2 * u]));
-            const amp_t rb = cfma(f1, shfl_xor_amp(v[2 * u + 1], 1 << bit), cmul(f0, v[2 * u + 1]));
-            const amp_t ga = shfl_amp(ra, src), gb = shfl_amp(rb, src);
-            __builtin_nontemporal_store(lane < 32 ? ga : gb, out + w0 + u * 64);
-        }
-    } else {
-        const uint64_t s = 1ull << bit;
-        amp_t lo[ITEMS], hi[ITEMS];
-#pragma unroll
-        for (int u = 0; u < ITEMS; ++u) {
-            const uint64_t i = insert_zero(w0 + u * 64, bit);
-            lo[u] = __builtin_nontemporal_load(a + i);
-            hi[u] = __builtin_nontemporal_load(a + i + s);
-        }
-#pragma unroll
-        for (int u = 0; u < ITEMS; ++u)
-            __builtin_nontemporal_store(cfma(f1, hi[u], cmul(f0, lo[u])), out + w0 + u * 64);
-    }
-}
-
-// out[j] = amp[bit(j)] * a[j with the bit removed]
-template <bool LOW, int ITEMS>
-__global__ __launch_bounds__(QSV_BLOCK) void k_insert_s(const amp_t *__restrict__ a, amp_t *__restrict__ out,
-                                                        uint64_t in_amps, int bit, cplx c0, cplx c1) {
-    const uint64_t w0 = (blockIdx.x * static_cast<uint64_t>(QSV_BLOCK) + (threadIdx.x & ~63u)) * ITEMS + (threadIdx.x & 63);
-    amp_t v[ITEMS];
-#pragma unroll
-    for (int u = 0; u < ITEMS; ++u) v[u] = __builtin_nontemporal_load(a + w0 + u * 64);
-    if constexpr (LOW) {
-        // a row of 64 inputs becomes two rows of 64 outputs: output lane l of row h reads input lane 32 h + (l without
-        // its `bit`) and takes the factor of its own bit
-        const int lane = threadIdx.x & 63;
-        const int from = static_cast<int>(((static_cast<uint32_t>(lane) >> (bit + 1)) << bit) | (lane & ((1 << bit) - 1)));
-        const cplx c = ((lane >> bit) & 1) ? c1 : c0;
-#pragma unroll
-        for (int u = 0; u < ITEMS; ++u) {
-            const uint64_t o = 2 * (w0 - lane + u * 64) + lane;
-            __builtin_nontemporal_store(cmul(c, shfl_amp(v[u], from)), out + o);
-            __builtin_nontemporal_store(cmul(c, shfl_amp(v[u], 32 + from)), out + o + 64);
-        }
-    } else {
-        const uint64_t s = 1ull << bit;
-#pragma unroll
-        for (int u = 0; u < ITEMS; ++u) {
-            const uint64_t o = insert_zero(w0 + u * 64, bit);
-            __builtin_nontemporal_store(cmul(c0, v[u]), out + o);
-            __builtin_nontemporal_store(cmul(c1, v[u]), out + o + s);
-        }
-    }
-}
-
-// Qubit permutation: out[j] = a[p(j)], p moves index bits.  A wave owns a tile of 64 amplitudes that is 8 whole
-// 128-byte lines on BOTH sides: the tile's six index bits are the destination bits 0..2 (inside a line), the destination
-// bits fed by source bits 0..2, and filler bits.  Stores are consecutive within each line; loads hit 8 whole source lines
-// in some lane order -- no LDS and no shuffle, the coalescer sees complete lines either way.  The tile's base addresses
-// are wave-uniform: the destination base is the tile number with zeros inserted at the tile's bit positions, the source
-// base is that number pushed through the bit permutation one byte at a time (256-entry tables, scalar loads).
-struct PermTileArgs {
-    uint64_t tiles;          // amps / 64
-    int32_t bytes;           // ceil(n / 8): lookup tables
-    uint8_t tile_dst[6];     // destination bit of lane bit k, ascending (tile_dst[0..2] = 0, 1, 2)
-    uint8_t tile_src[6];     // source bit that feeds it
-};
-
-template <int ITEMS>
-__global__ __launch_bounds__(QSV_BLOCK) void k_permute_s(const amp_t *__restrict__ a, amp_t *__restrict__ out,
-                                                         const PermTileArgs g,
-                                                         const uint64_t *__restrict__ lut /*[bytes][256]*/) {
-    const int lane = threadIdx.x & 63;
-    uint64_t dst_lane = 0, src_lane = 0;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const uint64_t b = (lane >> k) & 1;
-        dst_lane |= b << g.tile_dst[k];
-        src_lane |= b << g.tile_src[k];
-    }
-    // wave-uniform on purpose (readfirstlane): the per-tile address arithmetic below then runs on the scalar unit
-    const uint64_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (QSV_BLOCK / 64) + (threadIdx.x >> 6));
-    const uint64_t waves = static_cast<uint64_t>(gridDim.x) * (QSV_BLOCK / 64);
-    for (uint64_t t0 = wave * ITEMS; t0 < g.tiles; t0 += waves * ITEMS) {
-        amp_t v[ITEMS];
-        uint64_t dst[ITEMS];
-#pragma unroll
-        for (int u = 0; u < ITEMS; ++u) {
-            uint64_t d = t0 + u;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) d = insert_zero(d, g.tile_dst[k]);
-            uint64_t sidx = 0;
-            for (int b = 0; b < g.bytes; ++b) sidx |= lut[b * 256 + ((d >> (8 * b)) & 255)];
-            dst[u] = d | dst_lane;
-            v[u] = amp_t{0.0, 0.0};
-            if (t0 + u < g.tiles) v[u] = __builtin_nontemporal_load(a + (sidx | src_lane));
-        }
-#pragma unroll
-        for (int u = 0; u < ITEMS; ++u)
-            if (t0 + u < g.tiles) __builtin_nontemporal_store(v[u], out + dst[u]);
-    }
-}
-
 // K-qubit diagonal (K <= 6): a[i] *= table[bits of i at bitpos], natural order, table in LDS.
 template <int ITEMS>
 __global__ __launch_bounds__(QSV_BLOCK) void k_diag_table_s(amp_t *__restrict__ a, uint64_t amps, int K,
@@ -1489,386 +786,9 @@ __global__ __launch_bounds__(QSV_BLOCK) void k_diag_table_s(amp_t *__restrict__ 
     }
 }
 
-
-// ----------------------------------------------------------------------------------------------------
-// Reduced density matrix of k <= 6 kept qubits in ONE read pass:  rho[i][j] = sum_g psi[i, g] conj(psi[j, g]),
-// g running over the 2^(n-k) settings of the other qubits.  That is X X^H for the (2^k x 2^(n-k)) matrix X -- a rank
-// update with a tiny result -- and runs on the f64 matrix cores: a lane (i = lane & 15, kk = lane >> 4) loads ONE
-// amplitude, row i of group 4 q + kk, and the same register pair serves as A[i][kk] and as B[kk][j] of
-// v_mfma_f64_16x16x4_f64 (re = xr xr^T + xi xi^T, im = xi xr^T - xr xi^T).  T = 1, 2, 4 row tiles of 16 cover
-// 2^k <= 16, 32, 64; only the upper triangle of tiles is accumulated (rho is Hermitian).  The sum is deterministic:
-// waves add into their workgroup's LDS tile one after the other, workgroups write partials, a second launch adds
-// the partials in index order.
-// ----------------------------------------------------------------------------------------------------
-struct RdmArgs {
-    uint64_t W;          // groups = amps >> k
-    uint64_t or_mask;    // unused (0); lets deposit() serve this struct too
-    int32_t nins;        // k
-    int32_t D;           // 2^k
-    uint32_t pos[8];     // ascending kept bits
-};
-
-// RDM_U quads of groups are loaded before the first MFMA of an iteration (a wave with a single 16-byte load in flight
-// spends its life waiting for HBM: 0.25-1.3 TB/s in the first version of this kernel).  When 2^k < 16 the sixteen rows
-// of the tile are shared by S = 16 / 2^k groups (row i = r + 2^k s): every lane still loads a different amplitude, the
-// tile then holds S x S blocks of which only the S diagonal ones (same group on both sides) mean anything; the host adds
-// those up.
-constexpr int RDM_LOADS = 4;   // 16-byte loads per lane and buffer: RDM_LOADS / T quads of groups
-
-template <int T>
-__global__ __launch_bounds__(QSV_BLOCK) void k_rdm(const amp_t *__restrict__ a, const RdmArgs g,
-                                                   const uint64_t *__restrict__ hoff,  // [16 T] row offsets
-                                                   double *__restrict__ partials) {    // [grid][P][2][256]
-    constexpr int P = T * (T + 1) / 2;
-    constexpr int RDM_U = RDM_LOADS / T;
-    __shared__ double red[P * 2 * 256];
-    const int lane = threadIdx.x & 63, i = lane & 15, kk = lane >> 4;
-    const int S = T == 1 ? 16 / g.D : 1;                 // groups sharing the 16 rows of a tile (D = 1 never occurs)
-    const uint64_t sub = T == 1 ? static_cast<uint64_t>(i / g.D) : 0;
-    uint64_t row_off[T];
-#pragma unroll
-    for (int t = 0; t < T; ++t) row_off[t] = hoff[T == 1 ? i % g.D : 16 * t + i];
-    // C independent accumulator sets: consecutive MFMAs never wait for one another's result (with one set per tile
-    // pair the two updates of `re` and of `im` in a step are back-to-back dependent issues of a 64-cycle instruction)
-    constexpr int C = RDM_U >= 2 ? 2 : 1;
-    f64x4 re[C][P], im[C][P];
-#pragma unroll
-    for (int c = 0; c < C; ++c)
-#pragma unroll
-        for (int p = 0; p < P; ++p) re[c][p] = im[c][p] = f64x4{0.0, 0.0, 0.0, 0.0};
-    // a step = 4 S groups = one MFMA k-slice per tile pair.  The host sizes the grid so that waves * RDM_U divides the
-    // step count: every load below is unconditional.
-    const uint64_t steps = g.W / (4 * static_cast<uint64_t>(S));
-    const uint64_t wave = blockIdx.x * (QSV_BLOCK / 64) + (threadIdx.x >> 6);
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * (QSV_BLOCK / 64) * RDM_U;
-    auto fetch = [&](amp_t (&x)[RDM_U][T], uint64_t q0) {
-#pragma unroll
-        for (int u = 0; u < RDM_U; ++u) {
-            const uint64_t base = deposit(((q0 + u) * 4 + kk) * S + sub, g);
-#pragma unroll
-            for (int t = 0; t < T; ++t) x[u][t] = __builtin_nontemporal_load(a + base + row_off[t]);
-        }
-    };
-    auto update = [&](const amp_t (&x)[RDM_U][T]) {
-        // first halves of every sum, then second halves: 2 C P independent instructions between dependent ones
-#pragma unroll
-        for (int u = 0; u < RDM_U; ++u) {
-            int p = 0;
-#pragma unroll
-            for (int ti = 0; ti < T; ++ti)
-#pragma unroll
-                for (int tj = ti; tj < T; ++tj, ++p) {
-                    re[u % C][p] = __builtin_amdgcn_mfma_f64_16x16x4f64(x[u][ti].x, x[u][tj].x, re[u % C][p], 0, 0, 0);
-                    im[u % C][p] = __builtin_amdgcn_mfma_f64_16x16x4f64(x[u][ti].y, x[u][tj].x, im[u % C][p], 0, 0, 0);
-                }
-        }
-#pragma unroll
-        for (int u = 0; u < RDM_U; ++u) {
-            int p = 0;
-#pragma unroll
-            for (int ti = 0; ti < T; ++ti)
-#pragma unroll
-                for (int tj = ti; tj < T; ++tj, ++p) {
-                    re[u % C][p] = __builtin_amdgcn_mfma_f64_16x16x4f64(x[u][ti].y, x[u][tj].y, re[u % C][p], 0, 0, 0);
-                    im[u % C][p] = __builtin_amdgcn_mfma_f64_16x16x4f64(-x[u][ti].x, x[u][tj].y, im[u % C][p], 0, 0, 0);
-                }
-        }
-        __builtin_amdgcn_sched_barrier(0);   // the other buffer's loads stay where they are written: behind these MFMAs
-    };
-    // A ring of NBUF buffers, no copies between them: while one feeds the matrix cores the loads of the NBUF - 1 others
-    // are in flight, and the wait in front of the MFMAs is for the OLDEST buffer only (a register copy at the loop end
-    // made the compiler wait for every outstanding load in the middle of the MFMAs: one buffer in flight per wave,
-    // 4.3 TB/s).  Every fetch is unconditional (past the end a wave re-reads its first chunk and drops it): with loads
-    // under a branch the compiler cannot count how many younger loads are in flight and waits for all of them.
-    // T = 4 runs one wave per SIMD (160 accumulator registers) and an update is 40 MFMAs = 1 us: three buffers ahead
-    // cover the HBM latency; T = 1 has four waves per SIMD and needs one.
-    constexpr int NBUF = T == 1 ? 2 : T == 2 ? 3 : 4;
-    amp_t x[NBUF][RDM_U][T];
-    const uint64_t first = wave * RDM_U;
-#pragma unroll
-    for (int b = 0; b < NBUF - 1; ++b) {
-        const uint64_t q = first + b * stride;
-        fetch(x[b], q < steps ? q : first);
-    }
-    for (uint64_t q0 = first; q0 < steps;) {
-#pragma unroll
-        for (int b = 0; b < NBUF; ++b) {
-            const uint64_t q = q0 + (NBUF - 1) * stride;
-            fetch(x[(b + NBUF - 1) % NBUF], q < steps ? q : first);
-            update(x[b]);
-            q0 += stride;
-            if (q0 >= steps) break;
-        }
-    }
-#pragma unroll
-    for (int c = 1; c < C; ++c)
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-            re[0][p] += re[c][p];
-            im[0][p] += im[c][p];
-        }
-    // deterministic sum over the four waves of the workgroup, then one partial per workgroup
-    for (int wv = 0; wv < QSV_BLOCK / 64; ++wv) {
-        if ((threadIdx.x >> 6) == wv) {
-#pragma unroll
-            for (int p = 0; p < P; ++p)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    double *slot_re = red + ((p * 2 + 0) * 4 + r) * 64 + lane;
-                    double *slot_im = red + ((p * 2 + 1) * 4 + r) * 64 + lane;
-                    *slot_re = (wv == 0 ? 0.0 : *slot_re) + re[0][p][r];
-                    *slot_im = (wv == 0 ? 0.0 : *slot_im) + im[0][p][r];
-                }
-        }
-        __syncthreads();
-    }
-    double *out = partials + static_cast<size_t>(blockIdx.x) * (P * 2 * 256);
-    for (int e = threadIdx.x; e < P * 2 * 256; e += QSV_BLOCK) out[e] = red[e];
-}
-
-// Round 3 form of the same rank update: a WORKGROUP tile staged through LDS, so that HBM is read in whole 1 KiB
-// wave-instructions whatever the kept bits are.  k_rdm above lets lane i of the MFMA operand fetch row i itself: the 16
-// rows of a group are 2^(kept bit) apart, so with kept bits outside the lowest four every lane touches a different
-// 128-byte line (scattered kept bits [0, 5, 12, 25] at n = 28: 2.9 TB/s; k = 6: 1.9).  Here a tile is (16 T rows) x (64
-// groups).  A wave-load is 64 CONSECUTIVE amplitudes for one setting c_h of the kept bits >= 6: the lane bits carry the
-// kept bits < 6 (rows) and 6 - l free bits (groups); the 16 T loads of a tile (each wave issues 4 T of them, one tile
-// ahead, into registers) are written into the LDS tile at [row][group ^ (row & 15)] and read back as MFMA operands --
-// lane (i, kk), row tile t, step m reads [16 t + i][(4 m + kk) ^ i]: 16 distinct 16-byte columns per 16-lane group.
-// The arithmetic is cut from four to three MFMAs per (tile pair, step): with a = xr_i, b = xi_i, c = xr_j, d = xi_j
-//     P1 += a c^T,  P2 += b d^T,  P3 += (a + b)(c - d)^T      re = P1 + P2,   im = b c^T - a d^T = P3 - P1 + P2,
-// 7.5 instead of 10 MFMAs per KiB at k = 6 (the kernel that is bound by the matrix cores).  The (pair, step) units of a
-// tile are dealt to the four waves: T <= 2: four steps each, all pairs; T = 4: five pairs x eight steps each.
-struct RdmTileArgs {
-    uint64_t tiles;      // tiles of 64 S groups
-    uint64_t or_mask;    // unused (0); lets deposit() serve this struct too
-    int32_t nins;        // h: kept bits >= 6
-    uint32_t pos[8];     // those bits, ascending
-    int32_t k, l, h;     // kept bits, of which below / from bit 6
-    uint32_t lmask;      // lane bits that are kept bits
-    int32_t log_s;       // 2^k < 16: log2 of the groups sharing the 16 rows
-    uint32_t regions;    // tile order: R > 1 walks R contiguous regions of the register side by side
-    uint64_t hoff[64];   // offset of setting c_h of the kept bits >= 6 (kernel arguments: scalar loads, no upload)
-};
-
-template <int T>
-__global__ __launch_bounds__(QSV_BLOCK) __attribute__((amdgpu_waves_per_eu(2, T == 4 ? 2 : 4))) void k_rdm_tile(
-    const amp_t *__restrict__ a, const RdmTileArgs g, double *__restrict__ partials) {   // [grid][P][2][256]
-    // Work split over the four waves.  T <= 2: four of the sixteen steps each, every tile pair.  T = 4 (ten pairs: all of
-    // them would be 240 accumulator registers): five pairs x eight steps.  Both halves run the SAME code on the pair list
-    // A = {(0,0), (2,2), (0,1), (2,3), (0,2)} of operand slots; the second half fills slot tt with row tile tt + 1 mod 4
-    // and so computes (1,1), (3,3), (1,2), (3,0), (1,3) -- the complement (the cyclic shift maps A onto it), with (3,0)
-    // standing for (0,3) as its conjugate transpose (the host reads that block mirrored).  (Two code paths with their
-    // own pair lists made the compiler hold both sets of operands: 256 registers and 100 spilled.)
-    constexpr int P = T * (T + 1) / 2, NL = 4 * T /* loads per wave and tile */;
-    constexpr int MY_P = T == 4 ? 5 : P, MY_M = T == 4 ? 8 : 4;
-    constexpr int TILE_BYTES = 16 * T * 64 * 16, RED_BYTES = P * 2 * 256 * 8;
-    __shared__ __attribute__((aligned(16))) char smem[TILE_BYTES > RED_BYTES ? TILE_BYTES : RED_BYTES];
-    amp_t *tile = reinterpret_cast<amp_t *>(smem);
-    double *red = reinterpret_cast<double *>(smem);
-    const int lane = threadIdx.x & 63, i = lane & 15, kk = lane >> 4;
-    const uint32_t wave_s = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // this lane's place in a wave-load: row bits (kept bits < 6) and group bits (the other lane bits)
-    uint32_t r_low = 0, f_low = 0;
-    {
-        int rb = 0, fb = 0;
-        for (int b = 0; b < 6; ++b) {
-            if ((g.lmask >> b) & 1u) r_low |= ((lane >> b) & 1u) << rb++;
-            else f_low |= ((lane >> b) & 1u) << fb++;
-        }
-    }
-    // the NL loads of this wave: load j = NL wave + jj -> c_h = j mod 2^h, block bb = j >> h (s = bb >> l, b = bb mod 2^l).
-    // Everything about a load except the lane's own row / group bits is the same for the whole wave: scalar registers.
-    const uint32_t per_tile = 1u << (g.l + g.log_s);     // consecutive w values a tile consumes
-    auto lds_slot = [&](int jj) {                         // where my amplitude of load jj goes in the tile
-        const uint32_t j = NL * wave_s + jj, c_h = j & ((1u << g.h) - 1u), bb = j >> g.h;
-        const uint32_t sblk = bb >> g.l, b = bb & ((1u << g.l) - 1u);
-        const uint32_t row = (sblk << g.k) | (c_h << g.l) | r_low, slot = (b << (6 - g.l)) | f_low;
-        return row * 64 + (slot ^ (row & 15u));
-    };
-    auto fetch = [&](amp_t (&x)[NL], uint64_t t) {
-#pragma unroll
-        for (int jj = 0; jj < NL; ++jj) {
-            const uint32_t j = NL * wave_s + jj;
-            const uint64_t w = t * per_tile + (j >> g.h);
-            const uint64_t c_off = g.hoff[j & ((1u << g.h) - 1u)];    // scalar load
-            x[jj] = __builtin_nontemporal_load(a + deposit(w << 6, g) + c_off + lane);
-        }
-    };
-    f64x4 p1[MY_P], p2[MY_P], p3[MY_P];
-#pragma unroll
-    for (int p = 0; p < MY_P; ++p) p1[p] = p2[p] = p3[p] = f64x4{0.0, 0.0, 0.0, 0.0};
-    const uint32_t shift = T == 4 ? (wave_s & 1u) : 0u;                       // row-tile rotation of this wave
-    const int m_first = MY_M * (T == 4 ? wave_s >> 1 : wave_s);
-    // operand slots of pair q (T = 4: the list A above; otherwise every pair ti <= tj in order)
-    constexpr int A_I[5] = {0, 2, 0, 2, 0}, A_J[5] = {0, 2, 1, 3, 2};
-    amp_t x[NL];
-    // tile order: with R regions, the workgroups in flight together read from R places of the register instead of one
-    // narrow window per kept-bit setting (kept bits on the top address bits: every stream would sit in the same channels)
-    const uint64_t per_region = g.regions > 1 ? g.tiles / g.regions : 0;
-    auto place = [&](uint64_t s) { return g.regions > 1 ? (s % g.regions) * per_region + s / g.regions : s; };
-    uint64_t t = blockIdx.x;
-    fetch(x, place(t));                                   // gridDim.x <= tiles: every workgroup owns at least one
-    for (; t < g.tiles; t += gridDim.x) {
-#pragma unroll
-        for (int jj = 0; jj < NL; ++jj) tile[lds_slot(jj)] = x[jj];
-        __syncthreads();
-        const uint64_t nxt = t + gridDim.x;
-        fetch(x, place(nxt < g.tiles ? nxt : blockIdx.x));   // unconditional (see k_rdm): past the end re-read and drop
-        auto step = [&](int mm) {
-            const int m = m_first + mm;
-            amp_t v[T];
-#pragma unroll
-            for (int tt = 0; tt < T; ++tt) v[tt] = tile[(16 * ((tt + shift) & (T - 1)) + i) * 64 + ((4 * m + kk) ^ i)];
-            if constexpr (T == 4) {
-#pragma unroll
-                for (int q = 0; q < MY_P; ++q) {
-                    const amp_t vi = v[A_I[q]], vj = v[A_J[q]];
-                    p1[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(vi.x, vj.x, p1[q], 0, 0, 0);
-                    p2[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(vi.y, vj.y, p2[q], 0, 0, 0);
-                    p3[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(vi.x + vi.y, vj.x - vj.y, p3[q], 0, 0, 0);
-                }
-            } else {
-                int q = 0;
-#pragma unroll
-                for (int ti = 0; ti < T; ++ti)
-#pragma unroll
-                    for (int tj = ti; tj < T; ++tj, ++q) {
-                        p1[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(v[ti].x, v[tj].x, p1[q], 0, 0, 0);
-                        p2[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(v[ti].y, v[tj].y, p2[q], 0, 0, 0);
-                        p3[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(v[ti].x + v[ti].y, v[tj].x - v[tj].y, p3[q], 0, 0, 0);
-                    }
-            }
-            // the next step's LDS reads stay behind these MFMAs: hoisted, the operands of all steps are live at once
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        if constexpr (T == 4) {       // a real loop: unrolled, the eight steps of 15 MFMAs push the allocator into spills
-#pragma unroll 1
-            for (int mm = 0; mm < MY_M; ++mm) step(mm);
-        } else {
-#pragma unroll
-            for (int mm = 0; mm < MY_M; ++mm) step(mm);
-        }
-        __syncthreads();                                  // every wave is done with the tile before it is overwritten
-    }
-    // re = P1 + P2, im = P3 - P1 + P2; deterministic sum over the waves that share a pair, one partial per workgroup.
-    // Pair index p of slot pair q: T = 4, first half (0,0) (2,2) (0,1) (2,3) (0,2) = 0 7 1 8 2; second half (1,1) (3,3)
-    // (1,2) (3,0) (1,3) = 4 9 5 3 6, where 3 = (0,3) holds the block of (3,0): its conjugate transpose.
-    for (uint32_t wv = 0; wv < 4; ++wv) {
-        if (wave_s == wv) {
-            const bool first = T == 4 ? wv < 2 : wv == 0;
-#pragma unroll
-            for (int q = 0; q < MY_P; ++q) {
-                constexpr int HALF0[5] = {0, 7, 1, 8, 2}, HALF1[5] = {4, 9, 5, 3, 6};
-                const int p = T == 4 ? (shift ? HALF1[q] : HALF0[q]) : q;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    double *slot_re = red + ((p * 2 + 0) * 4 + r) * 64 + lane;
-                    double *slot_im = red + ((p * 2 + 1) * 4 + r) * 64 + lane;
-                    *slot_re = (first ? 0.0 : *slot_re) + (p1[q][r] + p2[q][r]);
-                    *slot_im = (first ? 0.0 : *slot_im) + (p3[q][r] - p1[q][r] + p2[q][r]);
-                }
-            }
-        }
-        __syncthreads();
-    }
-    double *out = partials + static_cast<size_t>(blockIdx.x) * (P * 2 * 256);
-    for (int e = threadIdx.x; e < P * 2 * 256; e += QSV_BLOCK) out[e] = red[e];
-}
-
-// out[e] = sum over blocks of partials[block][e].  16 entries x 16 slices per workgroup: slice s adds blocks s, s+16, ...
-// in order, the 16 slice sums are added in slice order through LDS -- a fixed summation tree, so the result does not
-// depend on scheduling (one thread per entry walking every block took 0.24 ms: a chain of ~1000 dependent-latency loads).
-__global__ __launch_bounds__(QSV_BLOCK) void k_sum_partials(const double *__restrict__ partials, int blocks, int entries,
-                                                            double *__restrict__ out) {
-    __shared__ double part[16][17];
-    const int le = threadIdx.x & 15, slice = threadIdx.x >> 4;
-    const int e = blockIdx.x * 16 + le;
-    double s = 0.0;
-    if (e < entries)
-        for (int b = slice; b < blocks; b += 16) s += partials[static_cast<size_t>(b) * entries + e];
-    part[slice][le] = s;
-    __syncthreads();
-    if (slice == 0 && e < entries) {
-        double t = 0.0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) t += part[i][le];
-        out[e] = t;
-    }
-}
-
-// Small registers: one thread per entry (i, j) of rho walks every group (2^n amplitudes < 2^14: microseconds).
-__global__ __launch_bounds__(QSV_BLOCK) void k_rdm_small(const amp_t *__restrict__ a, const RdmArgs g,
-                                                         const uint64_t *__restrict__ hoff, double *__restrict__ out) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= g.D * g.D) return;
-    const int i = e / g.D, j = e % g.D;
-    double sr = 0.0, si = 0.0;
-    for (uint64_t w = 0; w < g.W; ++w) {
-        const uint64_t base = deposit(w, g);
-        const amp_t x = a[base + hoff[i]], y = a[base + hoff[j]];
-        sr += x.x * y.x + x.y * y.y;   // x conj(y)
-        si += x.y * y.x - x.x * y.y;
-    }
-    out[2 * e] = sr;
-    out[2 * e + 1] = si;
-}
-
-// <a| rho |a> for a ket `a` (2^n amplitudes) and a density matrix stored row-major as a 2n-qubit register:
-// partials[2b], [2b+1] = this block's share of sum_ij conj(a_i) rho_ij a_j.  rho is streamed once; the ket stays in L2.
-__global__ __launch_bounds__(QSV_BLOCK) void k_expect_density(const amp_t *__restrict__ ket, const amp_t *__restrict__ rho,
-                                                              uint64_t dim_bits, double *__restrict__ partials) {
-    double re = 0.0, im = 0.0;
-    const uint64_t total = 1ull << (2 * dim_bits), mask = (1ull << dim_bits) - 1;
-    for (uint64_t e = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x; e < total;
-         e += static_cast<uint64_t>(gridDim.x) * blockDim.x) {
-        const amp_t r = __builtin_nontemporal_load(rho + e);
-        const amp_t ai = ket[e >> dim_bits], aj = ket[e & mask];
-        // conj(ai) * aj
-        const double cr = ai.x * aj.x + ai.y * aj.y, ci = ai.x * aj.y - ai.y * aj.x;
-        re += cr * r.x - ci * r.y;
-        im += cr * r.y + ci * r.x;
-    }
-    block_sum2(re, im);
-    if (threadIdx.x == 0) {
-        partials[2 * blockIdx.x] = re;
-        partials[2 * blockIdx.x + 1] = im;
-    }
-}
-
 // ----------------------------------------------------------------------------------------------------
 // host-side helpers
 // ----------------------------------------------------------------------------------------------------
-int grid_for(uint64_t items, int per_block, int cap) {
-    uint64_t blocks = (items + per_block - 1) / per_block;
-    if (blocks < 1) blocks = 1;
-    if (cap > 0 && blocks > static_cast<uint64_t>(cap)) blocks = cap;
-    // an AQL dispatch counts work-ITEMS in 32 bits: at most 2^32 / 256 workgroups of 256 threads per launch
-    // (a 33-qubit register would need 2^25); every kernel launched through here loops over the remainder
-    if (blocks > 0x00ffffffull) blocks = 0x00ffffffull;
-    return static_cast<int>(blocks);
-}
-
-int check_launch() {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return qsv_fail(QSV_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return QSV_OK;
-}
-
-// Sum the first `blocks` pairs of partials on the host, in index order (deterministic).
-int sum_partials(qsv_state *st, int blocks, double *x, double *y) {
-    QSV_HIP(hipMemcpyAsync(st->partials_host, st->partials, sizeof(double) * 2 * blocks, hipMemcpyDeviceToHost,
-                           st->stream));
-    QSV_HIP(hipStreamSynchronize(st->stream));
-    double sx = 0.0, sy = 0.0;
-    for (int i = 0; i < blocks; ++i) {
-        sx += st->partials_host[2 * i];
-        sy += st->partials_host[2 * i + 1];
-    }
-    *x = sx;
-    if (y) *y = sy;
-    return QSV_OK;
-}
-
 template <int KH, int KL, int U>
 void launch_dense_nt(qsv_state *st, const GateArgs &g, int grid) {
     const bool sub = g.nins > KH || g.lane_ctrl != 0;
@@ -2144,19 +1064,6 @@ int qsvk_adopt(qsv_state *st, uint64_t new_amps) {
     return QSV_OK;
 }
 
-// A runtime bool or small int as a compile-time constant for a generic lambda: f(std::true_type / std::false_type), or
-// f(std::integral_constant<int, v>) for v in LO..HI (any other value takes HI).  What f returns is passed on.
-template <class F>
-static auto with_bool(bool v, F &&f) {
-    return v ? f(std::true_type{}) : f(std::false_type{});
-}
-template <int LO, int HI, class F>
-static auto with_int(int v, F &&f) {
-    if constexpr (LO < HI) {
-        if (v != LO) return with_int<LO + 1, HI>(v, f);
-    }
-    return f(std::integral_constant<int, LO>{});
-}
 
 // The dispatches of one launch of g.W work items, at most `limit` each: launch(count) with g.w0 set to the range's start.
 template <class Args, class Launch>
@@ -3235,10 +2142,12 @@ int qsvk_diag(qsv_state *st, int k, const int *bits, int nctrl, const int *cbits
     if (rc) return rc;
     const double *dtable = reinterpret_cast<const double *>(staged.dev);
     const uint8_t *dpos = reinterpret_cast<const uint8_t *>(staged.dev + qsv_pad16(tbytes));
-    if (st->n >= RO_MIN_QUBITS && st->readout_variant != 1) {
+    if (streaming_forms(st)) {
         snprintf(st->last_kernel, sizeof(st->last_kernel), "k_diag_table_s");
-        QSV_RO_DISPATCH(ro_fit_items(getenv("QSV_RO_ITEMS") ? ro_move_items() : 2, st->amps), hipLaunchKernelGGL((k_diag_table_s<IT>), dim3(static_cast<unsigned>(st->amps / (QSV_BLOCK * IT))), dim3(QSV_BLOCK), 0,
-                           st->stream, st->data, st->amps, K, dpos, dtable));
+        with_pow2<1, 4>(ro_fit_items(getenv("QSV_RO_ITEMS") ? ro_move_items() : 2, st->amps), [&](auto IT) {
+            hipLaunchKernelGGL(k_diag_table_s<IT.value>, dim3(static_cast<unsigned>(st->amps / (QSV_BLOCK * IT.value))), dim3(QSV_BLOCK), 0,
+                               st->stream, st->data, st->amps, K, dpos, dtable);
+        });
     } else {
         const int grid = grid_for(st->amps, QSV_BLOCK, 4096);
         snprintf(st->last_kernel, sizeof(st->last_kernel), "k_diag_table");
@@ -3269,521 +2178,6 @@ int qsvk_phase(qsv_state *st, int nctrl, const int *cbits, double re, double im)
     return launch_diag(st, g);
 }
 
-int qsvk_measure_probs(qsv_state *st, int bit, const double e0[4], const double e1[4], double *p0, double *p1) {
-    if (st->n >= RO_MIN_QUBITS && st->readout_variant != 1) {
-        const int grid = grid_for(st->amps >> (bit < QSV_LANE_BITS ? 0 : 1), QSV_BLOCK * RO_ITEMS, QSV_REDUCE_BLOCKS);
-        const cplx a{e0[0], e0[1]}, b{e0[2], e0[3]}, c{e1[0], e1[1]}, d{e1[2], e1[3]};
-        snprintf(st->last_kernel, sizeof(st->last_kernel), "k_measure_probs_s<%s>", bit < QSV_LANE_BITS ? "true" : "false");
-        if (bit < QSV_LANE_BITS)
-            hipLaunchKernelGGL(k_measure_probs_s<true>, dim3(grid), dim3(QSV_BLOCK), 0, st->stream, st->data, st->amps, bit,
-                               a, b, c, d, st->partials);
-        else
-            hipLaunchKernelGGL(k_measure_probs_s<false>, dim3(grid), dim3(QSV_BLOCK), 0, st->stream, st->data, st->amps, bit,
-                               a, b, c, d, st->partials);
-        int rc = check_launch();
-        if (rc) return rc;
-        return sum_partials(st, grid, p0, p1);
-    }
-    snprintf(st->last_kernel, sizeof(st->last_kernel), "k_measure_probs");
-    const uint64_t pairs = st->amps >> 1;
-    const int grid = grid_for(pairs, QSV_BLOCK * 8, QSV_REDUCE_BLOCKS);
-    hipLaunchKernelGGL(k_measure_probs, dim3(grid), dim3(QSV_BLOCK), 0, st->stream, st->data, pairs, bit,
-                       cplx{e0[0], e0[1]}, cplx{e0[2], e0[3]}, cplx{e1[0], e1[1]}, cplx{e1[2], e1[3]},
-                       st->partials);
-    int rc = check_launch();
-    if (rc) return rc;
-    return sum_partials(st, grid, p0, p1);
-}
-
-static int adopt(qsv_state *st, amp_t *fresh, uint64_t new_amps) {
-    (void)fresh;  // == st->spare
-    return qsvk_adopt(st, new_amps);
-}
-
-int qsvk_collapse(qsv_state *st, int bit, const double e[4], double scale) {
-    const uint64_t pairs = st->amps >> 1;
-    amp_t *fresh = nullptr;
-    int rc = qsvk_scratch(st, pairs, &fresh);
-    if (rc) return rc;
-    if (st->n >= RO_MIN_QUBITS && st->readout_variant != 1) {
-        const int items = ro_fit_items(ro_move_items(), pairs);
-        const dim3 gd(static_cast<unsigned>(pairs / (QSV_BLOCK * items))), bd(QSV_BLOCK);
-        snprintf(st->last_kernel, sizeof(st->last_kernel), "k_collapse_s<%s>", bit < QSV_LANE_BITS ? "true" : "false");
-        if (bit < QSV_LANE_BITS)
-            QSV_RO_DISPATCH(items, hipLaunchKernelGGL((k_collapse_s<true, IT>), gd, bd, 0, st->stream, st->data, fresh, pairs, bit,
-                                                      cplx{e[0], e[1]}, cplx{e[2], e[3]}, scale));
-        else
-            QSV_RO_DISPATCH(items, hipLaunchKernelGGL((k_collapse_s<false, IT>), gd, bd, 0, st->stream, st->data, fresh, pairs, bit,
-                                                      cplx{e[0], e[1]}, cplx{e[2], e[3]}, scale));
-    } else {
-        const int grid = grid_for(pairs, QSV_BLOCK * 4, 8192);
-        snprintf(st->last_kernel, sizeof(st->last_kernel), "k_collapse");
-        hipLaunchKernelGGL(k_collapse, dim3(grid), dim3(QSV_BLOCK), 0, st->stream, st->data, fresh, pairs, bit,
-                           cplx{e[0], e[1]}, cplx{e[2], e[3]}, scale);
-    }
-    rc = check_launch();
-    if (rc) return rc;
-    st->n -= 1;
-    return adopt(st, fresh, pairs);
-}
-
-int qsvk_insert(qsv_state *st, int bit, const double amp[4]) {
-    const uint64_t out_amps = st->amps << 1;
-    if (!st->owns_data && out_amps > st->capacity)
-        return qsv_fail(QSV_ENOMEM, "insert: the caller-owned buffer has no room for one more qubit");
-    amp_t *fresh = nullptr;
-    int rc = qsvk_scratch(st, out_amps, &fresh);
-    if (rc) return rc;
-    if (st->n >= RO_MIN_QUBITS && st->readout_variant != 1) {
-        const int items = ro_fit_items(ro_move_items(), st->amps);
-        const dim3 gd(static_cast<unsigned>(st->amps / (QSV_BLOCK * items))), bd(QSV_BLOCK);
-        snprintf(st->last_kernel, sizeof(st->last_kernel), "k_insert_s<%s>", bit < QSV_LANE_BITS ? "true" : "false");
-        if (bit < QSV_LANE_BITS)
-            QSV_RO_DISPATCH(items, hipLaunchKernelGGL((k_insert_s<true, IT>), gd, bd, 0, st->stream, st->data, fresh, st->amps, bit,
-                                                      cplx{amp[0], amp[1]}, cplx{amp[2], amp[3]}));
-        else
-            QSV_RO_DISPATCH(items, hipLaunchKernelGGL((k_insert_s<false, IT>), gd, bd, 0, st->stream, st->data, fresh, st->amps, bit,
-                                                      cplx{amp[0], amp[1]}, cplx{amp[2], amp[3]}));
-    } else {
-        const int grid = grid_for(out_amps, QSV_BLOCK * 4, 8192);
-        snprintf(st->last_kernel, sizeof(st->last_kernel), "k_insert");
-        hipLaunchKernelGGL(k_insert, dim3(grid), dim3(QSV_BLOCK), 0, st->stream, st->data, fresh, out_amps, bit,
-                           cplx{amp[0], amp[1]}, cplx{amp[2], amp[3]});
-    }
-    rc = check_launch();
-    if (rc) return rc;
-    st->n += 1;
-    return adopt(st, fresh, out_amps);
-}
-
-int qsvk_permute(qsv_state *st, const int *src_bit_of_dst_bit) {
-    PermArgs g;
-    std::memset(&g, 0, sizeof(g));
-    g.n = st->n;
-    for (int b = 0; b < st->n; ++b) g.src_bit[b] = static_cast<uint8_t>(src_bit_of_dst_bit[b]);
-    amp_t *fresh = nullptr;
-    int rc = qsvk_scratch(st, st->amps, &fresh);
-    if (rc) return rc;
-    if (st->n >= RO_MIN_QUBITS && st->readout_variant != 1) {
-        // the tile: destination bits 0..2, the destinations of source bits 0..2, then the lowest other bits up to six
-        PermTileArgs t;
-        std::memset(&t, 0, sizeof(t));
-        t.tiles = st->amps >> 6;
-        t.bytes = (st->n + 7) / 8;
-        std::vector<int> tile = {0, 1, 2};
-        for (int j = 3; j < st->n; ++j)
-            if (src_bit_of_dst_bit[j] < 3) tile.push_back(j);
-        for (int j = 3; j < st->n && tile.size() < 6; ++j)
-            if (std::find(tile.begin(), tile.end(), j) == tile.end()) tile.push_back(j);
-        std::sort(tile.begin(), tile.end());
-        for (int k = 0; k < 6; ++k) {
-            t.tile_dst[k] = static_cast<uint8_t>(tile[k]);
-            t.tile_src[k] = static_cast<uint8_t>(src_bit_of_dst_bit[tile[k]]);
-        }
-        // lut[b][v]: where the destination-index bits 8b .. 8b+7 (value v) come from in the source index
-        std::vector<uint64_t> lut(static_cast<size_t>(t.bytes) * 256, 0);
-        for (int b = 0; b < t.bytes; ++b)
-            for (int v = 0; v < 256; ++v)
-                for (int i = 0; i < 8 && 8 * b + i < st->n; ++i)
-                    if ((v >> i) & 1) lut[b * 256 + v] |= 1ull << src_bit_of_dst_bit[8 * b + i];
-        rc = qsvk_ensure_matrix(st, sizeof(uint64_t) * lut.size());
-        if (rc) return rc;
-        QSV_HIP(hipMemcpyAsync(st->dev_matrix, lut.data(), sizeof(uint64_t) * lut.size(), hipMemcpyHostToDevice, st->stream));
-        QSV_HIP(hipStreamSynchronize(st->stream));  // `lut` dies at return
-        const int items = ro_move_items();
-        const int grid = grid_for(t.tiles, (QSV_BLOCK / 64) * items, 1 << 22);
-        snprintf(st->last_kernel, sizeof(st->last_kernel), "k_permute_s");
-        QSV_RO_DISPATCH(items, hipLaunchKernelGGL((k_permute_s<IT>), dim3(grid), dim3(QSV_BLOCK), 0, st->stream, st->data, fresh, t,
-                                                  reinterpret_cast<const uint64_t *>(st->dev_matrix)));
-    } else {
-        const int grid = grid_for(st->amps, QSV_BLOCK * 4, 8192);
-        snprintf(st->last_kernel, sizeof(st->last_kernel), "k_permute");
-        hipLaunchKernelGGL(k_permute, dim3(grid), dim3(QSV_BLOCK), 0, st->stream, st->data, fresh, st->amps, g);
-    }
-    rc = check_launch();
-    if (rc) return rc;
-    return adopt(st, fresh, st->amps);
-}
-
-int qsvk_norm2(qsv_state *st, double *out) {
-    const int grid = grid_for(st->amps, QSV_BLOCK * 8, QSV_REDUCE_BLOCKS);
-    hipLaunchKernelGGL(k_norm2, dim3(grid), dim3(QSV_BLOCK), 0, st->stream, st->data, st->amps, st->partials);
-    int rc = check_launch();
-    if (rc) return rc;
-    return sum_partials(st, grid, out, nullptr);
-}
-
-int qsvk_inner(qsv_state *a, qsv_state *b, double *re, double *im) {
-    QSV_HIP(hipStreamSynchronize(b->stream));
-    const int grid = grid_for(a->amps, QSV_BLOCK * 8, QSV_REDUCE_BLOCKS);
-    hipLaunchKernelGGL(k_inner, dim3(grid), dim3(QSV_BLOCK), 0, a->stream, a->data, b->data, a->amps, a->partials);
-    int rc = check_launch();
-    if (rc) return rc;
-    return sum_partials(a, grid, re, im);
-}
-
-
-// rho_out: 4^k complex, row-major, row / column index bit (k-1-j) <-> bits[j] (bits[0] = most significant leg).
-int qsvk_reduced_density(qsv_state *st, int k, const int *bits, double *rho_out) {
-    if (k < 1 || k > QSV_MAX_K || k > st->n) return qsv_fail(QSV_EINVAL, "reduced density matrix: keep 1..6 qubits");
-    const int D = 1 << k;
-    std::vector<int> sorted(bits, bits + k);
-    std::sort(sorted.begin(), sorted.end());
-    const int T = D <= 16 ? 1 : D <= 32 ? 2 : 4, P = T * (T + 1) / 2;
-    std::vector<uint64_t> off(16 * T, 0);
-    for (int r = 0; r < D; ++r)
-        for (int i = 0; i < k; ++i)
-            if ((r >> i) & 1) off[r] |= 1ull << sorted[i];
-    RdmArgs g;
-    std::memset(&g, 0, sizeof(g));
-    g.W = st->amps >> k;
-    g.nins = k;
-    g.D = D;
-    for (int i = 0; i < k; ++i) g.pos[i] = static_cast<uint32_t>(sorted[i]);
-    const int S = D < 16 ? 16 / D : 1;                   // groups sharing a 16-row tile (k_rdm)
-    const bool old_form = st->readout_variant == 2;      // round 2's per-lane row loads (measurement variant)
-    const bool big = st->n >= RO_MIN_QUBITS && (old_form ? g.W % (4ull * S * 4 * (RDM_LOADS / T)) == 0   // whole iterations
-                                                         : g.W % (64ull * S) == 0 && g.W >= 64ull * S);   // whole tiles
-    RdmTileArgs gt;
-    std::memset(&gt, 0, sizeof(gt));
-    if (big && !old_form) {
-        gt.k = k;
-        for (int i = 0; i < k; ++i) {
-            if (sorted[i] < 6) {
-                gt.lmask |= 1u << sorted[i];
-                ++gt.l;
-            } else {
-                gt.pos[gt.h++] = static_cast<uint32_t>(sorted[i]);
-            }
-        }
-        gt.nins = gt.h;
-        gt.log_s = S == 1 ? 0 : S == 2 ? 1 : S == 4 ? 2 : 3;
-        gt.tiles = g.W / (64ull * S);
-        for (int c = 0; c < (1 << gt.h); ++c)
-            for (int j = 0; j < gt.h; ++j)
-                if ((c >> j) & 1) gt.hoff[c] |= 1ull << gt.pos[j];
-        // 8 regions where a kept bit sits on the high address bits (k <= 4 on bits 24..27: 1.14 -> 0.82 ms at n = 28) and
-        // for 64-row tiles; plain order otherwise (within 5 % either way: profiles/r03_rdm.txt)
-        const uint32_t want = st->remap >= 0 ? static_cast<uint32_t>(st->remap) : ((sorted.back() >= 20 || k == 6) ? 8u : 0u);
-        gt.regions = want > 1 && gt.tiles % want == 0 ? want : 0;
-    }
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, st->device);  // 256 if the query fails
-    // a power-of-two grid, so that (waves in the grid) x RDM_U divides the (power-of-two) number of steps
-    int blocks = 0;
-    if (big && old_form) {
-        const uint64_t most = std::min<uint64_t>((T <= 2 ? 4ull : 2ull) * cus, std::max<uint64_t>(1, g.W / (4ull * S) / (4 * (RDM_LOADS / T))));
-        blocks = 1;
-        while (2ull * blocks <= most) blocks *= 2;
-    } else if (big) {   // persistent workgroups, as many as the LDS tiles (16 T KiB) and the accumulators let a CU hold
-        blocks = static_cast<int>(std::min<uint64_t>(gt.tiles, static_cast<uint64_t>(T == 4 ? 2 : T == 2 ? 4 : 8) * cus));
-    }
-    const int entries = big ? P * 2 * 256 : 2 * D * D;
-    const size_t b_off = sizeof(uint64_t) * off.size(), b_out = sizeof(double) * entries,
-                 b_part = sizeof(double) * static_cast<size_t>(blocks) * entries;
-    int rc = qsvk_ensure_matrix(st, b_off + b_out + b_part + 64);
-    if (rc) return rc;
-    char *p = reinterpret_cast<char *>(st->dev_matrix);
-    uint64_t *d_off = reinterpret_cast<uint64_t *>(p);
-    double *d_out = reinterpret_cast<double *>(p + b_off), *d_part = reinterpret_cast<double *>(p + b_off + b_out);
-    if (!(big && !old_form)) QSV_HIP(hipMemcpyAsync(d_off, off.data(), b_off, hipMemcpyHostToDevice, st->stream));
-    std::vector<double> raw(entries);
-    if (big && !old_form) {
-        snprintf(st->last_kernel, sizeof(st->last_kernel), "k_rdm_tile<%d>", T);
-        if (T == 1) hipLaunchKernelGGL(k_rdm_tile<1>, dim3(blocks), dim3(QSV_BLOCK), 0, st->stream, st->data, gt, d_part);
-        else if (T == 2) hipLaunchKernelGGL(k_rdm_tile<2>, dim3(blocks), dim3(QSV_BLOCK), 0, st->stream, st->data, gt, d_part);
-        else hipLaunchKernelGGL(k_rdm_tile<4>, dim3(blocks), dim3(QSV_BLOCK), 0, st->stream, st->data, gt, d_part);
-        rc = check_launch();
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_sum_partials, dim3((entries + 15) / 16), dim3(QSV_BLOCK), 0, st->stream, d_part,
-                           blocks, entries, d_out);
-    } else if (big) {
-        snprintf(st->last_kernel, sizeof(st->last_kernel), "k_rdm<%d>", T);
-        if (T == 1) hipLaunchKernelGGL(k_rdm<1>, dim3(blocks), dim3(QSV_BLOCK), 0, st->stream, st->data, g, d_off, d_part);
-        else if (T == 2) hipLaunchKernelGGL(k_rdm<2>, dim3(blocks), dim3(QSV_BLOCK), 0, st->stream, st->data, g, d_off, d_part);
-        else hipLaunchKernelGGL(k_rdm<4>, dim3(blocks), dim3(QSV_BLOCK), 0, st->stream, st->data, g, d_off, d_part);
-        rc = check_launch();
-        if (rc) {
-            (void)hipStreamSynchronize(st->stream);   // the offsets' upload reads a local vector
-            return rc;
-        }
-        hipLaunchKernelGGL(k_sum_partials, dim3((entries + 15) / 16), dim3(QSV_BLOCK), 0, st->stream, d_part,
-                           blocks, entries, d_out);
-    } else {
-        snprintf(st->last_kernel, sizeof(st->last_kernel), "k_rdm_small");
-        hipLaunchKernelGGL(k_rdm_small, dim3((D * D + QSV_BLOCK - 1) / QSV_BLOCK), dim3(QSV_BLOCK), 0, st->stream, st->data, g,
-                           d_off, d_out);
-    }
-    rc = check_launch();
-    if (rc) {
-        (void)hipStreamSynchronize(st->stream);
-        return rc;
-    }
-    QSV_HIP(hipMemcpyAsync(raw.data(), d_out, b_out, hipMemcpyDeviceToHost, st->stream));
-    QSV_HIP(hipStreamSynchronize(st->stream));
-    // kernel order (row bit i <-> sorted[i]) -> caller order (bit k-1-j <-> bits[j])
-    const std::vector<int> ui = user_index(k, bits, sorted.data());
-    for (int r = 0; r < D; ++r)
-        for (int c = 0; c < D; ++c) {
-            double vr, vi;
-            if (big) {
-                // tile pair p = (ti <= tj); D layout: col = lane & 15, row = (lane >> 4) + 4 reg.  Entries below the
-                // diagonal are the conjugates of those above it and the diagonal is real, exactly (the matrix cores
-                // sum the two mirror entries of a diagonal tile in different orders: equal up to rounding only)
-                const bool upper = r <= c;
-                const int rr = upper ? r : c, cc = upper ? c : r;
-                const int ti = rr / 16, tj = cc / 16;
-                // k_rdm_tile<4> holds pair (0, 3) as the block of (3, 0): read it mirrored, imaginary part negated
-                const bool mirrored = !old_form && T == 4 && ti == 0 && tj == 3;
-                int pidx = 0;
-                for (int a = 0; a < ti; ++a) pidx += T - a;
-                pidx += tj - ti;
-                vr = vi = 0.0;
-                for (int sgrp = 0; sgrp < S; ++sgrp) {   // 2^k < 16: the diagonal blocks of the shared tile add up
-                    int row = rr % 16 + D * sgrp * (D < 16), col = cc % 16 + D * sgrp * (D < 16);
-                    if (mirrored) std::swap(row, col);
-                    const int reg = row / 4, lane = (row % 4) * 16 + col;
-                    vr += raw[((pidx * 2 + 0) * 4 + reg) * 64 + lane];
-                    vi += (mirrored ? -1.0 : 1.0) * raw[((pidx * 2 + 1) * 4 + reg) * 64 + lane];
-                }
-                if (!upper) vi = -vi;  // rho[r][c] = conj(rho[c][r])
-                if (r == c) vi = 0.0;
-            } else {
-                vr = raw[2 * (r * D + c)];
-                vi = raw[2 * (r * D + c) + 1];
-            }
-            const int ur = ui[r], uc = ui[c];
-            rho_out[2 * (ur * D + uc)] = vr;
-            rho_out[2 * (ur * D + uc) + 1] = vi;
-        }
-    return QSV_OK;
-}
-
-int qsvk_expect_density(qsv_state *ket, qsv_state *rho, double *re, double *im) {
-    QSV_HIP(hipStreamSynchronize(ket->stream));
-    const int grid = grid_for(rho->amps, QSV_BLOCK * 8, QSV_REDUCE_BLOCKS);
-    hipLaunchKernelGGL(k_expect_density, dim3(grid), dim3(QSV_BLOCK), 0, rho->stream, ket->data, rho->data,
-                       static_cast<uint64_t>(ket->n), rho->partials);
-    int rc = check_launch();
-    if (rc) return rc;
-    return sum_partials(rho, grid, re, im);
-}
-
-int qsvk_expect_pauli(qsv_state *st, uint64_t xmask, uint64_t zmask, int n_y, double *re, double *im) {
-    const int grid = grid_for(st->amps, QSV_BLOCK * 8, QSV_REDUCE_BLOCKS);
-    hipLaunchKernelGGL(k_expect_pauli, dim3(grid), dim3(QSV_BLOCK), 0, st->stream, st->data, st->amps, xmask, zmask,
-                       st->partials);
-    int rc = check_launch();
-    if (rc) return rc;
-    double sr = 0.0, si = 0.0;
-    rc = sum_partials(st, grid, &sr, &si);
-    if (rc) return rc;
-    switch (n_y & 3) {  // times i^{nY}
-        case 0: *re = sr; *im = si; break;
-        case 1: *re = -si; *im = sr; break;
-        case 2: *re = -sr; *im = -si; break;
-        default: *re = si; *im = -sr; break;
-    }
-    return QSV_OK;
-}
-
-// values[p.index[t]] = <psi|P|psi> of every term of every pass.  The launches go out back to back on the register's
-// stream, each with its own slice of the scratch buffer (one partial per workgroup and term); one copy and one
-// synchronisation at the end, then the host sums each term's partials in index order (deterministic).
-int qsvk_expect_pauli_groups(qsv_state *st, const std::vector<qsv_pauli_plan::Pass> &passes, double *values) {
-    if (passes.empty()) return QSV_OK;
-    struct Slice { size_t offset; int grid, width; };
-    std::vector<Slice> slices;
-    size_t doubles = 0;
-    for (const qsv_pauli_plan::Pass &p : passes) {
-        const int count = static_cast<int>(p.zmask.size());
-        if (count < 1 || count > qsv_pauli_plan::PAULI_TERMS_PER_PASS) return qsv_fail(QSV_EINVAL, "bad Pauli pass");
-        const uint64_t items = p.pivot < 0 ? st->amps : st->amps / 2;
-        const int grid = grid_for(items, QSV_BLOCK * 2 * PAULI_ITEMS, QSV_REDUCE_BLOCKS);
-        const int width = count <= 1 ? 1 : count <= 2 ? 2 : count <= 4 ? 4 : 8;
-        slices.push_back({doubles, grid, width});
-        doubles += static_cast<size_t>(grid) * width;
-    }
-    int rc = qsvk_ensure_matrix(st, sizeof(double) * doubles);
-    if (rc) return rc;
-    for (size_t k = 0; k < passes.size(); ++k) {
-        const qsv_pauli_plan::Pass &p = passes[k];
-        PauliPassArgs g;
-        std::memset(&g, 0, sizeof(g));
-        g.items = p.pivot < 0 ? st->amps : st->amps / 2;
-        g.xmask = p.xmask;
-        g.pivot = p.pivot < 0 ? 0 : p.pivot;
-        for (size_t t = 0; t < p.zmask.size(); ++t) {
-            g.zmask[t] = p.zmask[t];
-            if (p.n_y[t] & 1) g.odd |= 1u << t;
-        }
-        double *out = st->dev_matrix + slices[k].offset;
-        const dim3 gd(slices[k].grid), bd(QSV_BLOCK);
-#define QSV_PAULI_LAUNCH(W)                                                                                       \
-    do {                                                                                                          \
-        if (p.pivot < 0) hipLaunchKernelGGL((k_expect_pauli_group<W, true>), gd, bd, 0, st->stream, st->data, g, out);   \
-        else hipLaunchKernelGGL((k_expect_pauli_group<W, false>), gd, bd, 0, st->stream, st->data, g, out);       \
-    } while (0)
-        switch (slices[k].width) {
-            case 1: QSV_PAULI_LAUNCH(1); break;
-            case 2: QSV_PAULI_LAUNCH(2); break;
-            case 4: QSV_PAULI_LAUNCH(4); break;
-            default: QSV_PAULI_LAUNCH(8); break;
-        }
-#undef QSV_PAULI_LAUNCH
-        rc = check_launch();
-        if (rc) {
-            (void)hipStreamSynchronize(st->stream);
-            return rc;
-        }
-    }
-    std::vector<double> host(doubles);
-    QSV_HIP(hipMemcpyAsync(host.data(), st->dev_matrix, sizeof(double) * doubles, hipMemcpyDeviceToHost, st->stream));
-    QSV_HIP(hipStreamSynchronize(st->stream));
-    for (size_t k = 0; k < passes.size(); ++k) {
-        const qsv_pauli_plan::Pass &p = passes[k];
-        const Slice &s = slices[k];
-        for (size_t t = 0; t < p.zmask.size(); ++t) {
-            double sum = 0.0;
-            for (int b = 0; b < s.grid; ++b) sum += host[s.offset + static_cast<size_t>(b) * s.width + t];
-            values[p.index[t]] = qsv_pauli_plan::pair_scale(p.pivot, p.n_y[t]) * sum;
-        }
-    }
-    return QSV_OK;
-}
-
-// Every pass of a qsv_apply_pauli_rotations plan, back to back on the register's stream with no host synchronisation.
-// cs / sn: cos(theta/2) and sin(theta/2) of every term, indexed as the caller's list.
-int qsvk_pauli_rotate_passes(qsv_state *st, const std::vector<qsv_pauli_rotation_plan::Pass> &passes, const double *cs,
-                             const double *sn) {
-    constexpr int CAP = qsv_pauli_rotation_plan::ROTATIONS_PER_PASS;
-    for (const qsv_pauli_rotation_plan::Pass &p : passes) {
-        const int count = static_cast<int>(p.index.size());
-        if (count < 1 || count > CAP || p.pivot >= st->n || (p.pivot < 0) != (p.xmask == 0) || p.xmask >= st->amps)
-            return qsv_fail(QSV_EINVAL, "bad Pauli rotation pass");
-        PauliRotateArgs g;
-        std::memset(&g, 0, sizeof(g));
-        g.items = p.pivot < 0 ? st->amps : st->amps / 2;
-        g.xmask = p.xmask;
-        g.pivot = p.pivot < 0 ? 0 : p.pivot;
-        for (int t = 0; t < CAP; ++t) {
-            const bool used = t < count;
-            g.zmask[t] = used ? p.zmask[t] : 0;
-            g.cs[t] = used ? cs[p.index[t]] : 1.0;
-            g.sn[t] = used ? sn[p.index[t]] : 0.0;
-            if (!used || p.term_xmask[t] == 0) g.diag |= 1u << t;
-            else g.rot |= static_cast<uint32_t>(p.n_y[t] & 3) << (2 * t);
-        }
-        const int width = count <= 1 ? 1 : count <= 2 ? 2 : count <= 4 ? 4 : 8;
-        // a pivot inside a 128-byte line: both halves of a line are written by one launch, let them meet in L2
-        const bool nt = st->nontemporal && (p.pivot < 0 || p.pivot >= 3);
-        const dim3 gd(grid_for(g.items, QSV_BLOCK, st->grid_cap)), bd(QSV_BLOCK);
-#define QSV_ROTATE_LAUNCH(W, D)                                                                                    \
-    do {                                                                                                           \
-        if (nt) hipLaunchKernelGGL((k_pauli_rotate_group<W, D, true>), gd, bd, 0, st->stream, st->data, g);        \
-        else hipLaunchKernelGGL((k_pauli_rotate_group<W, D, false>), gd, bd, 0, st->stream, st->data, g);          \
-    } while (0)
-#define QSV_ROTATE_WIDTH(W)                     \
-    do {                                        \
-        if (p.pivot < 0) QSV_ROTATE_LAUNCH(W, true); \
-        else QSV_ROTATE_LAUNCH(W, false);       \
-    } while (0)
-        switch (width) {
-            case 1: QSV_ROTATE_WIDTH(1); break;
-            case 2: QSV_ROTATE_WIDTH(2); break;
-            case 4: QSV_ROTATE_WIDTH(4); break;
-            default: QSV_ROTATE_WIDTH(8); break;
-        }
-#undef QSV_ROTATE_WIDTH
-#undef QSV_ROTATE_LAUNCH
-        snprintf(st->last_kernel, sizeof(st->last_kernel), "k_pauli_rotate_group<%d, %s, %s>", width, p.pivot < 0 ? "true" : "false",
-                 nt ? "true" : "false");
-        const int rc = check_launch();
-        if (rc) return rc;
-    }
-    return QSV_OK;
-}
-
-// Inverse-CDF sampling of basis states: out[s] = smallest index i with sum_{j <= i} |amp_j|^2 > u[s] * total.
-int qsvk_sample(qsv_state *st, int shots, const double *u, uint64_t *out) {
-    const uint64_t chunks = (st->amps + SAMPLE_CHUNK - 1) / SAMPLE_CHUNK;
-    const size_t sums_bytes = sizeof(double) * chunks, shot_bytes = sizeof(uint64_t) * shots;
-    int rc = qsvk_ensure_matrix(st, sums_bytes + 3 * shot_bytes + 64);
-    if (rc) return rc;
-    char *base = reinterpret_cast<char *>(st->dev_matrix);
-    double *d_sums = reinterpret_cast<double *>(base);
-    uint64_t *d_chunk = reinterpret_cast<uint64_t *>(base + (sums_bytes + 15) / 16 * 16);
-    double *d_resid = reinterpret_cast<double *>(d_chunk + shots);
-    uint64_t *d_out = reinterpret_cast<uint64_t *>(d_resid + shots);
-    hipLaunchKernelGGL(k_chunk_sums, dim3(grid_for(chunks, 1, 1 << 16)), dim3(QSV_BLOCK), 0, st->stream, st->data,
-                       st->amps, d_sums);
-    rc = check_launch();
-    if (rc) return rc;
-    std::vector<double> sums(chunks);
-    QSV_HIP(hipMemcpyAsync(sums.data(), d_sums, sums_bytes, hipMemcpyDeviceToHost, st->stream));
-    QSV_HIP(hipStreamSynchronize(st->stream));
-    std::vector<double> cum(chunks + 1, 0.0);
-    for (uint64_t c = 0; c < chunks; ++c) cum[c + 1] = cum[c] + sums[c];
-    const double total = cum[chunks];
-    if (!(total > 0.0)) return qsv_fail(QSV_EINVAL, "cannot sample from a register of zero norm");
-    std::vector<uint64_t> chunk(shots);
-    std::vector<double> resid(shots);
-    for (int s = 0; s < shots; ++s) {
-        if (!(u[s] >= 0.0 && u[s] < 1.0)) return qsv_fail(QSV_EINVAL, "uniform draws must lie in [0, 1)");
-        const double target = u[s] * total;
-        uint64_t c = std::upper_bound(cum.begin(), cum.end(), target) - cum.begin();  // first cum > target
-        c = c == 0 ? 0 : c - 1;
-        while (c + 1 < chunks && sums[c] == 0.0) ++c;  // never land in an empty chunk
-        if (c >= chunks) c = chunks - 1;
-        chunk[s] = c;
-        resid[s] = target - cum[c];
-    }
-    QSV_HIP(hipMemcpyAsync(d_chunk, chunk.data(), shot_bytes, hipMemcpyHostToDevice, st->stream));
-    QSV_HIP(hipMemcpyAsync(d_resid, resid.data(), sizeof(double) * shots, hipMemcpyHostToDevice, st->stream));
-    hipLaunchKernelGGL(k_sample_in_chunk, dim3(shots), dim3(QSV_BLOCK), 0, st->stream, st->data, st->amps, d_chunk,
-                       d_resid, d_out);
-    rc = check_launch();
-    if (rc) return rc;
-    QSV_HIP(hipMemcpyAsync(out, d_out, shot_bytes, hipMemcpyDeviceToHost, st->stream));
-    QSV_HIP(hipStreamSynchronize(st->stream));  // also covers the two pageable uploads above
-    return QSV_OK;
-}
-
-int qsvk_probabilities(qsv_state *st, const uint64_t *indices, int count, double *out) {
-    if (count <= 0) return QSV_OK;
-    const size_t ibytes = sizeof(uint64_t) * count, obytes = sizeof(double) * count;
-    int rc = qsvk_ensure_matrix(st, ibytes + obytes);
-    if (rc) return rc;
-    uint64_t *didx = reinterpret_cast<uint64_t *>(st->dev_matrix);
-    double *dout = reinterpret_cast<double *>(reinterpret_cast<char *>(st->dev_matrix) + ibytes);
-    QSV_HIP(hipMemcpyAsync(didx, indices, ibytes, hipMemcpyHostToDevice, st->stream));
-    hipLaunchKernelGGL(k_gather_prob, dim3((count + 255) / 256), dim3(256), 0, st->stream, st->data, didx, count,
-                       dout);
-    rc = check_launch();
-    if (rc) return rc;
-    QSV_HIP(hipMemcpyAsync(out, dout, obytes, hipMemcpyDeviceToHost, st->stream));
-    QSV_HIP(hipStreamSynchronize(st->stream));
-    return QSV_OK;
-}
-
-int qsvk_fill_random(qsv_state *st, uint64_t seed, uint64_t index_offset, double *norm2) {
-    const int grid = grid_for(st->amps, QSV_BLOCK * 8, QSV_REDUCE_BLOCKS);
-    hipLaunchKernelGGL(k_fill_random, dim3(grid), dim3(QSV_BLOCK), 0, st->stream, st->data, st->amps, seed,
-                       index_offset, st->partials);
-    int rc = check_launch();
-    if (rc) return rc;
-    double s = 0.0;
-    rc = sum_partials(st, grid, &s, nullptr);
-    if (norm2) *norm2 = s;
-    return rc;
-}
-
-int qsvk_scale(qsv_state *st, double re, double im) {
-    const int grid = grid_for(st->amps, QSV_BLOCK * 8, 8192);
-    hipLaunchKernelGGL(k_scale, dim3(grid), dim3(QSV_BLOCK), 0, st->stream, st->data, st->amps, cplx{re, im});
-    return check_launch();
-}
-
 int qsvk_copy(amp_t *dst, const amp_t *src, uint64_t amps, hipStream_t stream) {
     static const int mode = [] { const char *e = getenv("QSV_COPY_MODE"); return e ? atoi(e) : 1; }();
     static const int regions = [] { const char *e = getenv("QSV_COPY_REGIONS"); return e ? atoi(e) : 0; }();
@@ -3801,11 +2195,5 @@ int qsvk_copy(amp_t *dst, const amp_t *src, uint64_t amps, hipStream_t stream) {
         hipError_t e = hipMemcpyAsync(dst + bulk, src + bulk, sizeof(amp_t) * (amps - bulk), hipMemcpyDeviceToDevice, stream);
         if (e != hipSuccess) return qsv_fail(QSV_EHIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
     }
-    return check_launch();
-}
-
-int qsvk_set_basis(qsv_state *st, uint64_t index) {
-    const int grid = grid_for(st->amps, QSV_BLOCK * 8, 8192);
-    hipLaunchKernelGGL(k_zero, dim3(grid), dim3(QSV_BLOCK), 0, st->stream, st->data, st->amps, index);
     return check_launch();
 }

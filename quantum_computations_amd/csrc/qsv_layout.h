@@ -1,5 +1,5 @@
 // Host-side layouts of the dense-gate launchers (qsv_kernels.hip): plain C++, no HIP, so that the host tests can compile
-// it alone (tests/test_layout_host.py).
+// it alone (tests/test_layout_host.py).  The read-out and Pauli launchers have qsv_readout_layout.h.
 //
 // A launcher chooses a kernel form, asks this header for the tables of that form, stages them, fills the kernel's argument
 // struct and launches over the dispatch ranges.  Everything here is integer and index arithmetic on three index spaces:

@@ -1,4 +1,5 @@
-// TEST INFRASTRUCTURE: prints what qsv_layout.h computes for requests read from stdin (tests/test_layout_host.py).
+// TEST INFRASTRUCTURE: prints what qsv_layout.h and qsv_readout_layout.h compute for requests read from stdin
+// (tests/test_layout_host.py, tests/test_readout_layout_host.py).
 //
 // One request per input line, one answer line per request; numbers are decimal integers, doubles are printed as %a.
 //   split n k bits..                         -> enough KB | high.. | low.. | standin..
@@ -16,15 +17,29 @@
 //   form n k real variant complex_product mtile bits..  -> form transposed realm m3
 //   pass n tile_high count {kind k b0 b1 nctrl cbits.. m[0..32)}..
 //                                            -> status | tile_bits.. | groups {first count q0..q3 gates}.. | {form code rc tc tz0 tz1 omask m[0..32)}..
+// qsv_readout_layout.h:
+//   permute n src_bit_of_dst_bit..           -> tiles bytes | tile_dst[0..6) | tile_src[0..6) | lut[0 .. 256 bytes)
+//   rdm n amps k variant remap cus bits..    -> big old_form T P S blocks entries | sorted.. | off[0 .. 16 T) |
+//                                               W nins D pos[0..8) | tiles nins k l h lmask log_s regions pos[0..8) | hoff[0..64)
+//   rdmunpack n amps k variant remap cus bits.. raw[0 .. entries)  -> rho_out[0 .. 2 D D)
+//   sample chunks shots sums.. u..           -> status total | chunk.. | resid..
+//   paulisum n terms {xmask zmask}..         -> per pass of qsv_pauli_plan::plan: ok width items xmask pivot odd zmask[0..8) |
+//   passraw n xmask pivot count {zmask n_y}..  -> ok width            (a pass as given, well-formed or not)
+//   paulirot n terms {xmask zmask cs sn}..   -> per pass of qsv_pauli_rotation_plan::plan:
+//                                               ok width items xmask pivot diag rot zmask[0..8) cs[0..8) sn[0..8) |
+//   rotraw n xmask pivot count {term_xmask zmask n_y}..  -> ok width  (index = 0 .. count-1, cs = 0.5, sn = 0.25)
 #include <cstdio>
+#include <cstdlib>
 #include <iostream>
 #include <sstream>
 #include <string>
 #include <vector>
 
 #include "qsv_layout.h"
+#include "qsv_readout_layout.h"
 
 using namespace qsv_layout;
+using namespace qsv_readout_layout;
 
 static std::vector<int> ints(std::istream &in, int count) {
     std::vector<int> v(count > 0 ? count : 0);
@@ -42,6 +57,20 @@ static void put_ints(const V &v) {
 }
 static void put_doubles(const double *m, size_t count) {
     for (size_t i = 0; i < count; ++i) std::printf(" %a", m[i]);
+}
+static unsigned long long u64(std::istream &in) {
+    unsigned long long v = 0;
+    in >> v;
+    return v;
+}
+static RdmPlan read_rdm_plan(std::istream &in, std::vector<int> &bits) {
+    int n, k, variant, remap, cus;
+    in >> n;
+    const unsigned long long amps = u64(in);
+    in >> k >> variant >> remap >> cus;
+    if (k < 1 || k > MAX_K || k > n) std::exit(3);
+    bits = ints(in, k);
+    return rdm_plan(n, amps, k, bits.data(), variant, remap, cus);
 }
 
 int main() {
@@ -184,6 +213,108 @@ int main() {
                     put_doubles(g.m, 32);
                 }
             }
+        } else if (what == "permute") {
+            int n;
+            in >> n;
+            const std::vector<int> order = ints(in, n);
+            const PermTile t = permute_tile(n, order.data());
+            std::printf("%llu %d |", static_cast<unsigned long long>(t.args.tiles), t.args.bytes);
+            put_ints(std::vector<int>(t.args.tile_dst, t.args.tile_dst + 6));
+            std::printf(" |");
+            put_ints(std::vector<int>(t.args.tile_src, t.args.tile_src + 6));
+            std::printf(" |");
+            put_ints(t.lut);
+        } else if (what == "rdm") {
+            std::vector<int> bits;
+            const RdmPlan p = read_rdm_plan(in, bits);
+            std::printf("%d %d %d %d %d %d %d |", p.big ? 1 : 0, p.old_form ? 1 : 0, p.T, p.P, p.S, p.blocks, p.entries);
+            put_ints(p.sorted);
+            std::printf(" |");
+            put_ints(p.off);
+            std::printf(" | %llu %d %d", static_cast<unsigned long long>(p.g.W), p.g.nins, p.g.D);
+            put_ints(std::vector<uint32_t>(p.g.pos, p.g.pos + 8));
+            std::printf(" | %llu %d %d %d %d %u %d %u", static_cast<unsigned long long>(p.gt.tiles), p.gt.nins, p.gt.k, p.gt.l, p.gt.h,
+                        p.gt.lmask, p.gt.log_s, p.gt.regions);
+            put_ints(std::vector<uint32_t>(p.gt.pos, p.gt.pos + 8));
+            std::printf(" |");
+            put_ints(std::vector<uint64_t>(p.gt.hoff, p.gt.hoff + 64));
+        } else if (what == "rdmunpack") {
+            std::vector<int> bits;
+            const RdmPlan p = read_rdm_plan(in, bits);
+            const std::vector<double> raw = doubles(in, p.entries);
+            std::vector<double> rho(2ull * p.D * p.D);
+            rdm_unpack(p, bits.data(), raw.data(), rho.data());
+            put_doubles(rho.data(), rho.size());
+        } else if (what == "sample") {
+            int chunks, shots;
+            in >> chunks >> shots;
+            const std::vector<double> sums = doubles(in, chunks), u = doubles(in, shots);
+            const SampleChunks c = sample_chunks(sums, u.data(), shots);
+            std::printf("%d %a |", static_cast<int>(c.status), c.total);
+            if (c.status == SampleChunks::OK) {
+                put_ints(c.chunk);
+                std::printf(" |");
+                put_doubles(c.resid.data(), c.resid.size());
+            }
+        } else if (what == "paulisum") {
+            int n, count;
+            in >> n >> count;
+            std::vector<qsv_pauli_plan::Term> terms(count);
+            for (auto &t : terms) t.xmask = u64(in), t.zmask = u64(in);
+            for (const qsv_pauli_plan::Pass &pass : qsv_pauli_plan::plan(terms)) {
+                const PauliPass a = pauli_pass_args(pass, 1ull << n);
+                std::printf(" %d %d %llu %llu %d %u", a.ok ? 1 : 0, a.width, static_cast<unsigned long long>(a.g.items),
+                            static_cast<unsigned long long>(a.g.xmask), a.g.pivot, a.g.odd);
+                put_ints(std::vector<uint64_t>(a.g.zmask, a.g.zmask + qsv_pauli_plan::PAULI_TERMS_PER_PASS));
+                std::printf(" |");
+            }
+        } else if (what == "passraw") {
+            int n, count;
+            qsv_pauli_plan::Pass pass;
+            in >> n;
+            pass.xmask = u64(in);
+            in >> pass.pivot >> count;
+            for (int t = 0; t < count; ++t) {
+                pass.zmask.push_back(u64(in));
+                pass.n_y.push_back(ints(in, 1)[0]);
+                pass.index.push_back(t);
+            }
+            const PauliPass a = pauli_pass_args(pass, 1ull << n);
+            std::printf("%d %d", a.ok ? 1 : 0, a.width);
+        } else if (what == "paulirot") {
+            int n, count;
+            in >> n >> count;
+            std::vector<qsv_pauli_plan::Term> terms(count);
+            std::vector<double> cs(count), sn(count);
+            for (int t = 0; t < count; ++t) {
+                terms[t].xmask = u64(in), terms[t].zmask = u64(in);
+                in >> cs[t] >> sn[t];
+            }
+            constexpr int CAP = qsv_pauli_rotation_plan::ROTATIONS_PER_PASS;
+            for (const qsv_pauli_rotation_plan::Pass &pass : qsv_pauli_rotation_plan::plan(terms)) {
+                const PauliRotate a = pauli_rotate_args(pass, 1ull << n, cs.data(), sn.data());
+                std::printf(" %d %d %llu %llu %d %u %u", a.ok ? 1 : 0, a.width, static_cast<unsigned long long>(a.g.items),
+                            static_cast<unsigned long long>(a.g.xmask), a.g.pivot, a.g.diag, a.g.rot);
+                put_ints(std::vector<uint64_t>(a.g.zmask, a.g.zmask + CAP));
+                put_doubles(a.g.cs, CAP);
+                put_doubles(a.g.sn, CAP);
+                std::printf(" |");
+            }
+        } else if (what == "rotraw") {
+            int n, count;
+            qsv_pauli_rotation_plan::Pass pass;
+            in >> n;
+            pass.xmask = u64(in);
+            in >> pass.pivot >> count;
+            for (int t = 0; t < count; ++t) {
+                pass.term_xmask.push_back(u64(in));
+                pass.zmask.push_back(u64(in));
+                pass.n_y.push_back(ints(in, 1)[0]);
+                pass.index.push_back(t);
+            }
+            const std::vector<double> cs(count + 1, 0.5), sn(count + 1, 0.25);
+            const PauliRotate a = pauli_rotate_args(pass, 1ull << n, cs.data(), sn.data());
+            std::printf("%d %d", a.ok ? 1 : 0, a.width);
         } else {
             return 2;
         }

@@ -19,7 +19,7 @@ def splitmix64(x: np.ndarray) -> np.ndarray:
 
 
 def counter_normal(seed: int, start: int, count: int) -> np.ndarray:
-    """NumPy restatement of k_fill_random (qsv_kernels.hip): complex normals keyed by (seed, global index)."""
+    """NumPy restatement of k_fill_random (qsv_readout.hip): complex normals keyed by (seed, global index)."""
     with np.errstate(over="ignore"):
         key = splitmix64(np.array([seed], dtype=np.uint64))[0]
         g = np.arange(start, start + count, dtype=np.uint64)

@@ -20,7 +20,8 @@ REPO = HERE.parent.parent
 CSRC = REPO / "quantum_computations_amd" / "csrc"
 OUT = HERE / "_build"
 CLANG = Path("/opt/rocm/lib/llvm/bin/clang++")
-SOURCES = ["qsv_api.hip", "qsv_kernels.hip", "qsv_qudit.hip", "qsv_gemm.hip", "qsv_decomp.hip", "qsv_circuit.hip"]
+SOURCES = ["qsv_api.hip", "qsv_kernels.hip", "qsv_readout.hip", "qsv_pauli.hip", "qsv_qudit.hip", "qsv_gemm.hip", "qsv_decomp.hip",
+           "qsv_circuit.hip"]
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g", "-O1"]
 INC = [f"-I{REPO / 'include'}", f"-I{CSRC}"]
 
@@ -33,7 +34,8 @@ def build(verbose: bool = False) -> Path:
     if not CLANG.exists():
         raise RuntimeError(f"{CLANG} not found: the sanitized host build needs the ROCm clang")
     OUT.mkdir(exist_ok=True)
-    headers = [CSRC / "qsv_internal.h", CSRC / "qsv_linalg.h", CSRC / "qsv_plan.h", CSRC / "qsv_layout.h", REPO / "include" / "qsv.h"]
+    headers = [CSRC / "qsv_internal.h", CSRC / "qsv_device.h", CSRC / "qsv_linalg.h", CSRC / "qsv_plan.h", CSRC / "qsv_layout.h",
+               CSRC / "qsv_readout_layout.h", REPO / "include" / "qsv.h"]
     objs = []
 
     def run(cmd):

@@ -101,7 +101,8 @@ typedef struct qsv_state qsv_state;
  *  - Every other entry point that takes the register flushes the queue first: sync, download, upload, copy (both
  *    registers), fill_random, scale, set_basis, norm2, inner, expect_*, probabilities, reduced_density, sample,
  *    measure*, collapse, insert, permute, apply_kq, apply_mcphase, apply_sequence, apply_pauli_rotation(s) (never
- *    queued themselves), set_stream, set_option, device_ptr,
+ *    queued themselves), apply_pauli_sum, pauli_transition_sum, pauli_rotations_adjoint (both registers), set_stream,
+ *    set_option, device_ptr,
  *    timer_*, event_*, last_kernel, and qsv_flush itself.  qsv_destroy drops what is pending.
  *  - A launch error during a flush is returned by the call that flushed; the rest of the queue is dropped.
  *  - Views (qsv_create_view, qsv_rebind_view) never defer, nor does a register once qsv_device_ptr has handed out its
@@ -232,6 +233,38 @@ int qsv_expect_pauli(qsv_state *st, int k, const int *qubits, const char *paulis
  * launches made.  The whole list is validated before the first launch; n_terms = 0 gives 0 and no launch. */
 int qsv_expect_pauli_sum(qsv_state *st, int n_terms, const int *term_offsets, const int *qubits, const char *paulis,
                          const double *coeffs, double *term_values, double *re, double *im, uint64_t *passes);
+/* H as an operator, H = sum_t c_t P_t (layout of term_offsets / qubits / paulis as in qsv_expect_pauli_sum; coeffs holds
+ * n_terms interleaved complex c_t and is required):  dst = H src, or dst += H src with accumulate != 0.  dst and src are
+ * two qubit registers on one device whose memory does not meet (QSV_EINVAL otherwise, QSV_ESTATE for a mode register);
+ * dst needs room for src's amplitudes (QSV_ENOMEM) and takes src's size, and must already have it to accumulate
+ * (QSV_EINVAL).  Terms that flip the same qubits share a pass of at most 8 (csrc/qsv_pauli_plan.h): a pass reads src once,
+ * builds the two complex factors of each pair {i, i ^ xmask} from the terms' signs and writes dst once; only the first
+ * pass of a call that overwrites skips reading the old dst.  The whole list is validated before either deferred queue
+ * is flushed; src's stream is synchronised, then the launches go back to back on dst's stream with no host
+ * synchronisation.  n_terms = 0 zeroes dst (leaves it alone with accumulate).  passes (may be NULL) = kernel launches. */
+int qsv_apply_pauli_sum(qsv_state *dst, qsv_state *src, int n_terms, const int *term_offsets, const int *qubits,
+                        const char *paulis, const double *coeffs, int accumulate, uint64_t *passes);
+/* <bra| P_t |ket> for every term and (re, im) = <bra| H |ket> = sum_t c_t <bra|P_t|ket>, arguments as in
+ * qsv_expect_pauli_sum (coeffs NULL: all 1) except that term_values (may be NULL) receives n_terms interleaved COMPLEX
+ * numbers.  Read-only; the registers have the same size and device and may be the same register, which gives
+ * qsv_expect_pauli_sum's numbers.  Same grouping, launch order and deterministic host summation as there: all passes back
+ * to back on bra's stream (ket's is synchronised first), one copy and one synchronisation per call. */
+int qsv_pauli_transition_sum(qsv_state *bra, qsv_state *ket, int n_terms, const int *term_offsets, const int *qubits,
+                             const char *paulis, const double *coeffs, double *term_values, double *re, double *im,
+                             uint64_t *passes);
+/* The backward (adjoint) walk over a rotation list.  On entry psi = R_{T-1} ... R_0 psi0 with R_t = exp(-i thetas[t]/2 P_t),
+ * the list exactly as qsv_apply_pauli_rotations took it, and lambda is any other register of the same size on the same
+ * device (memory must not meet).  For t = T-1 ... 0:  values[2t], values[2t+1] = <lambda| P_t |psi>, then
+ * psi <- R_t^dagger psi and lambda <- R_t^dagger lambda.  On exit psi holds psi0 up to rounding and lambda holds
+ * U^dagger lambda: BOTH registers are consumed / rewound.  With lambda = H psi the gradient of E = <psi|H|psi> is
+ * dE/dtheta_t = Im values[t].  The passes are those of the forward plan taken last first
+ * (csrc/qsv_pauli_rotation_plan.h), so passes (may be NULL) equals the forward count and the cost does not grow with the
+ * rotations per pass; there is no host synchronisation between passes except where the per-workgroup partial sums of a
+ * long list on a large register outgrow a fixed scratch budget (csrc/qsv_pauli.hip).  Validation, flushes of both deferred
+ * queues and streams as in qsv_apply_pauli_sum: lambda's stream is synchronised, the launches go on psi's, and the call
+ * returns with both registers finished.  n_terms = 0 does nothing. */
+int qsv_pauli_rotations_adjoint(qsv_state *psi, qsv_state *lambda, int n_terms, const int *term_offsets, const int *qubits,
+                                const char *paulis, const double *thetas, double *values, uint64_t *passes);
 /* Reduced density matrix of the k <= 6 qubits `qubits` (all others traced out) in one read pass over the register:
  * rho[i][j] = sum_rest psi[i, rest] conj(psi[j, rest]), written row-major as 4^k complex numbers, qubits[0] the most
  * significant bit of i and j.  What a caller of the reference gets from npq.ket2dm (numpy_quantum.py:110-113)

@@ -915,14 +915,12 @@ int qsv_expect_pauli(qsv_state *st, int k, const int *qubits, const char *paulis
     return qsvk_expect_pauli(st, xmask, zmask, n_y, re, im);
 }
 
-int qsv_expect_pauli_sum(qsv_state *st, int n_terms, const int *term_offsets, const int *qubits, const char *paulis,
-                         const double *coeffs, double *term_values, double *re, double *im, uint64_t *passes) {
-    if (!valid(st) || !re || !im) return qsv_fail(QSV_EINVAL, "null pointer");
-    if (n_terms < 0) return qsv_fail(QSV_EINVAL, "negative number of Pauli terms");
-    if (n_terms > 0 && !term_offsets) return qsv_fail(QSV_EINVAL, "null pointer");
-    if (st->kind != 0) return qsv_fail(QSV_ESTATE, "this call needs a qubit register");
-    // the whole list is checked and turned into masks before anything is launched
-    std::vector<qsv_pauli_plan::Term> terms(n_terms);
+// The flattened term list of the Pauli-sum and Pauli-rotation calls as masks of register bits: term t is paulis[j] on
+// qubits[j] for j in [term_offsets[t], term_offsets[t + 1]).  The whole list is checked; nothing is launched or flushed.
+static int parse_pauli_terms(const qsv_state *st, int n_terms, const int *term_offsets, const int *qubits, const char *paulis,
+                             std::vector<qsv_pauli_plan::Term> *out) {
+    std::vector<qsv_pauli_plan::Term> &terms = *out;
+    terms.assign(n_terms, qsv_pauli_plan::Term());
     for (int t = 0; t < n_terms; ++t) {
         const int first = term_offsets[t], k = term_offsets[t + 1] - first;
         if (first < 0 || k < 0) return qsv_fail(QSV_EINVAL, "Pauli term offsets must start at or above 0 and never decrease");
@@ -941,6 +939,19 @@ int qsv_expect_pauli_sum(qsv_state *st, int n_terms, const int *term_offsets, co
             }
         }
     }
+    return QSV_OK;
+}
+
+int qsv_expect_pauli_sum(qsv_state *st, int n_terms, const int *term_offsets, const int *qubits, const char *paulis,
+                         const double *coeffs, double *term_values, double *re, double *im, uint64_t *passes) {
+    if (!valid(st) || !re || !im) return qsv_fail(QSV_EINVAL, "null pointer");
+    if (n_terms < 0) return qsv_fail(QSV_EINVAL, "negative number of Pauli terms");
+    if (n_terms > 0 && !term_offsets) return qsv_fail(QSV_EINVAL, "null pointer");
+    if (st->kind != 0) return qsv_fail(QSV_ESTATE, "this call needs a qubit register");
+    // the whole list is checked and turned into masks before anything is launched
+    std::vector<qsv_pauli_plan::Term> terms;
+    const int bad = parse_pauli_terms(st, n_terms, term_offsets, qubits, paulis, &terms);
+    if (bad) return bad;
     *re = 0.0;
     *im = 0.0;
     if (passes) *passes = 0;
@@ -970,25 +981,9 @@ int qsv_apply_pauli_rotations(qsv_state *st, int n_terms, const int *term_offset
     if (n_terms > 0 && (!term_offsets || !thetas)) return qsv_fail(QSV_EINVAL, "null pointer");
     if (st->kind != 0) return qsv_fail(QSV_ESTATE, "this call needs a qubit register");
     // the whole list is checked and turned into masks before the queue is flushed or anything is launched
-    std::vector<qsv_pauli_plan::Term> terms(n_terms);
-    for (int t = 0; t < n_terms; ++t) {
-        const int first = term_offsets[t], k = term_offsets[t + 1] - first;
-        if (first < 0 || k < 0) return qsv_fail(QSV_EINVAL, "Pauli term offsets must start at or above 0 and never decrease");
-        if (k > 64) return qsv_fail(QSV_EINVAL, "bad Pauli string length");
-        if (k > 0 && (!qubits || !paulis)) return qsv_fail(QSV_EINVAL, "null pointer");
-        const int rc = check_qubits(st, k, k ? qubits + first : nullptr);
-        if (rc) return rc;
-        for (int j = 0; j < k; ++j) {
-            const uint64_t bit = 1ull << bit_of(st, qubits[first + j]);
-            switch (paulis[first + j]) {
-                case 'I': case 'i': break;
-                case 'X': case 'x': terms[t].xmask |= bit; break;
-                case 'Z': case 'z': terms[t].zmask |= bit; break;
-                case 'Y': case 'y': terms[t].xmask |= bit; terms[t].zmask |= bit; break;
-                default: return qsv_fail(QSV_EINVAL, "Pauli letters must be I, X, Y or Z");
-            }
-        }
-    }
+    std::vector<qsv_pauli_plan::Term> terms;
+    const int bad = parse_pauli_terms(st, n_terms, term_offsets, qubits, paulis, &terms);
+    if (bad) return bad;
     if (passes) *passes = 0;
     if (n_terms == 0) return QSV_OK;
     QSV_FLUSH(st);
@@ -1009,6 +1004,126 @@ int qsv_apply_pauli_rotation(qsv_state *st, int k, const int *qubits, const char
     if (k < 0 || k > 64) return qsv_fail(QSV_EINVAL, "bad Pauli string length");
     const int offsets[2] = {0, k};
     return qsv_apply_pauli_rotations(st, 1, offsets, qubits, paulis, &theta, nullptr);
+}
+
+// Two registers that one launch reads and writes: qubit registers on one device.  check_disjoint: their first amps_a and
+// amps_b amplitudes (which must lie inside their allocations) do not meet.
+static int check_register_pair(const qsv_state *a, const qsv_state *b) {
+    if (a->kind != 0 || b->kind != 0) return qsv_fail(QSV_ESTATE, "this call needs qubit registers");
+    if (a == b) return qsv_fail(QSV_EINVAL, "the two registers must not share memory");
+    if (a->device != b->device) return qsv_fail(QSV_EINVAL, "registers on different devices");
+    return QSV_OK;
+}
+static int check_disjoint(const qsv_state *a, const qsv_state *b, uint64_t amps_a, uint64_t amps_b) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a->data), b0 = reinterpret_cast<uintptr_t>(b->data);
+    if (a0 < b0 + sizeof(amp_t) * amps_b && b0 < a0 + sizeof(amp_t) * amps_a)
+        return qsv_fail(QSV_EINVAL, "the two registers must not share memory");
+    return QSV_OK;
+}
+
+int qsv_apply_pauli_sum(qsv_state *dst, qsv_state *src, int n_terms, const int *term_offsets, const int *qubits,
+                        const char *paulis, const double *coeffs, int accumulate, uint64_t *passes) {
+    if (!valid(dst) || !valid(src)) return qsv_fail(QSV_EINVAL, "null pointer");
+    if (n_terms < 0) return qsv_fail(QSV_EINVAL, "negative number of Pauli terms");
+    if (n_terms > 0 && (!term_offsets || !coeffs)) return qsv_fail(QSV_EINVAL, "null pointer");
+    int rc = check_register_pair(dst, src);
+    if (rc) return rc;
+    if (dst->capacity < src->amps) return qsv_fail(QSV_ENOMEM, "destination register too small");
+    rc = check_disjoint(dst, src, src->amps, src->amps);
+    if (rc) return rc;
+    if (accumulate && dst->n != src->n) return qsv_fail(QSV_EINVAL, "registers of different sizes");
+    // the whole list is checked and turned into masks before a queue is flushed or anything is launched
+    std::vector<qsv_pauli_plan::Term> terms;
+    rc = parse_pauli_terms(src, n_terms, term_offsets, qubits, paulis, &terms);
+    if (rc) return rc;
+    if (passes) *passes = 0;
+    QSV_FLUSH(dst);
+    QSV_FLUSH(src);
+    QSV_HIP(hipSetDevice(dst->device));
+    QSV_HIP(hipStreamSynchronize(src->stream));
+    // dst takes src's size only once every launch went out, as in qsv_copy: a failed launch leaves dst's size alone
+    if (n_terms == 0) {
+        if (!accumulate) QSV_HIP(hipMemsetAsync(dst->data, 0, sizeof(amp_t) * src->amps, dst->stream));
+    } else {
+        const std::vector<qsv_pauli_plan::Pass> plan = qsv_pauli_plan::plan(terms);
+        rc = qsvk_pauli_sum_apply_passes(dst, src->data, src->amps, plan, coeffs, accumulate != 0);
+        if (rc) return rc;
+        if (passes) *passes = plan.size();
+    }
+    dst->n = src->n;
+    dst->amps = src->amps;
+    return QSV_OK;
+}
+
+int qsv_pauli_transition_sum(qsv_state *bra, qsv_state *ket, int n_terms, const int *term_offsets, const int *qubits,
+                             const char *paulis, const double *coeffs, double *term_values, double *re, double *im,
+                             uint64_t *passes) {
+    if (!valid(bra) || !valid(ket) || !re || !im) return qsv_fail(QSV_EINVAL, "null pointer");
+    if (n_terms < 0) return qsv_fail(QSV_EINVAL, "negative number of Pauli terms");
+    if (n_terms > 0 && !term_offsets) return qsv_fail(QSV_EINVAL, "null pointer");
+    if (bra->kind != 0 || ket->kind != 0) return qsv_fail(QSV_ESTATE, "this call needs qubit registers");
+    if (bra->n != ket->n) return qsv_fail(QSV_EINVAL, "registers of different sizes");
+    if (bra->device != ket->device) return qsv_fail(QSV_EINVAL, "registers on different devices");
+    std::vector<qsv_pauli_plan::Term> terms;
+    int rc = parse_pauli_terms(bra, n_terms, term_offsets, qubits, paulis, &terms);
+    if (rc) return rc;
+    *re = 0.0;
+    *im = 0.0;
+    if (passes) *passes = 0;
+    if (n_terms == 0) return QSV_OK;
+    QSV_FLUSH(bra);
+    QSV_FLUSH(ket);
+    QSV_HIP(hipSetDevice(bra->device));
+    if (ket != bra) QSV_HIP(hipStreamSynchronize(ket->stream));
+    const std::vector<qsv_pauli_plan::Pass> plan = qsv_pauli_plan::plan(terms);
+    std::vector<double> values(2 * static_cast<size_t>(n_terms), 0.0);
+    rc = qsvk_pauli_transition_groups(bra, ket->data, plan, values.data());
+    if (rc) return rc;
+    double sr = 0.0, si = 0.0;
+    for (int t = 0; t < n_terms; ++t) {
+        const double cr = coeffs ? coeffs[2 * t] : 1.0, ci = coeffs ? coeffs[2 * t + 1] : 0.0;
+        sr += cr * values[2 * t] - ci * values[2 * t + 1];
+        si += cr * values[2 * t + 1] + ci * values[2 * t];
+        if (term_values) {
+            term_values[2 * t] = values[2 * t];
+            term_values[2 * t + 1] = values[2 * t + 1];
+        }
+    }
+    *re = sr;
+    *im = si;
+    if (passes) *passes = plan.size();
+    return QSV_OK;
+}
+
+int qsv_pauli_rotations_adjoint(qsv_state *psi, qsv_state *lambda, int n_terms, const int *term_offsets, const int *qubits,
+                                const char *paulis, const double *thetas, double *values, uint64_t *passes) {
+    if (!valid(psi) || !valid(lambda)) return qsv_fail(QSV_EINVAL, "null pointer");
+    if (n_terms < 0) return qsv_fail(QSV_EINVAL, "negative number of Pauli terms");
+    if (n_terms > 0 && (!term_offsets || !thetas || !values)) return qsv_fail(QSV_EINVAL, "null pointer");
+    int rc = check_register_pair(psi, lambda);
+    if (rc) return rc;
+    if (psi->n != lambda->n) return qsv_fail(QSV_EINVAL, "registers of different sizes");
+    rc = check_disjoint(psi, lambda, psi->amps, lambda->amps);
+    if (rc) return rc;
+    std::vector<qsv_pauli_plan::Term> terms;
+    rc = parse_pauli_terms(psi, n_terms, term_offsets, qubits, paulis, &terms);
+    if (rc) return rc;
+    if (passes) *passes = 0;
+    if (n_terms == 0) return QSV_OK;
+    QSV_FLUSH(psi);
+    QSV_FLUSH(lambda);
+    QSV_HIP(hipSetDevice(psi->device));
+    QSV_HIP(hipStreamSynchronize(lambda->stream));
+    std::vector<double> cs(n_terms), sn(n_terms);
+    for (int t = 0; t < n_terms; ++t) {
+        cs[t] = std::cos(0.5 * thetas[t]);
+        sn[t] = std::sin(0.5 * thetas[t]);
+    }
+    const std::vector<qsv_pauli_rotation_plan::Pass> plan = qsv_pauli_rotation_plan::plan(terms);
+    rc = qsvk_pauli_adjoint_passes(psi, lambda->data, plan, cs.data(), sn.data(), values);
+    if (rc) return rc;
+    if (passes) *passes = plan.size();
+    return QSV_OK;
 }
 
 int qsv_sample(qsv_state *st, int shots, const double *u, uint64_t *out) {

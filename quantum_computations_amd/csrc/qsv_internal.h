@@ -164,6 +164,14 @@ int qsvk_expect_pauli_groups(qsv_state *st, const std::vector<qsv_pauli_plan::Pa
 // every pass of a qsv_apply_pauli_rotations plan, in place and with no synchronisation; cs / sn = cos, sin(theta / 2) per term of the caller's list
 int qsvk_pauli_rotate_passes(qsv_state *st, const std::vector<qsv_pauli_rotation_plan::Pass> &passes, const double *cs,
                              const double *sn);
+// every pass of a qsv_apply_pauli_sum plan: dst (+)= H src over amps amplitudes, no synchronisation; coeffs = interleaved complex per term
+int qsvk_pauli_sum_apply_passes(qsv_state *dst, const amp_t *src, uint64_t amps, const std::vector<qsv_pauli_plan::Pass> &passes,
+                                const double *coeffs, bool accumulate);
+// every pass of a qsv_pauli_transition_sum plan: values[2 index, 2 index + 1] = <bra|P|ket>, one synchronisation
+int qsvk_pauli_transition_groups(qsv_state *bra, const amp_t *ket, const std::vector<qsv_pauli_plan::Pass> &passes, double *values);
+// the backward walk over a qsv_apply_pauli_rotations plan: values[2 index, 2 index + 1] = <lambda|P|psi>, both registers rewound
+int qsvk_pauli_adjoint_passes(qsv_state *psi, amp_t *lambda, const std::vector<qsv_pauli_rotation_plan::Pass> &passes,
+                              const double *cs, const double *sn, double *values);
 int qsvk_reduced_density(qsv_state *st, int k, const int *bits, double *rho_out);
 int qsvk_expect_density(qsv_state *ket, qsv_state *rho, double *re, double *im);
 int qsvk_sample(qsv_state *st, int shots, const double *u, uint64_t *out);

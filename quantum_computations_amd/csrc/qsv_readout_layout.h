@@ -86,6 +86,20 @@ struct PauliRotateArgs {
 };
 static_assert(sizeof(PauliRotateArgs) == 32 + 24 * qsv_pauli_rotation_plan::ROTATIONS_PER_PASS, "kernel argument layout");
 
+// One planned pass of qsv_apply_pauli_sum (qsv_pauli_plan.h): dst (+)= (sum_t c_t P_t) src for up to T Pauli strings with
+// one shared xmask.  (P x)[k] = i^{nY} s(k ^ xmask) x[k ^ xmask]: with d_t = c_t i^{nY_t} the pair {i, j = i ^ xmask} gets
+// dst[i] (+)= f_i src[j], f_i = sum_t d_t s_t(j), and dst[j] (+)= f_j src[i], f_j = sum_t d_t s_t(i).
+struct PauliSumApplyArgs {
+    uint64_t items;      // pairs (amps / 2), or amps for the diagonal group
+    uint64_t xmask;
+    int32_t pivot;       // highest set bit of xmask: the pass writes (unused by the diagonal form)
+    uint32_t odd;        // bit t: term t has odd nY, s_t(j) = -s_t(i)
+    uint64_t zmask[qsv_pauli_plan::PAULI_TERMS_PER_PASS];   // 0 beyond the pass's terms
+    double d_re[qsv_pauli_plan::PAULI_TERMS_PER_PASS];      // d_t = c_t i^{nY_t}, 0 beyond the pass's terms
+    double d_im[qsv_pauli_plan::PAULI_TERMS_PER_PASS];
+};
+static_assert(sizeof(PauliSumApplyArgs) == 24 + 24 * qsv_pauli_plan::PAULI_TERMS_PER_PASS, "kernel argument layout");
+
 // ---- qubit permutation (k_permute_s) ------------------------------------------------------------------------------------
 struct PermTile {
     PermTileArgs args;
@@ -315,6 +329,83 @@ inline PauliRotate pauli_rotate_args(const qsv_pauli_rotation_plan::Pass &p, uin
     }
     out.width = pauli_width(count);
     out.ok = true;
+    return out;
+}
+
+// ---- Pauli sums as operators (k_pauli_sum_apply_group, k_pauli_transition_group, k_pauli_adjoint_group) ------------------
+// i^k (re + i im), the factor the kernels leave to the host
+inline void times_i_pow(int k, double re, double im, double *out_re, double *out_im) {
+    switch (k & 3) {
+        case 0: *out_re = re; *out_im = im; break;
+        case 1: *out_re = -im; *out_im = re; break;
+        case 2: *out_re = -re; *out_im = -im; break;
+        default: *out_re = im; *out_im = -re; break;
+    }
+}
+
+// coeffs: the interleaved complex c_t of every term, indexed as the caller's list.  The planner's own pivot (the lowest
+// flipped bit, for passes that only read) is not used: this pass writes and takes the highest, as the rotation pass does.
+struct PauliSumApply {
+    bool ok = false;     // 1 .. PAULI_TERMS_PER_PASS terms and an xmask inside the register
+    PauliSumApplyArgs g;
+    int width = 0;
+    bool first = false;  // the first pass of a call that overwrites: the old dst is not read
+};
+inline PauliSumApply pauli_sum_apply_args(const qsv_pauli_plan::Pass &p, uint64_t amps, const double *coeffs, bool first) {
+    PauliSumApply out;
+    PauliSumApplyArgs &g = out.g;
+    memset(&g, 0, sizeof(g));
+    const int count = static_cast<int>(p.zmask.size());
+    if (count < 1 || count > qsv_pauli_plan::PAULI_TERMS_PER_PASS || p.xmask >= amps) return out;
+    g.items = p.xmask ? amps / 2 : amps;
+    g.xmask = p.xmask;
+    g.pivot = p.xmask ? qsv_pauli_rotation_plan::highest_bit(p.xmask) : 0;
+    for (int t = 0; t < count; ++t) {
+        g.zmask[t] = p.zmask[t];
+        if (p.n_y[t] & 1) g.odd |= 1u << t;
+        times_i_pow(p.n_y[t], coeffs[2 * p.index[t]], coeffs[2 * p.index[t] + 1], &g.d_re[t], &g.d_im[t]);
+    }
+    out.width = pauli_width(count);
+    out.first = first;
+    out.ok = true;
+    return out;
+}
+// Every pass of a call; `first` is set on pass 0 of a call that does not accumulate, and nowhere else.
+inline std::vector<PauliSumApply> pauli_sum_apply_passes(const std::vector<qsv_pauli_plan::Pass> &passes, uint64_t amps,
+                                                         const double *coeffs, bool accumulate) {
+    std::vector<PauliSumApply> out;
+    for (size_t k = 0; k < passes.size(); ++k) out.push_back(pauli_sum_apply_args(passes[k], amps, coeffs, k == 0 && !accumulate));
+    return out;
+}
+
+// The backward walk of qsv_pauli_rotations_adjoint over one pass of the forward plan: the pass's terms in reverse order,
+// each with -theta (cs kept, sn negated); padding as in pauli_rotate_args.  index[t]: the caller's term behind slot t.
+struct PauliAdjoint {
+    PauliRotate r;
+    int index[qsv_pauli_rotation_plan::ROTATIONS_PER_PASS];
+    int n_y[qsv_pauli_rotation_plan::ROTATIONS_PER_PASS];    // of the term behind slot t (0: diagonal or padding)
+};
+inline PauliAdjoint pauli_adjoint_args(const qsv_pauli_rotation_plan::Pass &p, uint64_t amps, const double *cs, const double *sn) {
+    qsv_pauli_rotation_plan::Pass back = p;
+    std::reverse(back.index.begin(), back.index.end());
+    std::reverse(back.term_xmask.begin(), back.term_xmask.end());
+    std::reverse(back.zmask.begin(), back.zmask.end());
+    std::reverse(back.n_y.begin(), back.n_y.end());
+    PauliAdjoint out;
+    out.r = pauli_rotate_args(back, amps, cs, sn);
+    const int count = out.r.ok ? static_cast<int>(back.index.size()) : 0;
+    for (int t = 0; t < qsv_pauli_rotation_plan::ROTATIONS_PER_PASS; ++t) {
+        out.index[t] = t < count ? back.index[t] : -1;
+        out.n_y[t] = t < count && back.term_xmask[t] ? back.n_y[t] : 0;
+        if (t < count) out.r.g.sn[t] = -out.r.g.sn[t];
+    }
+    return out;
+}
+// The forward plan's passes in the order the walk takes them: last first.
+inline std::vector<PauliAdjoint> pauli_adjoint_passes(const std::vector<qsv_pauli_rotation_plan::Pass> &passes, uint64_t amps,
+                                                      const double *cs, const double *sn) {
+    std::vector<PauliAdjoint> out;
+    for (size_t k = passes.size(); k-- > 0;) out.push_back(pauli_adjoint_args(passes[k], amps, cs, sn));
     return out;
 }
 

@@ -38,6 +38,53 @@ def _ints(values) -> "C.Array[C.c_int]":
     return (C.c_int * max(len(values), 1))(*values)
 
 
+def _flat_terms(terms):
+    """``[(coefficient or angle, letters, qubits), ...]`` as the C ABI takes it: (count, offsets, qubits, letters,
+    the first entries as a float64 buffer of interleaved complex numbers)."""
+    offsets, qubits, letters, coeffs = [0], [], [], []
+    for coefficient, paulis, qs in terms:
+        qs = [int(q) for q in qs]
+        if len(paulis) != len(qs):
+            raise ValueError("one Pauli letter per qubit")
+        qubits += qs
+        letters.append(str(paulis))
+        offsets.append(len(qubits))
+        coeffs.append(complex(coefficient))
+    cbuf = np.ascontiguousarray(coeffs, dtype=np.complex128).view(np.float64)
+    return len(coeffs), _ints(offsets), _ints(qubits), "".join(letters).encode(), cbuf
+
+
+def _real_terms(terms, what: str) -> list:
+    terms = [(complex(c), str(paulis), [int(q) for q in qs]) for c, paulis, qs in terms]
+    if any(c.imag != 0.0 for c, _, _ in terms):
+        raise ValueError(f"{what} needs real coefficients (a hermitian Pauli sum)")
+    return terms
+
+
+def _check_terms(terms, n_qubits: int) -> None:
+    """The refusals of the C term parser, for a caller that has to know the list is good before it changes a register."""
+    for _, paulis, qs in terms:
+        if len(paulis) != len(qs):
+            raise ValueError("one Pauli letter per qubit")
+        if len(paulis) > 64:
+            raise ValueError("bad Pauli string length")
+        if any(letter not in "IXYZixyz" for letter in paulis):
+            raise ValueError("Pauli letters must be I, X, Y or Z")
+        if any(not 0 <= q < n_qubits for q in qs):
+            raise ValueError(f"qubit index out of range for a {n_qubits}-qubit register")
+        if len(set(qs)) != len(qs):
+            raise ValueError("Indices must be distinct.")
+
+
+def _ket_operand(register, name: str) -> None:
+    if isinstance(register, DensityState):
+        raise ValueError(f"{name} must be a ket register, not a density register")
+
+
+def _dbl(buf: np.ndarray):
+    return buf.ctypes.data_as(C.POINTER(C.c_double))
+
+
 class DeviceState:
     """An n-qubit complex128 register in HBM (qubit 0 = most significant bit, as in the reference)."""
 
@@ -314,20 +361,10 @@ class DeviceState:
         register (all Z-only terms need one pass per eight terms; XX and YY on a pair share one), each pass reads
         every amplitude once, and the whole sum costs one synchronisation.  Returns the complex value, or
         ``(value, per-term real expectation values in the caller's order)`` with ``return_terms=True``."""
-        offsets, qubits, letters, coeffs = [0], [], [], []
-        for coefficient, paulis, qs in terms:
-            qs = [int(q) for q in qs]
-            if len(paulis) != len(qs):
-                raise ValueError("one Pauli letter per qubit")
-            qubits += qs
-            letters.append(str(paulis))
-            offsets.append(len(qubits))
-            coeffs.append(complex(coefficient))
-        count = len(coeffs)
-        cbuf = np.ascontiguousarray(coeffs, dtype=np.complex128).view(np.float64)
+        count, offsets, qubits, letters, cbuf = _flat_terms(terms)
         values = np.zeros(count, dtype=np.float64)
         re, im = C.c_double(), C.c_double()
-        _lib.call("qsv_expect_pauli_sum", self._h, count, _ints(offsets), _ints(qubits), "".join(letters).encode(),
+        _lib.call("qsv_expect_pauli_sum", self._h, count, offsets, qubits, letters,
                   cbuf.ctypes.data_as(C.POINTER(C.c_double)), values.ctypes.data_as(C.POINTER(C.c_double)),
                   C.byref(re), C.byref(im), None)
         value = complex(re.value, im.value)
@@ -371,6 +408,75 @@ class DeviceState:
         coefficients): ``npq.trotter_rotations`` turned into shared passes by ``apply_pauli_rotations``."""
         from .dv_simulator import numpy_quantum as npq
         return self.apply_pauli_rotations(npq.trotter_rotations(npq.PauliSum(self.num_qubits, terms), t, steps, order))
+
+    # ---- Pauli sums as operators ---------------------------------------------------------------
+    def apply_pauli_sum(self, terms, out: "DeviceState | None" = None, accumulate: bool = False) -> "DeviceState":
+        """``out = H self`` (``out += H self`` with ``accumulate``) for ``H = sum_t c_t P_t``, ``terms`` as for
+        ``expect_pauli_sum``.  ``out`` is another register on the same device, allocated when None; it is returned.
+        Terms that flip the same qubits share a pass of at most eight.  ``self`` is not changed."""
+        if out is None:
+            out = DeviceState.zeros(self.num_qubits, self.device)
+        _ket_operand(out, "out")
+        count, offsets, qubits, letters, cbuf = _flat_terms(terms)
+        _lib.call("qsv_apply_pauli_sum", out._h, self._h, count, offsets, qubits, letters, _dbl(cbuf), int(bool(accumulate)), None)
+        return out
+
+    def transition_pauli_sum(self, terms, ket: "DeviceState", *, return_terms: bool = False):
+        """``<self| H |ket>`` for ``H = sum_t c_t P_t`` without forming ``H ket``; ``self`` is the bra.  Returns the
+        complex value, or ``(value, complex <self|P_t|ket> per term in the caller's order)`` with ``return_terms=True``.
+        ``ket`` may be ``self``: then this is ``expect_pauli_sum``."""
+        _ket_operand(ket, "ket")
+        count, offsets, qubits, letters, cbuf = _flat_terms(terms)
+        values = np.zeros(count, dtype=np.complex128)
+        re, im = C.c_double(), C.c_double()
+        _lib.call("qsv_pauli_transition_sum", self._h, ket._h, count, offsets, qubits, letters, _dbl(cbuf),
+                  _dbl(values.view(np.float64)), C.byref(re), C.byref(im), None)
+        value = complex(re.value, im.value)
+        return (value, values) if return_terms else value
+
+    def variance_pauli_sum(self, terms) -> float:
+        """``<H^2> - <H>^2`` of a hermitian ``H`` (real coefficients) on a normalised register: ``||H psi||^2`` from one
+        ``apply_pauli_sum`` into a scratch register and ``<H> = <psi|H psi>`` by ``inner``."""
+        terms = _real_terms(terms, "the variance")
+        h_psi = self.apply_pauli_sum(terms)
+        try:
+            return h_psi.norm2() - self.inner(h_psi).real ** 2
+        finally:
+            h_psi.close()
+
+    def pauli_rotations_adjoint(self, rotations, lam: "DeviceState") -> np.ndarray:
+        """The backward walk over ``rotations`` (the list ``apply_pauli_rotations`` took to make ``self``): for the last
+        rotation first, ``values[k] = <lam|P_k|self>``, then both registers are rotated back by ``R_k``.  On return
+        ``self`` is the register from before the rotations (up to rounding) and ``lam`` holds ``U^dagger lam``: both are
+        consumed.  Costs the passes of the forward list.  Returns the complex ``values``."""
+        _ket_operand(lam, "lam")
+        count, offsets, qubits, letters, cbuf = _flat_terms(rotations)
+        thetas = np.ascontiguousarray(cbuf.view(np.complex128).real)
+        values = np.zeros(count, dtype=np.complex128)
+        _lib.call("qsv_pauli_rotations_adjoint", self._h, lam._h, count, offsets, qubits, letters, _dbl(thetas),
+                  _dbl(values.view(np.float64)), None)
+        return values
+
+    def energy_and_gradient(self, rotations, terms) -> tuple[float, np.ndarray]:
+        """``E = <psi|H|psi>`` for ``psi = U(theta) self`` and ``dE/dtheta_k`` for every rotation of the list, by the
+        adjoint method: the rotations forward, ``lambda = H psi`` into a scratch register, ``E = Re <psi|lambda>``, then
+        one backward walk (``pauli_rotations_adjoint``) whose values give ``dE/dtheta_k = Im <lambda_k|P_k|psi_k>``.
+        About three times the passes of the forward list whatever its length, where the parameter-shift rule runs the
+        circuit twice per angle.  ``self`` holds the input state again on return (up to rounding).  ``H`` must be
+        hermitian: real coefficients.  Both lists are checked, and the scratch register is allocated, before ``self`` is
+        touched: a refused call leaves it bit for bit as it was."""
+        terms = _real_terms(terms, "the gradient")
+        _check_terms(terms, self.num_qubits)
+        rotations = [(float(theta), str(paulis), [int(q) for q in qs]) for theta, paulis, qs in rotations]
+        lam = DeviceState.zeros(self.num_qubits, self.device)
+        try:
+            self.apply_pauli_rotations(rotations)          # refuses a bad rotation before its first launch
+            self.apply_pauli_sum(terms, out=lam)
+            energy = self.inner(lam).real
+            values = self.pauli_rotations_adjoint(rotations, lam)
+        finally:
+            lam.close()
+        return energy, np.ascontiguousarray(values.imag)
 
     def sample(self, shots: int, rng=None) -> np.ndarray:
         """``shots`` computational-basis outcomes drawn from |amplitude|^2 (inverse-CDF on the device; the uniforms
@@ -501,6 +607,21 @@ class DensityState(DeviceState):
         self._pauli_rotations(rotations)
         self._pauli_rotations(rotations, qubit_offset=n, conjugate=True)
         return self
+
+    def apply_pauli_sum(self, terms, out=None, accumulate: bool = False):
+        raise ValueError("apply_pauli_sum is not defined for a density register: H rho is out of scope")
+
+    def transition_pauli_sum(self, terms, ket, *, return_terms: bool = False):
+        raise ValueError("transition_pauli_sum is not defined for a density register")
+
+    def variance_pauli_sum(self, terms):
+        raise ValueError("variance_pauli_sum is not defined for a density register")
+
+    def pauli_rotations_adjoint(self, rotations, lam):
+        raise ValueError("pauli_rotations_adjoint is not defined for a density register")
+
+    def energy_and_gradient(self, rotations, terms):
+        raise ValueError("energy_and_gradient is not defined for a density register")
 
     def purity(self) -> float:
         """``tr(rho rho)`` for a hermitian ``rho`` (``npq.purity``): the squared norm of the flattened register."""

@@ -319,6 +319,66 @@ def evolve(hamiltonian: PauliSum, state, t: float, steps: int = 1, order: int = 
     return state.to_numpy() if host else state
 
 
+def _lift(hamiltonian: PauliSum, state):
+    """(register, whether ``state`` was a host ket that had to be uploaded); sizes checked as ``expect_pauli_sum`` does.
+    The caller closes a register that was uploaded for it once its result is on the host."""
+    from ..device import DeviceState
+    host = not isinstance(state, DeviceState)
+    if host:
+        state = DeviceState.from_numpy(np.asarray(state))
+    if state.num_qubits != hamiltonian.n_qubits:
+        if host:
+            state.close()
+        raise TypeError("incompatible operator and state vector")
+    return state, host
+
+
+def apply_pauli_sum(hamiltonian: PauliSum, state):
+    """``H state`` on the device (``DeviceState.apply_pauli_sum``).  A register gives a new register and is left as it
+    is; a host ket is uploaded first and ``H ket`` is downloaded, as ``evolve`` lifts host arrays."""
+    state, host = _lift(hamiltonian, state)
+    if not host:
+        return state.apply_pauli_sum(hamiltonian.terms)
+    try:
+        out = state.apply_pauli_sum(hamiltonian.terms)
+        try:
+            return out.to_numpy()
+        finally:
+            out.close()
+    finally:
+        state.close()
+
+
+def transition(hamiltonian: PauliSum, bra, ket) -> complex:
+    """``<bra| H |ket>`` on the device (``DeviceState.transition_pauli_sum``); host kets are uploaded first, and their
+    registers are released once the value is on the host."""
+    uploaded = []
+    try:
+        bra, host = _lift(hamiltonian, bra)
+        if host:
+            uploaded.append(bra)
+        ket, host = _lift(hamiltonian, ket)
+        if host:
+            uploaded.append(ket)
+        return bra.transition_pauli_sum(hamiltonian.terms, ket)
+    finally:
+        for register in uploaded:
+            register.close()
+
+
+def energy_and_gradient(hamiltonian: PauliSum, rotations, state):
+    """``(E, dE/dtheta)`` of ``E(theta) = <state| U(theta)^dagger H U(theta) |state>`` for the rotation list
+    ``[(theta, letters, qubits), ...]`` by the adjoint method (``DeviceState.energy_and_gradient``): the cost of about
+    three circuit runs whatever the number of angles.  A register holds its input state again afterwards; a host ket is
+    uploaded first and left untouched."""
+    state, host = _lift(hamiltonian, state)
+    try:
+        return state.energy_and_gradient(rotations, hamiltonian.terms)
+    finally:
+        if host:
+            state.close()
+
+
 # ---- sizes ----------------------------------------------------------------------------------------------------------
 def is_power_of_two(n: int) -> bool:
     return n > 0 and n & (n - 1) == 0

@@ -265,6 +265,28 @@ int qsv_pauli_transition_sum(qsv_state *bra, qsv_state *ket, int n_terms, const 
  * returns with both registers finished.  n_terms = 0 does nothing. */
 int qsv_pauli_rotations_adjoint(qsv_state *psi, qsv_state *lambda, int n_terms, const int *term_offsets, const int *qubits,
                                 const char *paulis, const double *thetas, double *values, uint64_t *passes);
+/* Multi-register BLAS-1 passes (csrc/qsv_krylov.hip): what Lanczos and Krylov evolution need next
+ * to qsv_apply_pauli_sum.  All operands are qubit registers (QSV_ESTATE for a mode register) on one device and of one
+ * size (QSV_EINVAL); null handles, null arrays and negative counts are refused.  Everything is validated before any
+ * deferred queue is flushed; then every operand's queue is flushed, the streams of the registers that are only read are
+ * synchronised, and the launches go back to back on dst's (y's) stream.  passes (may be NULL) = kernel launches.
+ *
+ * qsv_lincomb: dst = beta dst + sum_k c_k src_k, k < n_src; coeffs holds n_src interleaved complex c_k, beta =
+ * (beta_re, beta_im).  A pass takes up to 8 sources, loads each once (exactly as many streams as it has sources),
+ * loads dst once only if its beta is not exactly 0, and stores dst once: ceil(n_src / 8) passes, at least one; the first
+ * uses beta, the others 1.  With beta == 0 the old dst is never read (NaN in it does not spread) and dst takes the
+ * sources' size if it has the room (QSV_ENOMEM), as in qsv_copy; otherwise it must have that size already.  n_src = 0
+ * scales dst by beta (zeroes it for beta == 0).  dst's memory must not meet a source's (address ranges are compared:
+ * QSV_EINVAL; fold dst's own coefficient into beta); sources may repeat and overlap.  norm2 (may be NULL) receives
+ * ||dst||^2 after the update, formed in the last pass from the values it stores -- no extra read of dst -- and summed
+ * on the host in index order; asking for it costs one copy and one synchronisation.
+ *
+ * qsv_inner_many: values[2k], values[2k+1] = <x_k|y> (x_k conjugated), k < n_x.  A pass reads y once and up to 8 x_k
+ * once each; all passes are launched back to back, then one copy and one synchronisation per call.  One partial per
+ * workgroup and x_k, summed by the host in index order: the same call gives the same bits.  x_k may be y.  Read-only. */
+int qsv_lincomb(qsv_state *dst, double beta_re, double beta_im, int n_src, qsv_state *const *srcs, const double *coeffs,
+                double *norm2, uint64_t *passes);
+int qsv_inner_many(qsv_state *y, int n_x, qsv_state *const *xs, double *values, uint64_t *passes);
 /* Reduced density matrix of the k <= 6 qubits `qubits` (all others traced out) in one read pass over the register:
  * rho[i][j] = sum_rest psi[i, rest] conj(psi[j, rest]), written row-major as 4^k complex numbers, qubits[0] the most
  * significant bit of i and j.  What a caller of the reference gets from npq.ket2dm (numpy_quantum.py:110-113)

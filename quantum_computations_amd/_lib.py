@@ -68,6 +68,8 @@ SIGNATURES: dict[str, list] = {
     "qsv_apply_pauli_sum": [_state_p, _state_p, C.c_int, _int_p, _int_p, C.c_char_p, _dbl_p, C.c_int, _u64_p],
     "qsv_pauli_transition_sum": [_state_p, _state_p, C.c_int, _int_p, _int_p, C.c_char_p, _dbl_p, _dbl_p, _dbl_p, _dbl_p, _u64_p],
     "qsv_pauli_rotations_adjoint": [_state_p, _state_p, C.c_int, _int_p, _int_p, C.c_char_p, _dbl_p, _dbl_p, _u64_p],
+    "qsv_lincomb": [_state_p, C.c_double, C.c_double, C.c_int, C.POINTER(_state_p), _dbl_p, _dbl_p, _u64_p],
+    "qsv_inner_many": [_state_p, C.c_int, C.POINTER(_state_p), _dbl_p, _u64_p],
     "qsv_reduced_density": [_state_p, C.c_int, _int_p, C.c_void_p],
     "qsv_expect_density": [_state_p, _state_p, _dbl_p, _dbl_p],
     "qsv_sample": [_state_p, C.c_int, C.c_void_p, C.c_void_p],

@@ -491,6 +491,55 @@ class DeviceState:
         _lib.call("qsv_inner", self._h, other._h, C.byref(re), C.byref(im))
         return complex(re.value, im.value)
 
+    # ---- several registers in one pass -----------------------------------
+    def lincomb(self, coeffs, sources, beta: complex = 0.0, return_norm2: bool = False):
+        """In place ``self = beta self + sum_k coeffs[k] sources[k]`` (``qsv_lincomb``): up to eight sources per pass,
+        each read once, ``self`` read only where ``beta != 0`` and written once per pass.  ``self`` may not be among
+        the sources (fold its coefficient into ``beta``); with ``beta == 0`` its old contents are never read and it
+        takes the sources' size.  Returns ``self``, or ``(self, ||self||^2)`` with ``return_norm2`` -- the norm comes
+        out of the last pass, from the values it stores, at the price of one synchronisation."""
+        norm2, _ = self._lincomb(coeffs, sources, beta, return_norm2)
+        return (self, norm2) if return_norm2 else self
+
+    def _lincomb(self, coeffs, sources, beta: complex = 0.0, want_norm2: bool = False) -> tuple[float | None, int]:
+        """``lincomb``; returns (||self||^2 or None, kernel launches)."""
+        sources = list(sources)
+        cbuf = np.ascontiguousarray(coeffs, dtype=np.complex128).reshape(-1)
+        if cbuf.size != len(sources):
+            raise ValueError("one coefficient per source register")
+        beta = complex(beta)
+        handles = (C.c_void_p * max(len(sources), 1))(*[s._h for s in sources])
+        norm2, passes = C.c_double(), C.c_uint64()
+        _lib.call("qsv_lincomb", self._h, beta.real, beta.imag, len(sources), handles, _dbl(cbuf.view(np.float64)),
+                  C.byref(norm2) if want_norm2 else None, C.byref(passes))
+        return (norm2.value if want_norm2 else None), passes.value
+
+    def inner_many(self, others) -> np.ndarray:
+        """Complex array of ``<others[k]|self>`` (``qsv_inner_many``): ``self`` is read once per eight ``others``, each
+        of them once; one synchronisation per call.  ``others[k]`` may be ``self``."""
+        return self._inner_many(others)[0]
+
+    def _inner_many(self, others) -> tuple[np.ndarray, int]:
+        """``inner_many``; returns (values, kernel launches)."""
+        others = list(others)
+        handles = (C.c_void_p * max(len(others), 1))(*[o._h for o in others])
+        values = np.zeros(len(others), dtype=np.complex128)
+        passes = C.c_uint64()
+        _lib.call("qsv_inner_many", self._h, len(others), handles, _dbl(values.view(np.float64)), C.byref(passes))
+        return values, passes.value
+
+    def ground_state_of(self, terms, **options):
+        """Ground state of ``H = sum_t c_t P_t`` by restarted Lanczos started from this register (``krylov.ground_state``;
+        holds ``m + 2`` registers of this size).  Returns ``(energy, state, info)``; ``self`` is not changed."""
+        from . import krylov
+        return krylov.ground_state(terms, self, **options)
+
+    def evolve_krylov(self, terms, t: float, **options) -> dict:
+        """In place ``exp(-i t H) self`` without Trotter error (``krylov.evolve_krylov``; holds ``m + 2`` registers of
+        this size).  Returns ``info``."""
+        from . import krylov
+        return krylov.evolve_krylov(self, terms, t, **options)
+
     def reduced_density(self, qubits) -> np.ndarray:
         """Reduced density matrix of ``qubits`` (at most six; everything else traced out) as a host
         ``(2^k, 2^k)`` array, ``qubits[0]`` the most significant bit of both indices.  One read pass on the device."""
@@ -622,6 +671,12 @@ class DensityState(DeviceState):
 
     def energy_and_gradient(self, rotations, terms):
         raise ValueError("energy_and_gradient is not defined for a density register")
+
+    def ground_state_of(self, terms, **options):
+        raise ValueError("ground_state_of is not defined for a density register")
+
+    def evolve_krylov(self, terms, t, **options):
+        raise ValueError("evolve_krylov is not defined for a density register")
 
     def purity(self) -> float:
         """``tr(rho rho)`` for a hermitian ``rho`` (``npq.purity``): the squared norm of the flattened register."""

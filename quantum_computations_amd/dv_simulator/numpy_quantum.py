@@ -379,6 +379,44 @@ def energy_and_gradient(hamiltonian: PauliSum, rotations, state):
             state.close()
 
 
+def ground_state(hamiltonian: PauliSum, state=None, **options):
+    """``(energy, ground state, info)`` of a hermitian ``PauliSum`` by restarted Lanczos on the device
+    (``krylov.ground_state``, whose keyword options pass through; ``m + 2`` registers of the state's size).  ``state``:
+    the start vector -- None for a random ket (``seed``), a register (left as it is; a new register is returned), or a
+    host ket, which is uploaded first, left untouched, and answered with a host ket."""
+    from .. import krylov
+    if state is None:
+        return krylov.ground_state(hamiltonian.terms, hamiltonian.n_qubits, **options)
+    state, host = _lift(hamiltonian, state)
+    try:
+        energy, ground, info = krylov.ground_state(hamiltonian.terms, state, **options)
+        if not host:
+            return energy, ground, info
+        try:
+            return energy, ground.to_numpy(), info
+        finally:
+            ground.close()
+    finally:
+        if host:
+            state.close()
+
+
+def evolve_exact(hamiltonian: PauliSum, state, t: float, **options):
+    """``exp(-i t H) state`` by Krylov evolution on the device, without Trotter error (``krylov.evolve_krylov``, whose
+    keyword options pass through; ``m + 2`` registers of the state's size).  A register is evolved in place and returned;
+    a host ket is uploaded first, left untouched, and the evolved ket is downloaded, as ``evolve`` lifts host arrays."""
+    from .. import krylov
+    state, host = _lift(hamiltonian, state)
+    if not host:
+        krylov.evolve_krylov(state, hamiltonian.terms, t, **options)
+        return state
+    try:
+        krylov.evolve_krylov(state, hamiltonian.terms, t, **options)
+        return state.to_numpy()
+    finally:
+        state.close()
+
+
 # ---- sizes ----------------------------------------------------------------------------------------------------------
 def is_power_of_two(n: int) -> bool:
     return n > 0 and n & (n - 1) == 0

@@ -1,0 +1,738 @@
+"""The kernel forms that only non-default tuning options select (include/qsv.h: QSV_OPT_NONTEMPORAL, QSV_OPT_UNROLL,
+QSV_OPT_TILE_REGIONS, QSV_OPT_ITEM_STRIDE_BIT, QSV_OPT_GRID_CAP), at the smallest registers where each of them engages.
+
+Method.  Every case fills two registers from one seed, one with default options and one with the options under test, and
+applies the same operations to both.
+
+1. The two registers agree bit for bit (``np.array_equal``): the options change which thread handles which amplitude and
+   the cache hint of loads and stores, never the arithmetic of an amplitude.  Exceptions, found by reading the launchers:
+
+   * An explicit QSV_OPT_UNROLL takes 1-qubit gates (plain or controlled) off the workgroup-tile form and onto the register
+     form (qsvk_dense, qsv_kernels.hip:2061).  With the target on bits 3..5 that is k_dense_tile12<1>, which sums the two
+     matrix columns in index order (tile12_body, :1355), against k_dense<0, 1, U> / k_dense_ctrl<0, 1, U>, whose lanes add
+     their OWN amplitude first and the partner's second (dense_body, :101-106): the lanes with the target bit set sum in
+     the other order.  Those gates are held to the oracle alone, and the register under test is then overwritten with the
+     default one so that the next gate starts from equal bits.  On every other placement the two forms sum alike and are
+     compared bit for bit.
+   * QSV_OPT_GRID_CAP changes the number of workgroups of k_lincomb's norm form (reduce_grid, qsv_krylov_layout.h:51) and
+     with it the number and contents of the partial sums the host adds (qsv_krylov.hip:127-129): ``norm2`` is held to its
+     existing bound alone; the amplitudes that pass stores are still compared bit for bit.
+
+   * QSV_OPT_TILE_REGIONS changes which tiles a workgroup of k_rdm_tile accumulates and in which order (``place``,
+     qsv_readout.hip:594-597): a reduced density matrix under it is held to the oracle alone.
+
+2. The default register agrees with the CPU oracle within the project's existing tolerance for the operation: ``1e-11 *
+   scale`` for gates, measure / insert / permute and Pauli expectations and ``1e-12 * scale`` for reduced density matrices
+   (tools/fuzz_gates.py), the bounds of tests/test_gpu_pauli_*.py and tests/test_gpu_krylov.py for those calls, ``1e-11 *
+   scale`` for mode operators (tools/fuzz_modes.py).  So an error the two registers share cannot hide.
+
+3. ``last_kernel()`` names the instantiation that ran; the names seen are collected over the module and the last test
+   asserts that the NT = false and the U = 4 / U = 8 forms of every family appear.
+
+Dense gates use Haar-random matrices, so a skipped or doubled work item changes amplitudes.
+
+Which launcher reads which option (grep of csrc/ for ``->nontemporal``, ``->grid_cap``, ``->remap``, ``->unroll``, ``->ubit``):
+
+====================================================  ==============================================  ==================
+family (launcher)                                     options honoured                                smallest n / d here
+====================================================  ==============================================  ==================
+k_dense, k_dense_ctrl (launch_dense)                  NONTEMPORAL UNROLL TILE_REGIONS STRIDE_BIT CAP  n = 13
+k_diag (launch_diag)                                  NONTEMPORAL UNROLL TILE_REGIONS CAP             n = 13
+k_dense_tile12, k_dense_tile12_ctrl (launch_tile12)   NONTEMPORAL TILE_REGIONS; UNROLL != 0 leaves it n = 14
+k_dense_tile / _lds / _big (launch_dense_big)         NONTEMPORAL TILE_REGIONS                        n = 13
+k_pass_tile (qsvk_pass)                               NONTEMPORAL TILE_REGIONS                        n = 15
+k_diag_table*, k_generic                              none                                            --
+read-out: k_measure_probs*, k_collapse*, k_insert*,   none (nontemporal accesses are unconditional,   n = 14
+  k_permute*, norm2, inner, probabilities, sample,    grids fixed); k_rdm_tile / k_rdm take
+  expect_pauli, reduced_density                       TILE_REGIONS (rdm_plan)
+k_pauli_rotate_group (apply_pauli_rotations)          NONTEMPORAL (pivot >= 3 or diagonal) CAP        n = 13
+k_pauli_sum_apply_group (apply_pauli_sum, of dst)     NONTEMPORAL (pivot >= 3 or diagonal) CAP        n = 13
+k_pauli_adjoint_group (pauli_rotations_adjoint)       NONTEMPORAL (pivot >= 3 or diagonal)            n = 13
+expect_pauli_sum, transition_pauli_sum                none                                            n = 13
+k_lincomb (of dst)                                    NONTEMPORAL CAP                                 n = 13
+k_mode2_plane (mode2_blocks, real, last two modes)    NONTEMPORAL                                     (3, 8)
+mode1, mode2, mode2_diag, mode2_gather, k_mode2_blocks none of their own (d = 8 = 2^3: mode1 / mode2    (3, 8)
+                                                      run the qubit kernels above)
+====================================================  ==============================================  ==================
+
+Worst errors are printed (run with -s).
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import pauli_operator_reference as P
+import pauli_rotation_reference as R
+from oracle import cv_oracle as CO
+from oracle import dv_oracle as O
+from quantum_computations_amd import _lib
+from quantum_computations_amd import workloads as W
+from quantum_computations_amd.device import DeviceState, QuditState
+from quantum_computations_amd.dv_simulator import gates as G
+from test_gpu_krylov import lincomb_model
+from test_gpu_pass_groups import Bits, mixed_circuit
+
+pytestmark = pytest.mark.gpu
+
+GATE_TOL = 1e-11            # tools/fuzz_gates.py: gates, measure / insert / permute, Pauli expectations (times the scale)
+RDM_TOL = 1e-12             # tools/fuzz_gates.py: reduced density matrices (times the scale)
+TERM_TOL = 1e-13            # tests/test_gpu_pauli_sum.py, test_gpu_pauli_operator.py, test_gpu_krylov.py
+CIRCUIT_TOL = 1e-12         # tests/test_gpu_pauli_rotation.py: a list of at most 100 rotations
+ADJOINT_TOL = 1e-12         # tests/test_gpu_pauli_operator.py
+MODE_TOL = 1e-11            # tools/fuzz_modes.py
+BLOCK = 256                 # QSV_BLOCK
+
+SEEN: set = set()           # every last_kernel() name of a register with non-default options
+
+
+def maxdiff(a, b):
+    return float(np.max(np.abs(np.asarray(a) - np.asarray(b))))
+
+
+def scale_of(want):
+    return max(1.0, float(np.max(np.abs(want))))
+
+
+def saw(dev):
+    name = dev.last_kernel()
+    SEEN.add(name)
+    return name
+
+
+def tf(flag):
+    return "true" if flag else "false"
+
+
+# ---- per-gate kernels -----------------------------------------------------------------------------------------------------------
+def launch_model(W_items, unroll, regions, ubit, cap):
+    """launch_dense (qsv_kernels.hip:830-857) for W work items: (U after halving, stride bit after the clamp, tiles,
+    whether the tile order is a real permutation, trips of the grid-stride loop)."""
+    U = max(unroll, 1)
+    while U > 1 and W_items < BLOCK * U:
+        U >>= 1
+    while ubit > 8 and (W_items >> ubit) < U:
+        ubit -= 1
+    tiles = -(-W_items // (BLOCK * U))
+    remapped = regions > 1 and tiles % regions == 0 and tiles > regions
+    trips = -(-tiles // cap) if cap else 1
+    return U, ubit, tiles, remapped, trips
+
+
+# (id, n, NONTEMPORAL, UNROLL, TILE_REGIONS, ITEM_STRIDE_BIT, GRID_CAP, high, low): ``high`` is what launch_model gives for
+# a 1-qubit gate on a bit >= 6 (W = 2^(n-1) pairs), ``low`` for one on a lane bit and for a full-traffic diagonal (W = 2^n),
+# each as (U, stride bit, tiles, remapped, trips); test_each_setting_meets_its_engagement_condition checks them against the
+# model, test_per_gate_kernels checks U against last_kernel().  Engaged means: W >= 256 U (U not halved), (W >> ubit) >= U
+# (stride bit not clamped), tiles % R == 0 and tiles > R (the tile order is not the identity).
+# The set is pruned, not the full product: every value of every option occurs, every (NONTEMPORAL, x) and (UNROLL, x) pair
+# of values occurs; pairs among TILE_REGIONS, ITEM_STRIDE_BIT and GRID_CAP only as listed.
+SETTINGS = [
+    # U = 4, ubit = 10 and R = 2 all engaged on both classes; two and three trips under the cap
+    ("A", 13, 0, 4, 2, 10, 3, (4, 10, 4, True, 2), (4, 10, 8, True, 3)),
+    # U = 8 engaged; R = 2 is the identity on the 2 tiles of a high target, engaged on the 4 tiles of W = 2^13
+    ("B", 13, 1, 8, 2, 8, 0, (8, 8, 2, False, 1), (8, 8, 4, True, 1)),
+    # every clamp fires: ubit 12 -> 9 (high) / 10 (low), R = 32 divides neither 2 nor 4 tiles, and the gate with three
+    # controls (W = 2^9 < 256 * 8) has U halved to 2
+    ("C", 13, 0, 8, 32, 12, 7, (8, 9, 2, False, 1), (8, 10, 4, False, 1)),
+    # U = 4 and ubit = 10 engaged; R = 8 is the identity on 8 tiles (high), engaged on 16 (low)
+    ("D", 14, 1, 4, 8, 10, 7, (4, 10, 8, False, 2), (4, 10, 16, True, 3)),
+    # plain tile order (R = 0) with U = 8; two and three trips
+    ("E", 14, 0, 8, 0, 8, 3, (8, 8, 4, False, 2), (8, 8, 8, False, 3)),
+    # ubit = 12 is clamped to 11 on a high target ((2^13 >> 12) = 2 < 4), engaged on W = 2^14; R = 2 engaged on both
+    ("F", 14, 0, 4, 2, 12, 0, (4, 11, 8, True, 1), (4, 12, 16, True, 1)),
+    # U = 4 with ubit = 12 engaged on both; R = 32 is the identity on 32 tiles (high), engaged on 64 (low)
+    ("G", 16, 0, 4, 32, 12, 0, (4, 12, 32, False, 1), (4, 12, 64, True, 1)),
+    # U = 8 with ubit = 12 engaged ((2^15 >> 12) = 8 >= 8); R = 2 engaged; 6 and 11 trips
+    ("H", 16, 1, 8, 2, 12, 3, (8, 12, 16, True, 6), (8, 12, 32, True, 11)),
+    # U = 8, ubit = 10, R = 8 engaged on both; 3 and 5 trips
+    ("I", 16, 0, 8, 8, 10, 7, (8, 10, 16, True, 3), (8, 10, 32, True, 5)),
+    # U = 4, plain order, 5 and 10 trips
+    ("J", 16, 1, 4, 0, 8, 7, (4, 8, 32, False, 5), (4, 8, 64, False, 10)),
+    # one item per thread: R = 32 engaged on the 128 tiles of a high target too; 43 and 86 trips
+    ("M", 16, 0, 1, 32, 8, 3, (1, 8, 128, True, 43), (1, 8, 256, True, 86)),
+    # U = 2 (so far tested at n <= 14 in default order only), ubit = 10, R = 8 engaged
+    ("N", 16, 1, 2, 8, 10, 0, (2, 10, 64, True, 1), (2, 10, 128, True, 1)),
+    # UNROLL = 0 keeps the workgroup-tile forms (k_dense_tile12*: 64 columns per tile, 2^(n-1) / 64 = 512 / 128 tiles, which
+    # R = 32 / 2 / 8 divide) and the built-in U of k_dense / k_diag (1, and 4 for sub-space diagonals); the cap bounds the
+    # grids of k_dense and k_diag only
+    ("K", 16, 0, 0, 32, 8, 3, None, None),
+    ("L", 14, 0, 0, 2, 8, 0, None, None),
+    ("P", 16, 1, 0, 8, 8, 7, None, None),
+]
+
+
+def test_each_setting_meets_its_engagement_condition():
+    for name, n, nt, unroll, regions, ubit, cap, high, low in SETTINGS:
+        if unroll:
+            assert launch_model(1 << (n - 1), unroll, regions, ubit, cap) == high, name
+            assert launch_model(1 << n, unroll, regions, ubit, cap) == low, name
+    engaged = [s for s in SETTINGS if s[7] is not None]
+    assert all(s[7][0] == s[3] and s[8][0] == s[3] for s in engaged)                             # U as asked on both classes
+    assert any(s[7][1] == s[5] > 8 for s in engaged) and any(s[7][1] < s[5] for s in engaged)    # stride bit kept, and clamped
+    assert any(s[7][3] for s in engaged) and any(s[4] > 1 and not s[7][3] for s in engaged)      # remapped, and R not dividing
+    assert launch_model(1 << 9, 8, 32, 12, 7)[0] == 2                                            # setting C, three controls
+
+
+def gate_list(n, seed):
+    """The operations of one per-gate case, placed by index bit (qubit q is bit n - 1 - q)."""
+    rng = np.random.default_rng(seed)
+    q = lambda *bits: [n - 1 - b for b in bits]
+    phases = lambda count: np.exp(1j * rng.uniform(0, 6.28, count))
+    ops = []
+    for b in range(n):                                                   # a Haar 2x2 on every bit
+        ops.append(("u", W.haar_unitary(2, rng), q(b), f"1q bit {b}"))
+    # Haar 4x4: low-low, low-high, high-high (lane bits are 0..5), both leg orders
+    for pair in ((1, 4), (4, 1), (2, n - 1), (n - 2, 3), (5, 7), (6, n - 1), (n - 1, 7), (8, 9)):
+        ops.append(("u", W.haar_unitary(4, rng), q(*pair), f"2q bits {pair}"))
+    # controlled-U: one control (outside the lanes, inside them, below bit 3 where it is folded into a 4x4), three controls
+    for ctrl, target in (((n - 1,), 7), ((9,), 4), ((4,), n - 2), ((1,), 8), ((n - 1, 8, 3), 10), ((7, 9, 11), 2)):
+        ops.append(("cu", W.haar_unitary(2, rng), q(*ctrl), q(target)[0], f"controls {ctrl} target {target}"))
+    for bits in ((2,), (n - 1,), (3, n - 2), (n - 1, 6)):                # full-traffic diagonals
+        ops.append(("diag", phases(1 << len(bits)), q(*bits), f"diagonal bits {bits}"))
+    ops.append(("diag", np.array([1.0, -1.0]), q(0), "Z bit 0"))         # below bit 3: full traffic
+    ops.append(("diag", np.array([1.0, -1.0]), q(n - 1), f"Z bit {n - 1}"))          # sub-space k_diag
+    ops.append(("diag", np.array([1.0, 1.0, 1.0, -1.0]), q(n - 1, 7), "CZ high-high"))
+    ops.append(("diag", np.array([1.0, 1.0, 1.0, -1.0]), q(1, 9), "CZ low-high"))
+    ops.append(("mcphase", q(4, 8, n - 1, n - 3), phases(1)[0], "multi-controlled phase"))
+    for pair in ((6, n - 1), (2, 9), (3, 4)):                            # pair exchange; SWAP as a dense 4x4
+        ops.append(("swap", *q(*pair), f"SWAP bits {pair}"))
+    # k = 3 on bits >= 3 (k_dense_tile), k = 4 with a bit inside a line (k_dense_big, transposed), k = 5 with lane bits
+    # (k_dense_lds) and on high bits (k_dense_big<5, 0>): the forms that read regions_or
+    for bits in ((n - 1, 7, 9), (1, 6, n - 2, 10), (0, 4, 8, n - 1, 11), (6, 8, 9, 11, n - 1)):
+        ops.append(("u", W.haar_unitary(1 << len(bits), rng), q(*bits), f"k = {len(bits)} bits {bits}"))
+    return ops
+
+
+def apply_op(dev, op):
+    kind = op[0]
+    if kind == "u":
+        dev.apply_matrix(op[1], op[2])
+    elif kind == "cu":
+        dev.apply_controlled(op[1], op[2], op[3])
+    elif kind == "diag":
+        dev.apply_diagonal(op[1], op[2])
+    elif kind == "mcphase":
+        dev.apply_mcphase(op[1], op[2])
+    else:
+        dev.apply_swap(op[1], op[2])
+
+
+def oracle_op(ket, op):
+    kind = op[0]
+    if kind == "u":
+        return O.apply_gate(ket, op[1], op[2])
+    if kind == "cu":
+        legs = list(op[2]) + [op[3]]
+        full = np.identity(1 << len(legs), dtype=complex)
+        full[-2:, -2:] = op[1]
+        return O.apply_gate(ket, full, legs)
+    if kind == "diag":
+        return O.apply_gate(ket, np.diag(op[1]), op[2])
+    if kind == "mcphase":
+        d = np.ones(1 << len(op[1]), dtype=complex)
+        d[-1] = op[2]
+        return O.apply_gate(ket, np.diag(d), op[1])
+    return O.apply_gate(ket, np.identity(4)[[0, 2, 1, 3]].astype(complex), [op[1], op[2]])
+
+
+def other_summation_order(default_name, name):
+    """The one exception of the module docstring: tile form by default, lane-bit register form under an explicit UNROLL."""
+    return default_name.startswith("k_dense_tile12") and (name.startswith("k_dense<0, 1,") or name.startswith("k_dense_ctrl<0, 1,"))
+
+
+@pytest.mark.parametrize("setting", SETTINGS, ids=[s[0] for s in SETTINGS])
+def test_per_gate_kernels(setting):
+    name, n, nt, unroll, regions, ubit, cap, high, low = setting
+    seed = 100 + ord(name)
+    ref, opt = DeviceState.random(n, seed), DeviceState.random(n, seed)
+    for dev in (ref, opt):
+        dev.set_option(_lib.OPT_DEFER, 0)
+    for option, value in ((_lib.OPT_NONTEMPORAL, nt), (_lib.OPT_UNROLL, unroll), (_lib.OPT_TILE_REGIONS, regions),
+                          (_lib.OPT_ITEM_STRIDE_BIT, ubit), (_lib.OPT_GRID_CAP, cap)):
+        opt.set_option(option, value)
+    want = ref.to_numpy()
+    assert np.array_equal(opt.to_numpy(), want)
+    failures, worst, excepted, differed = [], 0.0, 0, 0
+    for op in gate_list(n, seed):
+        label = op[-1]
+        apply_op(ref, op)
+        apply_op(opt, op)
+        default_name, opt_name = ref.last_kernel(), saw(opt)
+        want = oracle_op(want, op)
+        got_ref, got_opt = ref.to_numpy(), opt.to_numpy()
+        err = maxdiff(got_ref, want)
+        worst = max(worst, err)
+        if not err < GATE_TOL * scale_of(want):
+            failures.append((label, default_name, "default register against the oracle", err))
+        if other_summation_order(default_name, opt_name):
+            excepted += 1
+            differed += int(not np.array_equal(got_opt, got_ref))
+            err_opt = maxdiff(got_opt, want)
+            if not err_opt < GATE_TOL * scale_of(want):
+                failures.append((label, opt_name, "against the oracle", err_opt))
+            ref.copy_into(opt)                                           # equal bits again for the next gate
+        elif not np.array_equal(got_opt, got_ref):
+            failures.append((label, default_name, opt_name, maxdiff(got_opt, got_ref), int(np.count_nonzero(got_opt != got_ref))))
+            ref.copy_into(opt)
+        # the intended instantiation ran
+        bit = n - 1 - op[2][0] if op[0] == "u" and len(op[2]) == 1 else None
+        if bit is not None and unroll:
+            expect = f"k_dense<1, 0, {high[0]}, {tf(nt)}>" if bit >= 6 else f"k_dense<0, 1, {low[0]}, {tf(nt)}>"
+            if opt_name != expect:
+                failures.append((label, "ran", opt_name, "expected", expect))
+        if bit is not None and not unroll and bit >= 3 and opt_name != f"k_dense_tile12<1, {tf(nt)}>":
+            failures.append((label, "ran", opt_name, "expected the tile form"))
+        if label.startswith("diagonal") and unroll and opt_name != f"k_diag<{low[0]}, {tf(nt)}>":
+            failures.append((label, "ran", opt_name, "expected", f"k_diag<{low[0]}, {tf(nt)}>"))
+    print(f"setting {name} (n={n} NT={nt} U={unroll} R={regions} ubit={ubit} cap={cap}): worst error against the oracle {worst:.3e}, "
+          f"{excepted} gates compared with the oracle alone ({differed} of them differ from the default register in some bit)")
+    assert not failures, failures
+    assert excepted == (4 if unroll else 0)          # 1-qubit gates on bits 3, 4, 5 and the controlled-U with its target on bit 4
+    ref.close()
+    opt.close()
+
+
+# ---- the deferred pass kernel ----------------------------------------------------------------------------------------------------
+def subset_passes(n, subsets, seed):
+    """One pass per subset of six high tile bits: dense targets on exactly those bits (and on lane bits), so the planner
+    has no other choice of tile; 2x2 and 4x4 gates on tile x lane and tile x tile pairs, both leg orders."""
+    c = Bits(n, seed)
+    for k, s in enumerate(subsets):
+        s = sorted(s)
+        for i, b in enumerate(s):
+            c.u1(b)
+            lane = (k + 2 * i) % 6
+            if i % 2:
+                c.u2(b, lane)
+            else:
+                c.u2(lane, b)
+        c.u2(s[0], s[5])
+        c.u2(s[4], s[1])
+        c.u2(s[2], s[3])
+        c.u1(k % 6)
+    return c.ops
+
+
+def outside_controls(n, every_tile, controls=None):
+    """Tile = bits 0..11 (dense targets on every one of bits 6..11); CX / CU / CZ controlled from each bit outside the tile
+    in turn and a CZ with both bits outside.  Without ``every_tile`` every gate of the pass is controlled from outside: the
+    tiles whose outside bits are all 0 are never loaded and must come back unchanged."""
+    c = Bits(n, 7 * n + every_tile)
+    outside = list(range(12, n)) if controls is None else controls
+    for i, o in enumerate(outside):
+        c.named("CX", o, 6 + i % 6)
+        c.cu(o, 6 + (i + 1) % 6)
+        c.cu(o, 6 + (i + 2) % 6)
+        c.named("CZ", o, 6 + (i + 3) % 6)
+        c.cu(o, 6 + (i + 4) % 6)
+        c.cu(o, 6 + (i + 5) % 6)
+        c.cu(o, i % 6)
+    c.named("CZ", outside[0], outside[-1] if len(outside) > 1 else 3)
+    if every_tile:
+        c.u2(9, 2)
+    return c.ops
+
+
+def sixty_four(n):
+    c = Bits(n, 64)
+    for i in range(70):
+        if i % 3 == 2:
+            c.u2(i % 12, (i + 5) % 12)
+        else:
+            c.u1((5 * i) % 12)
+    return c.ops
+
+
+def random_subsets(seed):
+    rng = np.random.default_rng(seed)
+    return [sorted(int(b) for b in rng.choice(np.arange(6, 18), size=6, replace=False)) for _ in range(2)]
+
+
+# name -> (n, seed, ops, passes expected or None); tiles = 2^(n-12): 8 at n = 15, 16 at n = 16, 64 at n = 18
+PASS_CIRCUITS = {
+    "subsets-18": (18, 1, subset_passes(18, [range(12, 18), range(6, 18, 2), range(7, 18, 2), (6, 7, 8, 15, 16, 17)] + random_subsets(5), 11), 6),
+    "subsets-16": (16, 2, subset_passes(16, [range(10, 16), (6, 8, 10, 12, 14, 15), (6, 7, 8, 13, 14, 15)], 12), 3),
+    "outside-all-18": (18, 3, outside_controls(18, False), 1),
+    "outside-two-18": (18, 4, outside_controls(18, False, [17, 16]), 1),
+    "outside-every-tile-18": (18, 5, outside_controls(18, True), 1),
+    "outside-all-16": (16, 6, outside_controls(16, False), 1),
+    "outside-every-tile-15": (15, 7, outside_controls(15, True), 1),
+    "sixty-four-15": (15, 8, sixty_four(15), 2),
+    "mixed-15": (15, 9, mixed_circuit(15, 60, 15), None),
+    "mixed-16": (16, 10, mixed_circuit(16, 60, 16), None),
+}
+PASS_REFERENCE: dict = {}
+
+
+def pass_reference(name):
+    """(amplitudes of the per-gate default register, of the oracle), computed once per circuit."""
+    if name not in PASS_REFERENCE:
+        n, seed, ops, _ = PASS_CIRCUITS[name]
+        b = DeviceState.random(n, seed)
+        b.set_option(_lib.OPT_DEFER, 0)
+        ket = b.to_numpy()
+        for gate in W.to_gates(ops):
+            gate.apply(b)
+        per_gate = b.to_numpy()
+        assert b.defer_stats() == (0, 0)
+        b.close()
+        want, _ = O.run_circuit(ops, ket)
+        per_gate.setflags(write=False)
+        PASS_REFERENCE[name] = (per_gate, want)
+    return PASS_REFERENCE[name]
+
+
+@pytest.mark.parametrize("name", list(PASS_CIRCUITS))
+def test_per_gate_default_register_of_each_pass_circuit_agrees_with_the_oracle(name):
+    per_gate, want = pass_reference(name)
+    err = maxdiff(per_gate, want)
+    print(f"{name}: {len(PASS_CIRCUITS[name][2])} gates, per-gate path against the oracle {err:.3e}")
+    assert err < GATE_TOL * scale_of(want)
+
+
+# the tile order is a real permutation when tiles % R == 0 and tiles > R (k_pass_tile, qsv_kernels.hip:1822); -1 is the
+# built-in 8 regions: engaged at n = 16 (16 tiles) and n = 18 (64), the identity on the 8 tiles of n = 15, where R = 2 is
+# engaged; R = 16 is engaged at n = 18 only (the identity on 16 tiles, not a divisor of 8)
+@pytest.mark.parametrize("nt", [0, 1])
+@pytest.mark.parametrize("regions", [-1, 0, 2, 8, 16])
+@pytest.mark.parametrize("name", list(PASS_CIRCUITS))
+def test_pass_kernel(name, regions, nt):
+    n, seed, ops, passes = PASS_CIRCUITS[name]
+    per_gate, _ = pass_reference(name)
+    a = DeviceState.random(n, seed)
+    a.set_option(_lib.OPT_DEFER, 2)
+    a.set_option(_lib.OPT_TILE_REGIONS, regions)
+    a.set_option(_lib.OPT_NONTEMPORAL, nt)
+    for gate in W.to_gates(ops):
+        gate.apply(a)
+    got = a.to_numpy()
+    queued, launches = a.defer_stats()
+    kernel = saw(a)
+    a.close()
+    assert np.array_equal(got, per_gate), (np.max(np.abs(got - per_gate)), int(np.count_nonzero(got != per_gate)))
+    assert queued == len(ops) and launches < queued, (queued, launches)          # passes really ran
+    if passes is not None:
+        assert launches == passes and kernel == f"k_pass_tile<{tf(nt)}>", (launches, kernel)
+
+
+# ---- the other families ----------------------------------------------------------------------------------------------------------
+def with_options(dev, nt=0, cap=3, regions=None):
+    dev.set_option(_lib.OPT_NONTEMPORAL, nt)
+    dev.set_option(_lib.OPT_GRID_CAP, cap)
+    if regions is not None:
+        dev.set_option(_lib.OPT_TILE_REGIONS, regions)
+    return dev
+
+
+def test_read_out_calls():
+    """n = 14, the smallest register that takes the streaming forms.  None of these launchers reads NONTEMPORAL or GRID_CAP
+    (table above): every number must be the same bits.  reduced_density honours TILE_REGIONS, which reorders its sum."""
+    n = 14
+    ket, other = W.random_ket(n, 51) * 1.5, W.random_ket(n, 52)
+    ref, opt = DeviceState.from_numpy(ket), with_options(DeviceState.from_numpy(ket))
+    dev_other = DeviceState.from_numpy(other)
+    rng = np.random.default_rng(53)
+    assert ref.norm2() == opt.norm2() and abs(ref.norm2() - 2.25) < 1e-12
+    assert ref.inner(dev_other) == opt.inner(dev_other) and abs(ref.inner(dev_other) - np.vdot(ket, other)) < 1e-13 * 1.5
+    idx = [0, 5, (1 << n) - 1, 1234, 8191, 8192]
+    assert np.array_equal(ref.probabilities(idx), opt.probabilities(idx))
+    assert maxdiff(ref.probabilities(idx), np.abs(ket[idx]) ** 2) < 1e-15
+    for q, theta, phi in ((0, 0.9, 2.2), (6, np.pi / 2, 0.0), (9, 0.4, 1.1), (13, 0.0, 0.0)):
+        eigs = G.M(q, theta, phi).eigenvectors()
+        p_ref, p_opt = ref.measure_probs(q, *eigs), opt.measure_probs(q, *eigs)
+        saw(opt)
+        want_p = [nrm ** 2 for _, nrm in O.measure_branches(ket, q, theta, phi)]
+        assert p_ref == p_opt and maxdiff(p_ref, want_p) < 1e-13 * 2.25, (q, p_ref, p_opt, want_p)
+    for letters, qubits in (("XYZ", [0, 7, 13]), ("ZZ", [3, 12]), ("Y", [13]), ("XX", [12, 13])):
+        e_ref, e_opt = ref.expect_pauli(letters, qubits), opt.expect_pauli(letters, qubits)
+        want_e = np.vdot(ket, R.apply_string(ket, letters, qubits))
+        assert e_ref == e_opt and abs(e_ref - want_e) < GATE_TOL * max(1.0, abs(want_e)), (letters, e_ref, e_opt, want_e)
+    for kept in ([13], [0, 13], [5, 2, 9], [12, 1, 7, 3], [0, 4, 8, 12, 13, 6]):
+        r_ref, r_opt = ref.reduced_density(kept), opt.reduced_density(kept)
+        name = saw(opt)
+        want_r = O.reduced_density(ket, kept)
+        assert np.array_equal(r_ref, r_opt), (kept, name, maxdiff(r_ref, r_opt))
+        assert maxdiff(r_ref, want_r) < RDM_TOL * scale_of(want_r), (kept, name)
+        for regions in (2, 8):                       # another order of the tiles, so of the sum: the oracle alone (docstring)
+            opt.set_option(_lib.OPT_TILE_REGIONS, regions)
+            assert maxdiff(opt.reduced_density(kept), want_r) < RDM_TOL * scale_of(want_r), (kept, regions, saw(opt))
+        opt.set_option(_lib.OPT_TILE_REGIONS, -1)
+    u = np.ascontiguousarray(rng.random(2000))
+    drawn = []
+    for dev in (ref, opt):
+        out = np.empty(len(u), dtype=np.uint64)
+        _lib.call("qsv_sample", dev._h, len(u), u.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+        drawn.append(out)
+    cdf = np.cumsum(np.abs(ket) ** 2)
+    want_idx = np.searchsorted(cdf, u * cdf[-1], side="right")
+    margin = np.minimum(np.abs(cdf[np.minimum(want_idx, len(cdf) - 1)] - u * cdf[-1]),
+                        np.abs(np.concatenate([[0.0], cdf])[want_idx] - u * cdf[-1]))
+    safe = margin > 1e-12
+    assert np.array_equal(drawn[0], drawn[1])
+    assert safe.sum() > 1900 and np.array_equal(drawn[0][safe], want_idx[safe].astype(np.uint64))
+    # collapse, insert, permute: the register changes size and comes back
+    want = ket
+    for q, theta, phi, result in ((13, 0.9, 2.2, 1), (4, 0.3, 0.5, 0)):
+        n_now = O.num_qubits(want)
+        eigs = G.M(q, theta, phi).eigenvectors()
+        branch, nrm = O.measure_branches(want, q, theta, phi)[result]
+        want = branch / nrm
+        for dev in (ref, opt):
+            dev.collapse(q, eigs[result], 1.0 / nrm)
+        saw(opt)
+        got_ref, got_opt = ref.to_numpy(), opt.to_numpy()
+        assert np.array_equal(got_ref, got_opt) and maxdiff(got_ref, want) < GATE_TOL * scale_of(want), ("collapse", q, n_now)
+        amp = rng.standard_normal(2) + 1j * rng.standard_normal(2)
+        for dev in (ref, opt):
+            dev.insert(q, amp)
+        saw(opt)
+        want = O.insert_qubit(want, q, amp)
+        got_ref, got_opt = ref.to_numpy(), opt.to_numpy()
+        assert np.array_equal(got_ref, got_opt) and maxdiff(got_ref, want) < GATE_TOL * scale_of(want), ("insert", q)
+        order = [int(v) for v in rng.permutation(n)]
+        for dev in (ref, opt):
+            dev.permute(order)
+        saw(opt)
+        want = O.permute_qubits(want, order)
+        got_ref, got_opt = ref.to_numpy(), opt.to_numpy()
+        assert np.array_equal(got_ref, got_opt) and maxdiff(got_ref, want) < GATE_TOL * scale_of(want), ("permute", order)
+
+
+def on_bits(n, flips, ys=(), zs=()):
+    letters = "".join("Y" if b in ys else "X" for b in flips) + "Z" * len(zs)
+    return letters, [n - 1 - b for b in list(flips) + list(zs)]
+
+
+def pauli_strings(n):
+    """Pivots (the highest flipped bit) inside a 128-byte line (0, 2: the launcher drops NONTEMPORAL there), inside a wave
+    (3, 5), above it (6, 9, n - 1), and diagonal strings; strings that share their flips share a pass."""
+    return [on_bits(n, (6, 0)), on_bits(n, (6, 0), ys=(6, 0)), on_bits(n, (0,), zs=(7,)), on_bits(n, (2, 1), ys=(1,)),
+            on_bits(n, (3,), zs=(0, n - 1)), on_bits(n, (5, 2), ys=(5,)), on_bits(n, (9, 4, 1), ys=(4,), zs=(12,)),
+            on_bits(n, (n - 1, 3), zs=(5,)), on_bits(n, (n - 1, 3), ys=(3,)), on_bits(n, (), zs=(0, n - 1)), on_bits(n, (), zs=(4,)),
+            on_bits(n, tuple(range(n)), ys=(1, 8))]
+
+
+def test_pauli_calls():
+    """n = 13: 4096 pairs in 16 workgroups, three under GRID_CAP = 3 (six trips).  Rotations, the operator and the backward
+    walk are elementwise in the amplitudes: same bits.  expect / transition read no option at all."""
+    n = 13
+    rng = np.random.default_rng(61)
+    strings = pauli_strings(n)
+    rotations = [(float(rng.uniform(-3, 3)), letters, qubits) for letters, qubits in strings + strings[::-1]]
+    terms = [(complex(rng.standard_normal(), rng.standard_normal()), letters, qubits) for letters, qubits in strings]
+    weight = float(sum(abs(c) for c, _, _ in terms))
+    psi0, lam0, bra = W.random_ket(n, 62), 3.7 * W.random_ket(n, 63), 1.7 * W.random_ket(n, 64)
+    ref, opt = DeviceState.from_numpy(psi0), with_options(DeviceState.from_numpy(psi0))
+    # apply_pauli_rotations, one rotation at a time (every instantiation is named) and as a list
+    want = psi0
+    for rotation in rotations:
+        ref.apply_pauli_rotations([rotation])
+        opt.apply_pauli_rotations([rotation])
+        name = saw(opt)
+        want = R.rotate_list(want, [rotation])
+        pivot = max([n - 1 - q for letter, q in zip(rotation[1], rotation[2]) if letter in "XY"], default=-1)
+        assert name.endswith(", false>") and name == ref.last_kernel().replace("true>", "false>"), (name, ref.last_kernel())
+        assert ref.last_kernel().endswith(f", {tf(pivot < 0 or pivot >= 3)}>"), (pivot, ref.last_kernel())
+        assert np.array_equal(ref.to_numpy(), opt.to_numpy()), (rotation[1:], name)
+    assert maxdiff(ref.to_numpy(), want) < CIRCUIT_TOL
+    ref.upload(psi0)
+    opt.upload(psi0)
+    ref.apply_pauli_rotations(rotations)
+    opt.apply_pauli_rotations(rotations)
+    psi = ref.to_numpy()
+    assert np.array_equal(psi, opt.to_numpy()) and maxdiff(psi, R.rotate_list(psi0, rotations)) < CIRCUIT_TOL
+    # expect_pauli_sum / transition_pauli_sum
+    real_terms = [(c.real, letters, qubits) for c, letters, qubits in terms]
+    e_ref, v_ref = ref.expect_pauli_sum(real_terms, return_terms=True)
+    e_opt, v_opt = opt.expect_pauli_sum(real_terms, return_terms=True)
+    want_e, want_v = P.transition(real_terms, psi, psi)
+    assert e_ref == e_opt and np.array_equal(v_ref, v_opt)
+    assert maxdiff(v_ref, want_v) < TERM_TOL and abs(e_ref - want_e) <= TERM_TOL * weight
+    dev_bra, dev_bra_opt = DeviceState.from_numpy(bra), with_options(DeviceState.from_numpy(bra))
+    t_ref, tv_ref = dev_bra.transition_pauli_sum(terms, ref, return_terms=True)
+    t_opt, tv_opt = dev_bra_opt.transition_pauli_sum(terms, opt, return_terms=True)
+    want_t, want_tv = P.transition(terms, bra, psi)
+    assert t_ref == t_opt and np.array_equal(tv_ref, tv_opt)
+    assert maxdiff(tv_ref, want_tv) < TERM_TOL * 1.7 and abs(t_ref - want_t) < TERM_TOL * 1.7 * weight
+    # apply_pauli_sum: the options are the destination's
+    old = 0.5 * W.random_ket(n, 65)
+    h_psi = P.apply_sum(terms, psi)
+    dst, dst_opt = DeviceState.from_numpy(old), with_options(DeviceState.from_numpy(old))
+    for accumulate, want_dst, bound in ((True, old + h_psi, TERM_TOL * (weight * np.max(np.abs(psi)) + np.max(np.abs(old)))),
+                                        (False, h_psi, TERM_TOL * weight * np.max(np.abs(psi)))):
+        ref.apply_pauli_sum(terms, out=dst, accumulate=accumulate)
+        opt.apply_pauli_sum(terms, out=dst_opt, accumulate=accumulate)
+        name = saw(dst_opt)
+        assert name.endswith(", false>") and name.startswith("k_pauli_sum_apply_group<"), name
+        assert np.array_equal(dst.to_numpy(), dst_opt.to_numpy()), (accumulate, name)
+        assert maxdiff(dst.to_numpy(), want_dst) < bound, accumulate
+    # pauli_rotations_adjoint: the options are psi's
+    lam, lam_opt = DeviceState.from_numpy(lam0), DeviceState.from_numpy(lam0)
+    want_values, _, want_lam = P.adjoint_values(rotations, psi, lam0)
+    values, values_opt = ref.pauli_rotations_adjoint(rotations, lam), opt.pauli_rotations_adjoint(rotations, lam_opt)
+    name = saw(opt)                                  # the walk ends with the first forward pass: XX and YY on bits 6 and 0
+    assert name == "k_pauli_adjoint_group<2, false, false>" and ref.last_kernel() == "k_pauli_adjoint_group<2, false, true>", (name, ref.last_kernel())
+    assert np.array_equal(values, values_opt) and maxdiff(values, want_values) < ADJOINT_TOL * 3.7
+    assert np.array_equal(ref.to_numpy(), opt.to_numpy()) and np.array_equal(lam.to_numpy(), lam_opt.to_numpy())
+    assert maxdiff(ref.to_numpy(), psi0) < 2 * CIRCUIT_TOL and maxdiff(lam.to_numpy(), want_lam) < CIRCUIT_TOL * 3.7
+
+
+def test_lincomb():
+    """n = 13: 32 workgroups by default, three under GRID_CAP = 3 (eleven trips).  The stored amplitudes are the same bits;
+    ``norm2`` is summed from another number of partial sums (module docstring) and is held to its bound alone."""
+    n = 13
+    kets = [W.random_ket(n, 70 + k) * (0.5 + 0.25 * k) for k in range(9)]
+    sources = [DeviceState.from_numpy(ket) for ket in kets]
+    old = 1.3 * W.random_ket(n, 79)
+    dst, dst_opt = DeviceState.from_numpy(old), with_options(DeviceState.from_numpy(old))
+    coeffs = np.arange(1, 10) * (0.3 - 0.1j)
+    for count in (1, 3, 9):
+        for beta in (0.0, 0.4 - 0.9j):
+            for want_norm in (False, True):
+                results = []
+                for dev in (dst, dst_opt):
+                    dev.upload(np.full_like(old, np.nan) if beta == 0 else old)
+                    norm2, passes = dev._lincomb(coeffs[:count], sources[:count], beta, want_norm)
+                    results.append((dev.to_numpy(), norm2, passes, dev.last_kernel()))
+                (got, norm2, passes, name), (got_opt, norm2_opt, passes_opt, name_opt) = results
+                SEEN.add(name_opt)
+                label = (count, beta, want_norm, name_opt)
+                want, bound = lincomb_model(beta, old, coeffs[:count], kets[:count])
+                last = count - 8 * (passes - 1)
+                assert passes == passes_opt == -(-count // 8), label
+                assert name_opt == f"k_lincomb<{last}, {tf(beta != 0 or passes > 1)}, {tf(want_norm)}, false>", label
+                assert name == name_opt.replace("false>", "true>"), label
+                assert np.array_equal(got, got_opt), label
+                assert maxdiff(got, want) <= bound, label
+                if want_norm:
+                    stored = float(np.vdot(got, got).real)
+                    assert abs(norm2 - stored) <= 1e-13 * stored and abs(norm2_opt - stored) <= 1e-13 * stored, (label, norm2, norm2_opt, stored)
+
+
+def test_mode_operators():
+    """(n_modes, d) = (3, 8).  Only k_mode2_plane (real blocks on the last two modes) reads NONTEMPORAL itself; d = 8 sends
+    mode1 / mode2 through the qubit kernels, which do."""
+    d, m = 8, 3
+    rng = np.random.default_rng(81)
+    psi = rng.standard_normal((d,) * m) + 1j * rng.standard_normal((d,) * m)
+    psi /= np.linalg.norm(psi)
+    ref, opt = QuditState.from_numpy(psi), QuditState.from_numpy(psi)
+    opt.set_option(_lib.OPT_NONTEMPORAL, 0)
+    opt.set_option(_lib.OPT_GRID_CAP, 3)
+    want = psi
+    names = {}
+
+    def compare(label):
+        names[label] = saw(opt)
+        got_ref, got_opt = ref.to_numpy(), opt.to_numpy()
+        assert np.array_equal(got_ref, got_opt), (label, names[label], maxdiff(got_ref, got_opt))
+        assert maxdiff(got_ref, want) < MODE_TOL * scale_of(want), (label, ref.last_kernel())
+
+    op = rng.standard_normal((d, d)) + 1j * rng.standard_normal((d, d))
+    op /= np.linalg.norm(op, 2)
+    for st in (ref, opt):
+        st.apply_mode(op, 1)
+    want = CO.apply_axis(want, op, 1)
+    compare("mode1")
+    op = rng.standard_normal((d * d, d * d)) + 1j * rng.standard_normal((d * d, d * d))
+    op /= np.linalg.norm(op, 2)
+    for st in (ref, opt):
+        st.apply_two_mode(op, 0, 2)
+    want = CO.apply_two_axes(want, op, 0, 2)
+    compare("mode2")
+    plane = np.exp(1j * rng.uniform(0, 6.28, (d, d)))
+    for st in (ref, opt):
+        st.apply_two_mode(plane, 2, 1)
+    want = CO.apply_two_axes_diag(want, plane, 2, 1)
+    compare("mode2_diag")
+    cols = rng.integers(-1, d * d, size=(d * d, 2)).astype(np.int32)
+    vals = rng.standard_normal((d * d, 2)) + 1j * rng.standard_normal((d * d, 2))
+    op = np.zeros((d * d, d * d), dtype=complex)
+    for r in range(d * d):
+        for c, v in zip(cols[r], vals[r]):
+            if c >= 0:
+                op[r, c] += v
+    for st in (ref, opt):
+        st.apply_two_mode_gather(cols, vals, 1, 0)
+    want = CO.apply_two_axes(want, op, 1, 0)
+    compare("mode2_gather")
+    for label, legs, is_real in (("mode2_blocks, real", (1, 2), True), ("mode2_blocks, complex", (0, 1), False)):
+        perm = rng.permutation(d * d)
+        blocks, pos = [], 0
+        for s in (1, 5, 8, 17, 32):
+            idx = [int(v) for v in perm[pos:pos + s]]
+            mat = rng.standard_normal((s, s)) + (0 if is_real else 1j * rng.standard_normal((s, s)))
+            blocks.append((idx, mat / max(1.0, np.linalg.norm(mat, 2))))
+            pos += s
+        op = np.identity(d * d, dtype=complex)
+        for idx, mat in blocks:
+            op[np.ix_(idx, idx)] = mat
+        for st in (ref, opt):
+            st.apply_two_mode_blocks(blocks, *legs)
+        want = CO.apply_two_axes(want, op, *legs)
+        compare(label)
+    print(f"mode operators, kernels under NONTEMPORAL = 0: {names}")
+    assert names["mode2_blocks, real"].startswith("k_mode2_blocks<") and names["mode2_blocks, complex"].startswith("k_mode2_blocks<")
+
+
+def test_mode_plane_kernel():
+    """k_mode2_plane, the one mode kernel that reads NONTEMPORAL itself, takes real blocks with one element stride on the
+    last two modes and needs the planes in front of them to fill batches of 1024 / d^2 = 16 (launch_plane,
+    qsv_qudit.hip:680): at d = 8 that is four modes (64 planes), not three (8).  A Fock-basis beam splitter is such an
+    operator (anti-diagonal blocks, stride d - 1)."""
+    from quantum_computations_amd.cv_simulator import fock
+
+    d, m = 8, 4
+    rng = np.random.default_rng(82)
+    psi = rng.standard_normal((d,) * m) + 1j * rng.standard_normal((d,) * m)
+    psi /= np.linalg.norm(psi)
+    ref, opt = QuditState.from_numpy(psi), QuditState.from_numpy(psi)
+    opt.set_option(_lib.OPT_NONTEMPORAL, 0)
+    want = psi
+    for theta in (0.7, 1.3):
+        for st in (ref, opt):
+            st.apply_two_mode_blocks(fock.beamsplitter_blocks(d, theta, 0.0), m - 2, m - 1)
+        want = CO.apply_two_axes(want, fock.beamsplitter_matrix(d, theta, 0.0), m - 2, m - 1)
+        name = saw(opt)
+        assert name.startswith("k_mode2_plane<") and name.endswith(", false>"), name
+        assert ref.last_kernel() == name.replace("false>", "true>")
+        got_ref, got_opt = ref.to_numpy(), opt.to_numpy()
+        assert np.array_equal(got_ref, got_opt), maxdiff(got_ref, got_opt)
+        assert maxdiff(got_ref, want) < MODE_TOL * scale_of(want)
+
+
+# ---- what ran --------------------------------------------------------------------------------------------------------------------
+def test_the_non_default_instantiations_ran():
+    """Must run after the tests above (pytest keeps file order).  Lists the NT = false and U = 4 / 8 names seen."""
+    false_forms = sorted(name for name in SEEN if "false" in name)
+    unrolled = sorted(name for name in SEEN if name.startswith(("k_dense<", "k_dense_ctrl<", "k_diag<")) and
+                      any(f", {u}, " in name or name.startswith(f"k_diag<{u},") for u in (4, 8)))
+    print("NT = false and other non-default instantiations seen:")
+    for name in false_forms:
+        print("   ", name)
+    print("U = 4 / U = 8 instantiations seen:")
+    for name in unrolled:
+        print("   ", name)
+    missing = []
+    for shape in ("1, 0", "0, 1", "2, 0", "1, 1", "0, 2"):              # k_dense<KH, KL, U, NT>
+        for u in (4, 8):
+            for nt in ("false", "true"):
+                if f"k_dense<{shape}, {u}, {nt}>" not in SEEN:
+                    missing.append(f"k_dense<{shape}, {u}, {nt}>")
+    # (prefix, ending): some name seen starts and ends like this; NT is the last template argument of every family but
+    # k_dense_lds<K, KB, NT, REAL>, which is looked at below
+    for prefix, ending in (("k_dense_ctrl<1, 0, 4,", "false>"), ("k_dense_ctrl<1, 0, 8,", "false>"), ("k_dense_ctrl<0, 1, 4,", "false>"),
+                           ("k_dense_ctrl<0, 1, 8,", "false>"), ("k_diag<4,", "false>"), ("k_diag<8,", "false>"), ("k_diag<4,", "true>"),
+                           ("k_diag<8,", "true>"), ("k_diag<4,", "false> [sub-space]"), ("k_diag<8,", "false> [sub-space]"),
+                           ("k_dense_tile12<1,", "false>"), ("k_dense_tile12<2,", "false>"), ("k_dense_tile12_ctrl<1,", "false>"),
+                           ("k_dense_tile<3, 2, false,", "false>"), ("k_dense_big<4,", "false>"), ("k_dense_big<5, 0,", "false>"),
+                           ("k_pass_tile<", "false>"), ("k_pass_tile<", "true>"), ("k_pauli_rotate_group<", "false, false>"),
+                           ("k_pauli_rotate_group<", "true, false>"), ("k_pauli_sum_apply_group<", "false>"),
+                           ("k_pauli_adjoint_group<", "false, false>"), ("k_lincomb<", "false>"), ("k_mode2_plane<", "false>")):
+        if not any(name.startswith(prefix) and name.endswith(ending) for name in SEEN):
+            missing.append(prefix + " ... " + ending)
+    if not any(name.startswith("k_dense_lds<5, ") and name.split(", ")[2] == "false" for name in SEEN):
+        missing.append("k_dense_lds<5, KB, false, ...>")
+    assert not missing, (missing, sorted(SEEN))

@@ -2,7 +2,9 @@
 """Randomised cross-check of the C ABI against the CPU oracle on one GPU: registers of 3..19 qubits, random sequences of
 dense k-qubit gates (k = 1..6; complex, real, diagonal, permutation matrices), controlled gates, multi-controlled
 phases, SWAPs, measurements, insertions, qubit permutations and read-out calls -- every kernel family at sizes and
-placements the parametrised tests do not enumerate.  Exits non-zero at the first mismatch.
+placements the parametrised tests do not enumerate.  Every round also draws the tuning options (nontemporal accesses,
+items per thread, tile order, item stride bit, grid cap) from a random stream of its own.  Exits non-zero at the first
+mismatch.
 
     python tools/fuzz_gates.py [--rounds 200] [--seed 0]
 """
@@ -28,6 +30,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
     rng = np.random.default_rng(args.seed)
+    tuning = np.random.default_rng([args.seed, 0x7e5])     # a stream of its own: the operations drawn from `rng` stay as they were
     kernels = {}
     for rnd in range(args.rounds):
         n = int(rng.integers(3, 20))
@@ -37,6 +40,12 @@ def main():
         dev.set_option(_lib.OPT_READOUT_VARIANT, int(rng.choice([0, 0, 1, 2])))
         dev.set_option(_lib.OPT_COMPLEX_PRODUCT, int(rng.choice([0, 0, 3, 4])))
         dev.set_option(_lib.OPT_SPECIALIZE, int(rng.choice([1, 1, 0])))
+        # the tuning options: which instantiation runs and which thread takes which amplitude, never the result
+        options = {_lib.OPT_NONTEMPORAL: int(tuning.integers(2)), _lib.OPT_UNROLL: int(tuning.choice([0, 1, 2, 4, 8])),
+                   _lib.OPT_TILE_REGIONS: int(tuning.choice([-1, 0, 2, 8, 32])), _lib.OPT_ITEM_STRIDE_BIT: int(tuning.integers(8, 13)),
+                   _lib.OPT_GRID_CAP: int(tuning.choice([0, 0, 3, 7]))}
+        for option, value in options.items():
+            dev.set_option(option, value)
         want = ket
         log = []
         for step in range(int(rng.integers(4, 12))):
@@ -128,7 +137,7 @@ def main():
             scale = max(1.0, float(np.max(np.abs(want))))
             err = float(np.max(np.abs(dev.to_numpy() - want)))
             if not err < 1e-11 * scale:
-                raise SystemExit(f"round {rnd}: after {log[-1]} on {n} qubits ({name}): max abs err {err:.3e}\n{log}")
+                raise SystemExit(f"round {rnd}: after {log[-1]} on {n} qubits ({name}; options {options}): max abs err {err:.3e}\n{log}")
         dev.close()
     print(f"fuzz ok: {args.rounds} rounds; kernels exercised:")
     for name in sorted(kernels):

@@ -287,6 +287,60 @@ int qsv_pauli_rotations_adjoint(qsv_state *psi, qsv_state *lambda, int n_terms, 
 int qsv_lincomb(qsv_state *dst, double beta_re, double beta_im, int n_src, qsv_state *const *srcs, const double *coeffs,
                 double *norm2, uint64_t *passes);
 int qsv_inner_many(qsv_state *y, int n_x, qsv_state *const *xs, double *values, uint64_t *passes);
+
+/* ---- real diagonal operators on the device (csrc/qsv_diagonal.hip) ----
+ * A qsv_diag holds 2^n doubles d[i] in device memory, indexed exactly like the register (qubit q is bit n-1-q of i):
+ * a classical cost function, an oracle on any marked set, the ZZ part of an Ising or MaxCut Hamiltonian.  It is owned
+ * by the library and has a stream of its own (default: the null stream).  Every call on a register and a diagonal is ONE
+ * pass over the register, whatever the number of terms the diagonal was built from. */
+typedef struct qsv_diag qsv_diag;
+
+/* Allocate, zero-filled; the sizes qsv_create accepts. */
+int qsv_diag_create(int n_qubits, int device, qsv_diag **out);
+int qsv_diag_destroy(qsv_diag *d);
+int qsv_diag_set_stream(qsv_diag *d, void *hip_stream);
+int qsv_diag_num_qubits(const qsv_diag *d, int *n_qubits);
+/* Only QSV_OPT_GRID_CAP (max workgroups of the diagonal's own kernels); anything else is QSV_EINVAL. */
+int qsv_diag_set_option(qsv_diag *d, int option, int64_t value);
+/* Name of the kernel the most recent qsv_diag_set_pauli_sum / qsv_diag_extrema launched. */
+int qsv_diag_last_kernel(const qsv_diag *d, char *buf, size_t buf_len);
+/* Windows [offset, offset + count) of doubles, bounds-checked; the host buffer is only touched during the call. */
+int qsv_diag_upload(qsv_diag *d, const double *host, uint64_t offset, uint64_t count);
+int qsv_diag_download(qsv_diag *d, double *host, uint64_t offset, uint64_t count);
+/* d[i] = (accumulate ? d[i] : 0) + sum_t c_t (-1)^popcount(i & zmask_t).  Term layout as in qsv_expect_pauli_sum, but
+ * coeffs holds n_terms REAL numbers (NULL: all 1) and only the letters I and Z are accepted (X, Y: QSV_EINVAL); qubits in
+ * range and distinct within a term, at most 64 letters; everything is validated before any launch.  One write pass for
+ * any number of terms: masks and coefficients go to the device once as a table that every thread walks in the caller's
+ * order, one rounded addition per term (c_t * (+-1) is exact), so the result equals the same loop in float64 on the
+ * host bit for bit.  n_terms = 0 zeroes the vector (leaves it alone with accumulate); the empty term adds a constant.
+ * passes (may be NULL) = kernel launches: 1, or 0 where nothing had to be done. */
+int qsv_diag_set_pauli_sum(qsv_diag *d, int n_terms, const int *term_offsets, const int *qubits, const char *paulis,
+                           const double *coeffs, int accumulate, uint64_t *passes);
+/* Smallest and largest entry and their indices in one read pass; ties go to the lowest index; any pointer may be NULL. */
+int qsv_diag_extrema(qsv_diag *d, double *min, uint64_t *argmin, double *max, uint64_t *argmax);
+/* Register x diagonal passes.  Rules for all of them, as for qsv_lincomb and qsv_apply_pauli_sum: null handles are
+ * refused; mode registers give QSV_ESTATE; registers and diagonal must be on one device and of one size (QSV_EINVAL);
+ * everything is validated before any deferred queue is flushed, then every register's queue is flushed; the streams of
+ * read-only operands are synchronised, the diagonal's too when it is not the stream that launches, and the launches go
+ * on the written register's stream (st's / bra's for the read-only calls).  Reductions leave one partial per workgroup
+ * (at most 1024) and slot, and the host sums them in index order after one copy and one synchronisation: the same call
+ * gives the same bits.
+ *
+ * qsv_apply_diag_phase: psi[i] *= exp(-i gamma d[i]) in place; the sine and cosine are formed in double on the device.
+ * qsv_apply_diag_mul: dst = c d.src, or dst += c d.src with accumulate, c = (c_re, c_im).  dst needs room for src's
+ *   amplitudes (QSV_ENOMEM), takes src's size, and must have it already to accumulate; their memory must not meet, except
+ *   that dst == src is allowed when not accumulating (D psi in place).  Without accumulate the old dst is never read.
+ * qsv_expect_diag: out = { sum p_i, sum p_i d_i, sum p_i d_i^2, sum_{d_i <= *threshold} p_i }, p_i = |psi_i|^2;
+ *   threshold may be NULL (then out[3] = 0).  Read-only.
+ * qsv_diag_transition: (re, im) = <bra| D |ket>.  Read-only; the same register may be passed twice.
+ * qsv_diag_phase_adjoint: (re, im) = <lambda| D |psi>, then psi *= exp(-i gamma d) and lambda *= exp(-i gamma d), all in
+ *   one pass with one sincos per amplitude.  D commutes with the phase, so the value is the same before and after it.
+ *   psi and lambda are two registers whose memory does not meet.  Both are finished when the call returns. */
+int qsv_apply_diag_phase(qsv_state *st, qsv_diag *d, double gamma);
+int qsv_apply_diag_mul(qsv_state *dst, qsv_state *src, qsv_diag *d, double c_re, double c_im, int accumulate);
+int qsv_expect_diag(qsv_state *st, qsv_diag *d, const double *threshold, double *out);
+int qsv_diag_transition(qsv_state *bra, qsv_state *ket, qsv_diag *d, double *re, double *im);
+int qsv_diag_phase_adjoint(qsv_state *psi, qsv_state *lambda, qsv_diag *d, double gamma, double *re, double *im);
 /* Reduced density matrix of the k <= 6 qubits `qubits` (all others traced out) in one read pass over the register:
  * rho[i][j] = sum_rest psi[i, rest] conj(psi[j, rest]), written row-major as 4^k complex numbers, qubits[0] the most
  * significant bit of i and j.  What a caller of the reference gets from npq.ket2dm (numpy_quantum.py:110-113)

@@ -5,3 +5,5 @@ HBM-resident registers; ``_lib`` binds libqsv.so (include/qsv.h).  Importing the
 GPU; the first register does, and raises if libqsv.so has not been built.
 """
 __version__ = "0.1.0"
+
+from .diagonal import DiagonalOperator  # noqa: E402,F401  (binds nothing until the first operator is made)

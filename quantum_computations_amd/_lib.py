@@ -70,6 +70,21 @@ SIGNATURES: dict[str, list] = {
     "qsv_pauli_rotations_adjoint": [_state_p, _state_p, C.c_int, _int_p, _int_p, C.c_char_p, _dbl_p, _dbl_p, _u64_p],
     "qsv_lincomb": [_state_p, C.c_double, C.c_double, C.c_int, C.POINTER(_state_p), _dbl_p, _dbl_p, _u64_p],
     "qsv_inner_many": [_state_p, C.c_int, C.POINTER(_state_p), _dbl_p, _u64_p],
+    "qsv_diag_create": [C.c_int, C.c_int, C.POINTER(_state_p)],
+    "qsv_diag_destroy": [_state_p],
+    "qsv_diag_set_stream": [_state_p, C.c_void_p],
+    "qsv_diag_num_qubits": [_state_p, C.POINTER(C.c_int)],
+    "qsv_diag_set_option": [_state_p, C.c_int, C.c_int64],
+    "qsv_diag_last_kernel": [_state_p, C.c_char_p, C.c_size_t],
+    "qsv_diag_upload": [_state_p, _dbl_p, C.c_uint64, C.c_uint64],
+    "qsv_diag_download": [_state_p, _dbl_p, C.c_uint64, C.c_uint64],
+    "qsv_diag_set_pauli_sum": [_state_p, C.c_int, _int_p, _int_p, C.c_char_p, _dbl_p, C.c_int, _u64_p],
+    "qsv_diag_extrema": [_state_p, _dbl_p, _u64_p, _dbl_p, _u64_p],
+    "qsv_apply_diag_phase": [_state_p, _state_p, C.c_double],
+    "qsv_apply_diag_mul": [_state_p, _state_p, _state_p, C.c_double, C.c_double, C.c_int],
+    "qsv_expect_diag": [_state_p, _state_p, _dbl_p, _dbl_p],
+    "qsv_diag_transition": [_state_p, _state_p, _state_p, _dbl_p, _dbl_p],
+    "qsv_diag_phase_adjoint": [_state_p, _state_p, _state_p, C.c_double, _dbl_p, _dbl_p],
     "qsv_reduced_density": [_state_p, C.c_int, _int_p, C.c_void_p],
     "qsv_expect_density": [_state_p, _state_p, _dbl_p, _dbl_p],
     "qsv_sample": [_state_p, C.c_int, C.c_void_p, C.c_void_p],

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 
 import numpy as np
 
@@ -83,6 +84,16 @@ def _ket_operand(register, name: str) -> None:
 
 def _dbl(buf: np.ndarray):
     return buf.ctypes.data_as(C.POINTER(C.c_double))
+
+
+# what DeviceState.expect_diagonal returns: sum p, sum p d, sum p d^2 and sum of p over d <= threshold, p = |amplitude|^2
+DiagonalMoments = namedtuple("DiagonalMoments", ["norm2", "mean", "second_moment", "probability_below"])
+
+
+def _diagonal_operand(diag) -> None:
+    from .diagonal import DiagonalOperator
+    if not isinstance(diag, DiagonalOperator):
+        raise TypeError("expected a DiagonalOperator")
 
 
 class DeviceState:
@@ -478,6 +489,59 @@ class DeviceState:
             lam.close()
         return energy, np.ascontiguousarray(values.imag)
 
+    # ---- diagonal operators: one pass each, whatever the diagonal was built from ----------
+    def apply_diagonal_phase(self, diag, gamma: float) -> "DeviceState":
+        """In place ``exp(-i gamma D) self`` for a ``DiagonalOperator`` of this size on this device."""
+        _diagonal_operand(diag)
+        _lib.call("qsv_apply_diag_phase", self._h, diag._h, float(gamma))
+        return self
+
+    def apply_diagonal_operator(self, diag, out: "DeviceState | None" = None, coeff: complex = 1.0,
+                                accumulate: bool = False) -> "DeviceState":
+        """``out = coeff D self`` (``out += coeff D self`` with ``accumulate``).  ``out`` is a register on the same
+        device, allocated when None; it may be ``self`` when not accumulating (``D psi`` in place).  Returns ``out``."""
+        _diagonal_operand(diag)
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate needs a destination register")
+            out = DeviceState.zeros(self.num_qubits, self.device)
+        _ket_operand(out, "out")
+        coeff = complex(coeff)
+        _lib.call("qsv_apply_diag_mul", out._h, self._h, diag._h, coeff.real, coeff.imag, int(bool(accumulate)))
+        return out
+
+    def expect_diagonal(self, diag, threshold: float | None = None) -> DiagonalMoments:
+        """``(norm2, mean, second_moment, probability_below)`` = ``(sum p_i, sum p_i d_i, sum p_i d_i^2,
+        sum_{d_i <= threshold} p_i)`` with ``p_i = |amplitude_i|^2`` in one read pass; without a threshold the last
+        entry is 0.  Nothing is divided by the norm."""
+        _diagonal_operand(diag)
+        out = np.zeros(4, dtype=np.float64)
+        thr = None if threshold is None else C.byref(C.c_double(float(threshold)))
+        _lib.call("qsv_expect_diag", self._h, diag._h, thr, _dbl(out))
+        return DiagonalMoments(*(float(v) for v in out))
+
+    def variance_diagonal(self, diag) -> float:
+        """``<D^2> - <D>^2`` on a normalised register, from one ``expect_diagonal`` pass."""
+        moments = self.expect_diagonal(diag)
+        return moments.second_moment - moments.mean ** 2
+
+    def transition_diagonal(self, diag, ket: "DeviceState") -> complex:
+        """``<self| D |ket>``; ``self`` is the bra and ``ket`` may be ``self``.  Read-only."""
+        _diagonal_operand(diag)
+        _ket_operand(ket, "ket")
+        re, im = C.c_double(), C.c_double()
+        _lib.call("qsv_diag_transition", self._h, ket._h, diag._h, C.byref(re), C.byref(im))
+        return complex(re.value, im.value)
+
+    def diagonal_phase_adjoint(self, diag, lam: "DeviceState", gamma: float) -> complex:
+        """``<lam| D |self>``, then ``exp(-i gamma D)`` on ``self`` and on ``lam``, all in one pass
+        (``qsv_diag_phase_adjoint``): the step of an adjoint walk over a cost layer (``qaoa.energy_and_gradient``)."""
+        _diagonal_operand(diag)
+        _ket_operand(lam, "lam")
+        re, im = C.c_double(), C.c_double()
+        _lib.call("qsv_diag_phase_adjoint", self._h, lam._h, diag._h, float(gamma), C.byref(re), C.byref(im))
+        return complex(re.value, im.value)
+
     def sample(self, shots: int, rng=None) -> np.ndarray:
         """``shots`` computational-basis outcomes drawn from |amplitude|^2 (inverse-CDF on the device; the uniforms
         come from ``rng``, a ``numpy.random.Generator``, default the global ``np.random`` state).  No collapse."""
@@ -671,6 +735,24 @@ class DensityState(DeviceState):
 
     def energy_and_gradient(self, rotations, terms):
         raise ValueError("energy_and_gradient is not defined for a density register")
+
+    def apply_diagonal_phase(self, diag, gamma):
+        raise ValueError("apply_diagonal_phase is not defined for a density register")
+
+    def apply_diagonal_operator(self, diag, out=None, coeff=1.0, accumulate: bool = False):
+        raise ValueError("apply_diagonal_operator is not defined for a density register")
+
+    def expect_diagonal(self, diag, threshold=None):
+        raise ValueError("expect_diagonal is not defined for a density register")
+
+    def variance_diagonal(self, diag):
+        raise ValueError("variance_diagonal is not defined for a density register")
+
+    def transition_diagonal(self, diag, ket):
+        raise ValueError("transition_diagonal is not defined for a density register")
+
+    def diagonal_phase_adjoint(self, diag, lam, gamma):
+        raise ValueError("diagonal_phase_adjoint is not defined for a density register")
 
     def ground_state_of(self, terms, **options):
         raise ValueError("ground_state_of is not defined for a density register")

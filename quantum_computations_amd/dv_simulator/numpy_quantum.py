@@ -417,6 +417,94 @@ def evolve_exact(hamiltonian: PauliSum, state, t: float, **options):
         state.close()
 
 
+# ---- diagonal operators (``DiagonalOperator``) ---------------------------------------------------
+def _term_list(pauli_sum_or_terms) -> list:
+    terms = pauli_sum_or_terms.terms if isinstance(pauli_sum_or_terms, PauliSum) else pauli_sum_or_terms
+    return [(c, str(letters), [int(q) for q in qubits]) for c, letters, qubits in terms]
+
+
+def split_diagonal(terms) -> tuple[list, list]:
+    """``(z_only_terms, other_terms)`` of a term list or ``PauliSum``, each in the caller's order: the first is what a
+    ``DiagonalOperator`` holds, the second what stays a Pauli sum."""
+    z_only, other = [], []
+    for term in _term_list(terms):
+        (z_only if all(letter in "IZiz" for letter in term[1]) else other).append(term)
+    return z_only, other
+
+
+def diagonal_of(pauli_sum_or_terms, n: int) -> np.ndarray:
+    """The ``2^n`` float64 values of a Z-only Pauli sum, built on the host: ``c_t * sign`` added term by term in the
+    caller's order, the additions ``DiagonalOperator.from_terms`` makes on the device (the two agree bit for bit)."""
+    n = int(n)
+    index = np.arange(1 << n, dtype=np.uint64)
+    values = np.zeros(1 << n, dtype=np.float64)
+    for c, letters, qubits in _term_list(pauli_sum_or_terms):
+        c = complex(c)
+        if c.imag != 0.0:
+            raise ValueError("a diagonal operator needs real coefficients")
+        if len(letters) != len(qubits):
+            raise ValueError("one Pauli letter per qubit")
+        if any(letter not in "IZiz" for letter in letters):
+            raise ValueError("a diagonal operator takes the letters I and Z only")
+        if any(not 0 <= q < n for q in qubits):
+            raise ValueError(f"qubit index out of range for a {n}-qubit register")
+        if len(set(qubits)) != len(qubits):
+            raise ValueError("Indices must be distinct.")
+        parity = np.zeros(1 << n, dtype=np.uint64)
+        for letter, q in zip(letters, qubits):
+            if letter in "Zz":
+                parity ^= (index >> np.uint64(n - 1 - q)) & np.uint64(1)
+        values += np.where(parity == 1, -c.real, c.real)
+    return values
+
+
+def _lift_diagonal(diag, state):
+    """(operator, register, which of the two were uploaded here).  ``diag``: a ``DiagonalOperator`` or a host vector;
+    ``state``: a ``DeviceState`` or a host ket.  Sizes are checked as ``expect_pauli_sum`` checks them."""
+    from ..device import DeviceState
+    from ..diagonal import DiagonalOperator
+    uploaded = []
+    try:
+        if not isinstance(state, DeviceState):
+            state = DeviceState.from_numpy(np.asarray(state))
+            uploaded.append(state)
+        if not isinstance(diag, DiagonalOperator):
+            diag = DiagonalOperator.from_numpy(np.asarray(diag), state.device)
+            uploaded.append(diag)
+        if diag.num_qubits != state.num_qubits:
+            raise TypeError("incompatible operator and state vector")
+    except Exception:
+        for handle in uploaded:
+            handle.close()
+        raise
+    return diag, state, uploaded
+
+
+def apply_diagonal_phase(diag, state, gamma: float):
+    """``exp(-i gamma D) state`` on the device (``DeviceState.apply_diagonal_phase``).  A register is changed in place
+    and returned; a host ket is uploaded first and the result is downloaded, as ``evolve`` lifts host arrays."""
+    from ..device import DeviceState
+    host = not isinstance(state, DeviceState)
+    diag, state, uploaded = _lift_diagonal(diag, state)
+    try:
+        state.apply_diagonal_phase(diag, gamma)
+        return state.to_numpy() if host else state
+    finally:
+        for handle in uploaded:
+            handle.close()
+
+
+def expect_diagonal(diag, state, threshold: float | None = None):
+    """``(norm2, mean, second_moment, probability_below)`` of a diagonal operator in ``state``, one read pass on the
+    device (``DeviceState.expect_diagonal``); host arrays are uploaded first and released afterwards."""
+    diag, state, uploaded = _lift_diagonal(diag, state)
+    try:
+        return state.expect_diagonal(diag, threshold)
+    finally:
+        for handle in uploaded:
+            handle.close()
+
+
 # ---- sizes ----------------------------------------------------------------------------------------------------------
 def is_power_of_two(n: int) -> bool:
     return n > 0 and n & (n - 1) == 0

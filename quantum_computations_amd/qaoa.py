@@ -1,0 +1,106 @@
+"""QAOA on a ``DiagonalOperator`` cost: layers ``exp(-i beta_l B) exp(-i gamma_l D)`` on
+``|+>^n`` with the mixer ``B = sum_q X_q``, the energy ``<D>`` and its gradient in all ``2 p`` angles by one adjoint walk.
+
+The cost layer is one pass over the register whatever ``D`` was built from (``DeviceState.apply_diagonal_phase``); the
+mixer is ``RX(2 beta)`` on every qubit through ``apply_matrix``, which the deferred queue batches into shared passes.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .device import DeviceState
+from .diagonal import DiagonalOperator
+
+_H = np.array([[1.0, 1.0], [1.0, -1.0]], dtype=complex) / np.sqrt(2.0)
+
+
+def _angles(gammas, betas) -> tuple[np.ndarray, np.ndarray]:
+    gammas = np.atleast_1d(np.asarray(gammas, dtype=np.float64))
+    betas = np.atleast_1d(np.asarray(betas, dtype=np.float64))
+    if gammas.ndim != 1 or gammas.shape != betas.shape:
+        raise ValueError("one gamma and one beta per layer")
+    return gammas, betas
+
+
+def plus_state(n_qubits: int, device: int = 0) -> DeviceState:
+    """``|+>^n`` made on the device: H on every qubit of ``|0...0>``."""
+    state = DeviceState.zeros(n_qubits, device)
+    for q in range(n_qubits):
+        state.apply_matrix(_H, [q])
+    return state
+
+
+def mixer(state: DeviceState, beta: float) -> DeviceState:
+    """In place ``exp(-i beta sum_q X_q) state``: ``RX(2 beta)`` on every qubit."""
+    c, s = np.cos(beta), np.sin(beta)
+    rx = np.array([[c, -1j * s], [-1j * s, c]], dtype=complex)
+    for q in range(state.num_qubits):
+        state.apply_matrix(rx, [q])
+    return state
+
+
+def mixer_terms(n_qubits: int) -> list[tuple]:
+    """``B = sum_q X_q`` as a Pauli term list."""
+    return [(1.0, "X", [q]) for q in range(n_qubits)]
+
+
+def run(diag: DiagonalOperator, gammas, betas, state: DeviceState | None = None) -> DeviceState:
+    """The QAOA state: for every layer the cost phase ``exp(-i gamma_l D)`` and then the mixer ``exp(-i beta_l B)``, on
+    ``state`` in place (``|+>^n`` on the diagonal's device when None).  Returns the register."""
+    gammas, betas = _angles(gammas, betas)
+    if state is None:
+        state = plus_state(diag.num_qubits, diag.device)
+    for gamma, beta in zip(gammas, betas):
+        state.apply_diagonal_phase(diag, gamma)
+        mixer(state, beta)
+    return state
+
+
+def energy_and_gradient(diag: DiagonalOperator, gammas, betas, state: DeviceState | None = None):
+    """``(E, dE/dgamma, dE/dbeta)`` of ``E = <psi_p| D |psi_p>`` by one adjoint walk: the layers forward, ``E`` and
+    ``lambda = D psi``, then for the last layer first ``dE/dbeta_l = 2 Im <lambda| B |psi>``, the mixer undone on both
+    registers, and ``dE/dgamma_l = 2 Im <lambda| D |psi>`` from ``qsv_diag_phase_adjoint``, which undoes the cost phase
+    on both in the same pass.  ``state`` (``|+>^n`` when None) holds its input again on return, up to rounding."""
+    gammas, betas = _angles(gammas, betas)
+    own = state is None
+    psi = plus_state(diag.num_qubits, diag.device) if own else state
+    lam = DeviceState.zeros(psi.num_qubits, psi.device)
+    try:
+        run(diag, gammas, betas, psi)
+        energy = psi.expect_diagonal(diag).mean
+        psi.apply_diagonal_operator(diag, out=lam)
+        b_terms = mixer_terms(psi.num_qubits)
+        d_gamma, d_beta = np.zeros_like(gammas), np.zeros_like(betas)
+        for layer in range(len(gammas) - 1, -1, -1):
+            d_beta[layer] = 2.0 * lam.transition_pauli_sum(b_terms, psi).imag
+            mixer(psi, -betas[layer])
+            mixer(lam, -betas[layer])
+            d_gamma[layer] = 2.0 * psi.diagonal_phase_adjoint(diag, lam, -gammas[layer]).imag
+    finally:
+        lam.close()
+        if own:
+            psi.close()
+    return energy, d_gamma, d_beta
+
+
+def minimise(diag: DiagonalOperator, p: int, x0=None, **scipy_options):
+    """Minimise ``<D>`` over the ``2 p`` angles ``x = (gammas, betas)`` with L-BFGS-B on ``energy_and_gradient``.
+    ``x0``: the starting angles (default: ``gamma_l = 0.1 (l + 1) / p``, ``beta_l = 0.1 (p - l) / p``); keyword options
+    go to ``scipy.optimize.minimize``.  Returns ``(angles, energy, result)``, ``angles`` as ``x``."""
+    from scipy.optimize import minimize
+
+    p = int(p)
+    if p < 1:
+        raise ValueError("at least one layer")
+    if x0 is None:
+        x0 = np.concatenate([0.1 * (np.arange(p) + 1) / p, 0.1 * (p - np.arange(p)) / p])
+    x0 = np.asarray(x0, dtype=np.float64).reshape(-1)
+    if x0.size != 2 * p:
+        raise ValueError("x0 holds p gammas and then p betas")
+
+    def objective(x):      # a fresh |+>^n per evaluation: rounding of the rewound register does not pile up
+        energy, d_gamma, d_beta = energy_and_gradient(diag, x[:p], x[p:])
+        return energy, np.concatenate([d_gamma, d_beta])
+
+    result = minimize(objective, x0, jac=True, method="L-BFGS-B", **scipy_options)
+    return np.asarray(result.x), float(result.fun), result

@@ -225,3 +225,32 @@ def ising_terms(n: int, h: float, coupling: float = 1.0) -> list[tuple]:
     """Transverse-field Ising chain ``-J sum_q Z_q Z_q+1 - h sum_q X_q``: n - 1 couplings (one diagonal group) and n
     field terms (one group each)."""
     return [(-coupling, "ZZ", [q, q + 1]) for q in range(n - 1)] + [(-h, "X", [q]) for q in range(n)]
+
+
+# ---- diagonal cost functions: Z-only term lists, what DiagonalOperator.from_terms takes -------------------------------
+def ring_chord_edges(n: int) -> list[tuple[int, int]]:
+    """The deterministic 3-regular graph on an even number ``n >= 4`` of vertices: the ring ``(i, i + 1)`` and the
+    chords ``(i, i + n/2)``; ``3 n / 2`` edges."""
+    if n < 4 or n % 2:
+        raise ValueError("the ring-and-chord graph needs an even number of at least 4 vertices")
+    return [(i, (i + 1) % n) for i in range(n)] + [(i, i + n // 2) for i in range(n // 2)]
+
+
+def maxcut_terms(n: int, edges, weights=None) -> list[tuple]:
+    """MaxCut as a minimisation: ``C = sum_e w_e / 2 (Z_i Z_j - 1)``, so ``C(x) = -(weight of the cut x)``.  One ZZ term
+    per edge in the caller's order, then the identity term ``-sum_e w_e / 2``."""
+    edges = [(int(i), int(j)) for i, j in edges]
+    weights = [1.0] * len(edges) if weights is None else [float(w) for w in weights]
+    if len(weights) != len(edges):
+        raise ValueError("one weight per edge")
+    if any(i == j or not (0 <= i < n and 0 <= j < n) for i, j in edges):
+        raise ValueError(f"edges must join two different vertices below {n}")
+    return [(w / 2.0, "ZZ", [i, j]) for (i, j), w in zip(edges, weights)] + [(-sum(w / 2.0 for w in weights), "", [])]
+
+
+def sk_terms(n: int, seed: int) -> list[tuple]:
+    """A Sherrington-Kirkpatrick instance ``sum_{i < j} J_ij Z_i Z_j`` with ``J = default_rng(seed).standard_normal``
+    couplings drawn in the order of the pairs: ``n (n - 1) / 2`` terms."""
+    pairs = [(i, j) for i in range(n) for j in range(i + 1, n)]
+    couplings = np.random.default_rng(seed).standard_normal(len(pairs))
+    return [(float(c), "ZZ", [i, j]) for c, (i, j) in zip(couplings, pairs)]

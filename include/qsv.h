@@ -103,7 +103,9 @@ typedef struct qsv_state qsv_state;
  *    measure*, collapse, insert, permute, apply_kq, apply_mcphase, apply_sequence, apply_pauli_rotation(s) (never
  *    queued themselves), apply_pauli_sum, pauli_transition_sum, pauli_rotations_adjoint (both registers), set_stream,
  *    set_option, device_ptr,
- *    timer_*, event_*, last_kernel, and qsv_flush itself.  qsv_destroy drops what is pending.
+ *    timer_*, event_*, last_kernel, density_expect_paulis, apply_channel with a general channel, and qsv_flush itself.
+ *    qsv_apply_channel with a mixed-unitary channel does NOT flush: its gate is queued like any other, and
+ *    qsv_channel_log_read leaves the queue alone.  qsv_destroy drops what is pending.
  *  - A launch error during a flush is returned by the call that flushed; the rest of the queue is dropped.
  *  - Views (qsv_create_view, qsv_rebind_view) never defer, nor does a register once qsv_device_ptr has handed out its
  *    address (the caller may then touch the amplitudes directly): that call flushes and switches deferral off for good.
@@ -341,6 +343,45 @@ int qsv_apply_diag_mul(qsv_state *dst, qsv_state *src, qsv_diag *d, double c_re,
 int qsv_expect_diag(qsv_state *st, qsv_diag *d, const double *threshold, double *out);
 int qsv_diag_transition(qsv_state *bra, qsv_state *ket, qsv_diag *d, double *re, double *im);
 int qsv_diag_phase_adjoint(qsv_state *psi, qsv_state *lambda, qsv_diag *d, double gamma, double *re, double *im);
+
+/* ---- noise: Kraus channels on kets and Pauli traces of density registers (csrc/qsv_channel.hip) ----
+ * A qsv_channel holds 1 <= n_kraus <= 16 Kraus operators K_j on k = 1 or 2 qubits (n_kraus x 2^k x 2^k complex, row-major,
+ * qubits[0] the most significant leg) and their effects E_j = K_j^dagger K_j in device memory, so a call uploads nothing.
+ * Trace preservation is not demanded: branch weights are always taken relative to their sum, so a call preserves the
+ * register's norm whatever it was.  A channel whose every E_j equals p_j I (to 16 eps per entry) is marked mixed-unitary
+ * at creation: bit flip, phase flip, depolarising, any Pauli channel.  The 16 eps are ABSOLUTE, on purpose: the operators of
+ * a trace-preserving channel have entries of at most 1, and the Python layer applies the same rule without a device.  A
+ * list that is not normalised should be scaled to unit weight first: with entries far above 1 its own rounding may
+ * keep it off the queued path (slower, never wrong); with entries below about 1e-8 every list is taken for mixed-unitary. */
+typedef struct qsv_channel qsv_channel;
+int qsv_channel_create(int k, int n_kraus, const double *kraus, int device, qsv_channel **out);
+int qsv_channel_destroy(qsv_channel *c);
+int qsv_channel_info(const qsv_channel *c, int *k, int *n_kraus, int *mixed_unitary);  /* any output may be NULL */
+/* One quantum-trajectory step: psi <- K_j psi sqrt(total / w_j), w_j = <psi| E_j |psi>, total = sum_j w_j, where j = forced
+ * if forced >= 0, else the first j with w_0 + ... + w_j > u01 total (the last j with w_j > 0 if rounding leaves none).  A
+ * forced branch of weight 0 leaves an all-zero register and logs probability 0; no inf or nan is produced.
+ *  - Mixed-unitary channel: the weights are the p_j whatever the state, so the host picks j and K_j / sqrt(p_j) goes through
+ *    qsv_apply_1q / qsv_apply_2q: no reduction, no flush -- on a deferring register the gate joins the queue.
+ *  - Any other channel flushes the queue and takes two passes over the register: a read pass that leaves the reduced
+ *    density matrix of the target qubits in device memory, a one-workgroup kernel that forms the weights, takes the branch
+ *    and writes the scaled K_j to a device slot, and an in-place update pass that reads that slot.  Everything is enqueued
+ *    on the register's stream; the call returns without waiting and downloads nothing.
+ * QSV_EINVAL for null pointers, u01 outside [0, 1), forced outside -1 .. n_kraus - 1, qubits repeated or out of range, a
+ * channel on another device; QSV_ESTATE for a mode register: each before any launch and with the deferred queue untouched.
+ * Every call appends (j, w_j / total) to the register's branch log, in call order.  The device part of the log has a fixed
+ * number of slots; a call that finds it full drains it to host memory first -- the only time this call synchronises. */
+int qsv_apply_channel(qsv_state *st, qsv_channel *c, const int *qubits, double u01, int forced);
+/* The branch log: *count = entries pending.  With capacity >= *count they are copied out (after a synchronisation of the
+ * register's stream) and the log is cleared; with a smaller capacity nothing is copied or cleared.  Pending gates of a
+ * deferring register stay queued.  qsv_destroy frees the log. */
+int qsv_channel_log_read(qsv_state *st, int32_t *branches, double *probs, uint64_t capacity, uint64_t *count);
+/* tr(P_t rho) for every Pauli string of a list (layout of term_offsets / qubits / paulis as in qsv_expect_pauli_sum, qubits
+ * numbered 0 .. n-1) and a density matrix held row-major as a 2n-qubit register: values[2t], values[2t+1] =
+ * i^nY sum_k (-1)^popcount(k & zmask_t) rho[k][k ^ xmask_t].  One launch for all terms, one workgroup per term, each reading
+ * 2^n of the 4^n entries; the empty term gives the trace.  Flushes the queue; QSV_EINVAL for a register with an odd number
+ * of qubits.  The whole list is validated before the flush. */
+int qsv_density_expect_paulis(qsv_state *rho, int n_terms, const int *term_offsets, const int *qubits, const char *paulis,
+                              double *values);
 /* Reduced density matrix of the k <= 6 qubits `qubits` (all others traced out) in one read pass over the register:
  * rho[i][j] = sum_rest psi[i, rest] conj(psi[j, rest]), written row-major as 4^k complex numbers, qubits[0] the most
  * significant bit of i and j.  What a caller of the reference gets from npq.ket2dm (numpy_quantum.py:110-113)

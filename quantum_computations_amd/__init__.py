@@ -7,3 +7,4 @@ GPU; the first register does, and raises if libqsv.so has not been built.
 __version__ = "0.1.0"
 
 from .diagonal import DiagonalOperator  # noqa: E402,F401  (binds nothing until the first operator is made)
+from . import noise  # noqa: E402,F401  (Kraus channels, noise models, trajectories; binds nothing until a channel is used)

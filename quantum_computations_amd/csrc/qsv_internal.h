@@ -113,6 +113,9 @@ struct qsv_state {
     std::vector<QsvOp> queue;         // pending gates, in call order
     uint64_t defer_gates = 0;         // gates that went through the queue
     uint64_t defer_launches = 0;      // launches that applied them (passes + single gates)
+    // Kraus channels (qsv_channel.hip): the register's workspace and branch log, and how qsv_destroy frees them
+    void *channel_work = nullptr;
+    void (*channel_work_free)(void *) = nullptr;
 };
 
 constexpr int QSV_REDUCE_BLOCKS = 1024;
@@ -157,6 +160,7 @@ int qsvk_insert(qsv_state *st, int bit, const double amp[4]);
 int qsvk_permute(qsv_state *st, const int *src_bit_of_dst_bit);
 int qsvk_norm2(qsv_state *st, double *out);
 int qsvk_inner(qsv_state *a, qsv_state *b, double *re, double *im);
+int qsvk_sum_partials(hipStream_t stream, const double *partials, int blocks, int entries, double *out);   // device-side, fixed order
 int qsvk_probabilities(qsv_state *st, const uint64_t *indices, int count, double *out);
 int qsvk_expect_pauli(qsv_state *st, uint64_t xmask, uint64_t zmask, int n_y, double *re, double *im);
 // every pass of a qsv_expect_pauli_sum plan: values[index of the term in the caller's list] = <psi|P|psi>, one synchronisation

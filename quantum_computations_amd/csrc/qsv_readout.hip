@@ -843,6 +843,12 @@ int qsvk_norm2(qsv_state *st, double *out) {
     return sum_partials(st, grid, out, nullptr);
 }
 
+// out[e] = the sum over `blocks` workgroups of partials[block][e], on the device and in a fixed order (k_sum_partials)
+int qsvk_sum_partials(hipStream_t stream, const double *partials, int blocks, int entries, double *out) {
+    hipLaunchKernelGGL(k_sum_partials, dim3((entries + 15) / 16), dim3(QSV_BLOCK), 0, stream, partials, blocks, entries, out);
+    return check_launch();
+}
+
 int qsvk_inner(qsv_state *a, qsv_state *b, double *re, double *im) {
     QSV_HIP(hipStreamSynchronize(b->stream));
     const int grid = grid_for(a->amps, QSV_BLOCK * 8, QSV_REDUCE_BLOCKS);

@@ -604,6 +604,20 @@ class DeviceState:
         from . import krylov
         return krylov.evolve_krylov(self, terms, t, **options)
 
+    # ---- noise (noise.py) ---------------------------------------------------
+    def apply_channel(self, channel, qubits, *, u=None, forced=None, rng=None) -> "DeviceState":
+        """One quantum-trajectory step of the ``noise.KrausChannel`` on ``qubits``: a Kraus branch taken with its Born
+        weight replaces the ket, renormalised.  ``u`` in [0, 1) decides (default: one draw from ``rng``, else from the
+        global ``np.random``, where ``M`` draws); ``forced`` names the branch instead.  Weights, choice and update happen
+        on the device and nothing is downloaded; ``channel_log()`` tells what was taken."""
+        from . import noise
+        return noise._apply_to_ket(self, channel, qubits, u=u, forced=forced, rng=rng)
+
+    def channel_log(self) -> tuple[np.ndarray, np.ndarray]:
+        """``(branches, probabilities)`` of the ``apply_channel`` calls since the last read, in call order."""
+        from . import noise
+        return noise._channel_log(self)
+
     def reduced_density(self, qubits) -> np.ndarray:
         """Reduced density matrix of ``qubits`` (at most six; everything else traced out) as a host
         ``(2^k, 2^k)`` array, ``qubits[0]`` the most significant bit of both indices.  One read pass on the device."""
@@ -759,6 +773,26 @@ class DensityState(DeviceState):
 
     def evolve_krylov(self, terms, t, **options):
         raise ValueError("evolve_krylov is not defined for a density register")
+
+    def apply_channel(self, channel, qubits) -> "DensityState":
+        """``rho <- sum_j K_j rho K_j^dagger`` exactly: one pass with the channel's superoperator on the row and column
+        legs of ``qubits``."""
+        from . import noise
+        return noise._apply_to_density(self, channel, qubits)
+
+    def channel_log(self):
+        raise ValueError("channel_log is not defined for a density register: its channels are exact")
+
+    def trace(self) -> float:
+        """``tr(rho)``: the all-identity term of ``expect_terms``."""
+        return self.expect_terms([(1.0, "", [])]).real
+
+    def expect_terms(self, terms, *, return_terms: bool = False):
+        """``tr(H rho)`` for ``H = sum_t c_t P_t``, terms as in ``expect_pauli_sum``: one launch for all terms, one
+        workgroup per term reading 2^n of the 4^n entries (``qsv_density_expect_paulis``).  Returns the complex value, or
+        ``(value, complex per-term traces in the caller's order)`` with ``return_terms=True``."""
+        from . import noise
+        return noise._density_terms(self, terms, return_terms)
 
     def purity(self) -> float:
         """``tr(rho rho)`` for a hermitian ``rho`` (``npq.purity``): the squared norm of the flattened register."""

@@ -1,0 +1,368 @@
+"""Noisy circuits: Kraus channels on density registers (exact) and on kets (quantum trajectories).
+
+The reference has channels only in its analysis code: ``tomography.quantum_channel(Ks)`` applies ``sum K rho K^dagger`` in
+NumPy to the output of process tomography.  Here a :class:`KrausChannel` is something a circuit can contain:
+
+* on a :class:`~quantum_computations_amd.device.DensityState` it is applied exactly, as one pass with its superoperator
+  ``sum_j K_j (x) conj(K_j)`` on the row and column qubits;
+* on a :class:`~quantum_computations_amd.device.DeviceState` it is one trajectory step: branch ``j`` is drawn with its Born
+  weight ``<psi|K_j^dagger K_j|psi>`` and ``K_j psi`` renormalised replaces the ket.  The weights, the choice and the update
+  all happen on the device (``qsv_apply_channel``); the host supplies one uniform number and waits for nothing.
+
+``NoiseModel`` inserts channels after the gates of a circuit, ``run_trajectories`` averages an observable over shots and
+``run_density`` gives the exact answer the average converges to.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .device import DensityState, DeviceState, _ints
+from .dv_simulator.gates import Gate, _borrow_register, _return_register, is_device_register
+
+_I = np.eye(2, dtype=np.complex128)
+_X = np.array([[0, 1], [1, 0]], dtype=np.complex128)
+_Y = np.array([[0, -1j], [1j, 0]], dtype=np.complex128)
+_Z = np.array([[1, 0], [0, -1]], dtype=np.complex128)
+TRACE_TOL = 1e-12          # KrausChannel(check=True): sum K^dagger K = I to this, entry by entry
+MAX_KRAUS = 16             # what qsv_channel_create takes
+
+
+class KrausChannel:
+    """``rho -> sum_j K_j rho K_j^dagger`` on one or two qubits.
+
+    ``kraus``: a list of 2x2 or 4x4 matrices, or the reference's ``(weights, Ks)`` pair meaning ``sum d K rho K^dagger``
+    (``tomography.quantum_channel``); the weights must not be negative.  ``check``: refuse a list that is not trace
+    preserving to 1e-12."""
+
+    def __init__(self, kraus, *, check: bool = True):
+        if isinstance(kraus, tuple) and len(kraus) == 2 and isinstance(kraus[1], list):
+            weights = np.asarray(kraus[0], dtype=np.float64).reshape(-1)
+            if len(weights) != len(kraus[1]):
+                raise ValueError("one weight per Kraus operator")
+            if np.any(weights < 0.0):
+                raise ValueError("the weights of a (weights, Ks) channel must not be negative")
+            kraus = [np.sqrt(d) * np.asarray(K, dtype=np.complex128) for d, K in zip(weights, kraus[1])]
+        ops = [np.array(K, dtype=np.complex128) for K in kraus]
+        if not 1 <= len(ops) <= MAX_KRAUS:
+            raise ValueError(f"a channel has 1 to {MAX_KRAUS} Kraus operators")
+        dim = ops[0].shape[0] if ops[0].ndim == 2 else 0
+        if dim not in (2, 4) or any(K.shape != (dim, dim) for K in ops):
+            raise ValueError("Kraus operators must all be 2x2 or all 4x4 matrices")
+        if not all(np.all(np.isfinite(K)) for K in ops):
+            raise ValueError("Kraus operators must be finite")
+        self._kraus = np.ascontiguousarray(np.stack(ops))
+        self._kraus.setflags(write=False)
+        if check:
+            total = sum(K.conj().T @ K for K in ops)
+            if np.max(np.abs(total - np.eye(dim))) > TRACE_TOL:
+                raise ValueError("the Kraus operators are not trace preserving: sum K^dagger K differs from the identity")
+        self._handles: dict[int, C.c_void_p] = {}
+
+    # ---- named channels ---------------------------------------------------------------------------------------
+    @classmethod
+    def pauli_channel(cls, px: float, py: float, pz: float) -> "KrausChannel":
+        px, py, pz = float(px), float(py), float(pz)
+        if min(px, py, pz) < 0.0 or px + py + pz > 1.0:
+            raise ValueError("Pauli probabilities must be non-negative and sum to at most 1")
+        return cls([np.sqrt(1.0 - px - py - pz) * _I, np.sqrt(px) * _X, np.sqrt(py) * _Y, np.sqrt(pz) * _Z])
+
+    @classmethod
+    def bit_flip(cls, p: float) -> "KrausChannel":
+        _probability(p)
+        return cls([np.sqrt(1.0 - p) * _I, np.sqrt(p) * _X])
+
+    @classmethod
+    def phase_flip(cls, p: float) -> "KrausChannel":
+        _probability(p)
+        return cls([np.sqrt(1.0 - p) * _I, np.sqrt(p) * _Z])
+
+    @classmethod
+    def bit_phase_flip(cls, p: float) -> "KrausChannel":
+        _probability(p)
+        return cls([np.sqrt(1.0 - p) * _I, np.sqrt(p) * _Y])
+
+    @classmethod
+    def depolarizing(cls, p: float, n_qubits: int = 1) -> "KrausChannel":
+        """``rho -> (1 - p) rho + p/(4^n - 1) sum_{P != I} P rho P``."""
+        _probability(p)
+        if n_qubits == 1:
+            return cls.pauli_channel(p / 3.0, p / 3.0, p / 3.0)
+        if n_qubits != 2:
+            raise ValueError("depolarizing acts on 1 or 2 qubits")
+        paulis = [np.kron(a, b) for a in (_I, _X, _Y, _Z) for b in (_I, _X, _Y, _Z)]
+        return cls([np.sqrt(1.0 - p) * paulis[0]] + [np.sqrt(p / 15.0) * P for P in paulis[1:]])
+
+    @classmethod
+    def amplitude_damping(cls, gamma: float) -> "KrausChannel":
+        _probability(gamma)
+        return cls([np.array([[1, 0], [0, np.sqrt(1.0 - gamma)]]), np.array([[0, np.sqrt(gamma)], [0, 0]])])
+
+    @classmethod
+    def generalized_amplitude_damping(cls, gamma: float, p_excited: float) -> "KrausChannel":
+        """Damping towards the thermal state with excited population ``p_excited``."""
+        _probability(gamma)
+        _probability(p_excited)
+        down, up = np.sqrt(1.0 - p_excited), np.sqrt(p_excited)
+        root = np.sqrt(1.0 - gamma)
+        return cls([down * np.array([[1, 0], [0, root]]), down * np.array([[0, np.sqrt(gamma)], [0, 0]]),
+                    up * np.array([[root, 0], [0, 1]]), up * np.array([[0, 0], [np.sqrt(gamma), 0]])])
+
+    @classmethod
+    def phase_damping(cls, lam: float) -> "KrausChannel":
+        _probability(lam)
+        return cls([np.array([[1, 0], [0, np.sqrt(1.0 - lam)]]), np.array([[0, 0], [0, np.sqrt(lam)]])])
+
+    @classmethod
+    def reset(cls, p: float) -> "KrausChannel":
+        """With probability ``p`` the qubit is replaced by ``|0>``."""
+        _probability(p)
+        return cls([np.sqrt(1.0 - p) * _I, np.sqrt(p) * np.array([[1, 0], [0, 0]]), np.sqrt(p) * np.array([[0, 1], [0, 0]])])
+
+    # ---- properties ---------------------------------------------------------------------------------------------
+    @property
+    def num_qubits(self) -> int:
+        return 1 if self._kraus.shape[1] == 2 else 2
+
+    @property
+    def kraus(self) -> np.ndarray:
+        """``(n_kraus, 2^k, 2^k)`` complex128, read-only."""
+        return self._kraus
+
+    def superoperator(self) -> np.ndarray:
+        """``sum_j K_j (x) conj(K_j)``: the matrix ``DensityState`` applies to the legs ``[q, n + q]`` (one qubit) or
+        ``[q0, q1, n + q0, n + q1]`` (two) -- row legs first, then column legs."""
+        return sum(np.kron(K, K.conj()) for K in self._kraus)
+
+    @property
+    def is_mixed_unitary(self) -> bool:
+        """Every ``K_j^dagger K_j`` is a multiple of the identity (to 16 eps per entry): the branch weights do not depend
+        on the state.  The rule of ``qsv_channel_create``, so that host and library agree without a device.  The 16 eps
+        are absolute: right for operators of a trace-preserving channel, whose entries are at most 1.  With
+        ``check=False`` a list of much larger operators may miss the mark by its own rounding (it only loses the queued
+        path) and one of operators below about 1e-8 always gets it; scale such a list to unit weight first."""
+        dim = self._kraus.shape[1]
+        tol = 16.0 * np.finfo(np.float64).eps
+        for K in self._kraus:
+            E = K.conj().T @ K
+            if np.max(np.abs(E - E[0, 0].real * np.eye(dim))) > tol:
+                return False
+        return True
+
+    # ---- device handles -----------------------------------------------------------------------------------------
+    def handle(self, device: int = 0) -> C.c_void_p:
+        """The ``qsv_channel`` of this channel on ``device``, made on first use and kept."""
+        h = self._handles.get(int(device))
+        if h is None:
+            h = C.c_void_p()
+            buf = np.ascontiguousarray(self._kraus).view(np.float64)
+            _lib.call("qsv_channel_create", self.num_qubits, len(self._kraus), buf.ctypes.data_as(C.POINTER(C.c_double)),
+                      int(device), C.byref(h))
+            self._handles[int(device)] = h
+        return h
+
+    def close(self) -> None:
+        for h in self._handles.values():
+            _lib.load().qsv_channel_destroy(h)
+        self._handles.clear()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __repr__(self):
+        return f"KrausChannel({len(self._kraus)} operators on {self.num_qubits} qubit{'s' if self.num_qubits > 1 else ''})"
+
+
+def _probability(p: float) -> None:
+    if not 0.0 <= float(p) <= 1.0:
+        raise ValueError("a probability lies in [0, 1]")
+
+
+# ---- registers ---------------------------------------------------------------------------------------------------------
+def _apply_to_ket(state: DeviceState, channel: KrausChannel, qubits, *, u=None, forced=None, rng=None) -> DeviceState:
+    qubits = [int(q) for q in qubits]
+    if len(qubits) != channel.num_qubits:
+        raise ValueError(f"the channel acts on {channel.num_qubits} qubits, got {len(qubits)}")
+    if u is None:
+        u = float(rng.random()) if rng is not None else float(np.random.random())     # where M draws, too
+    _lib.call("qsv_apply_channel", state._h, channel.handle(state.device), _ints(qubits), float(u),
+              -1 if forced is None else int(forced))
+    return state
+
+
+def _channel_log(state: DeviceState) -> tuple[np.ndarray, np.ndarray]:
+    count = C.c_uint64(0)
+    _lib.call("qsv_channel_log_read", state._h, None, None, 0, C.byref(count))
+    branches = np.zeros(count.value, dtype=np.int32)
+    probs = np.zeros(count.value, dtype=np.float64)
+    if count.value:
+        _lib.call("qsv_channel_log_read", state._h, branches.ctypes.data_as(C.POINTER(C.c_int32)),
+                  probs.ctypes.data_as(C.POINTER(C.c_double)), count.value, C.byref(count))
+    return branches, probs
+
+
+def _apply_to_density(rho: DensityState, channel: KrausChannel, qubits) -> DensityState:
+    n = rho.num_qubits
+    qubits = [int(q) for q in qubits]
+    if len(qubits) != channel.num_qubits:
+        raise ValueError(f"the channel acts on {channel.num_qubits} qubits, got {len(qubits)}")
+    if any(not 0 <= q < n for q in qubits):
+        raise ValueError(f"qubit index out of range for a {n}-qubit register")
+    if len(set(qubits)) != len(qubits):
+        raise ValueError("Indices must be distinct.")
+    DeviceState.apply_matrix(rho, channel.superoperator(), qubits + [n + q for q in qubits])
+    return rho
+
+
+def _density_terms(rho: DensityState, terms, return_terms: bool):
+    from .device import _flat_terms
+    terms = list(terms)
+    count, offsets, qubits, letters, cbuf = _flat_terms(terms)
+    values = np.zeros(2 * count, dtype=np.float64)
+    _lib.call("qsv_density_expect_paulis", rho._h, count, offsets, qubits, letters, values.ctypes.data_as(C.POINTER(C.c_double)))
+    per_term = values.view(np.complex128)
+    total = complex(sum(complex(c) * v for (c, _, _), v in zip(terms, per_term)))     # in the caller's order
+    return (total, per_term) if return_terms else total
+
+
+# ---- circuits ------------------------------------------------------------------------------------------------------------
+class Channel(Gate):
+    """A channel as a circuit element.  Exact on density matrices (``DensityState`` or a 2-D array), one trajectory step on
+    kets (``DeviceState`` or a 1-D array); either way ``apply`` returns the state alone.  ``rng``: where ket steps draw
+    their uniform number (default: the global ``np.random``, like ``M``)."""
+
+    result_dtype = np.complex128
+
+    def __init__(self, channel: KrausChannel, indices, rng=None):
+        indices = [int(i) for i in indices]
+        if len(indices) != channel.num_qubits:
+            raise ValueError(f"the channel acts on {channel.num_qubits} qubits, got {len(indices)}")
+        super().__init__(indices, None)
+        self.channel = channel
+        self.rng = rng
+
+    def apply(self, state):
+        if isinstance(state, DensityState):
+            return state.apply_channel(self.channel, self.indices)
+        if isinstance(state, DeviceState):
+            return state.apply_channel(self.channel, self.indices, rng=self.rng)
+        if is_device_register(state):
+            raise NotImplementedError("channels on sharded registers are not implemented")
+        state = np.asarray(state)
+        if state.ndim == 1:
+            dev = _borrow_register(state)
+            n = DeviceState.num_qubits.fget(dev)
+            try:
+                dev.apply_channel(self.channel, self.indices, rng=self.rng)
+                out = dev.to_numpy()
+                dev.channel_log()                      # a pooled register goes back with an empty log
+            except BaseException:
+                dev.close()
+                raise
+            _return_register(dev, n)
+            return out
+        if state.ndim == 2:
+            flat = _borrow_register(np.ascontiguousarray(state).reshape(-1))
+            n2 = DeviceState.num_qubits.fget(flat)
+            n = n2 // 2
+            try:
+                if any(not 0 <= q < n for q in self.indices):
+                    raise ValueError(f"qubit index out of range for a {n}-qubit register")
+                flat.apply_matrix(self.channel.superoperator(), self.indices + [n + q for q in self.indices])
+                out = flat.to_numpy().reshape(state.shape)
+            except BaseException:
+                flat.close()
+                raise
+            _return_register(flat, n2)
+            return out
+        raise ValueError("State has wrong dimensions.")
+
+
+class NoiseModel:
+    """Rules ``(which gates, which channel)``; ``insert`` puts a :class:`Channel` after every matching gate."""
+
+    def __init__(self):
+        self._rules: list = []
+
+    def add(self, channel_or_factory, after) -> "NoiseModel":
+        """``after``: a gate class, a tuple of them, or an arity (1 or 2: every plain gate on that many qubits).
+        ``channel_or_factory``: a ``KrausChannel`` or a callable ``gate -> KrausChannel``."""
+        if not (isinstance(after, int) or isinstance(after, type) or
+                (isinstance(after, tuple) and all(isinstance(t, type) for t in after))):
+            raise TypeError("after must be a gate class, a tuple of gate classes or an arity")
+        self._rules.append((after, channel_or_factory))
+        return self
+
+    def _matches(self, after, gate) -> bool:
+        if isinstance(gate, Channel) or not isinstance(gate, Gate):
+            return False
+        if isinstance(after, int):
+            return gate.matrix is not None and gate.matrix.shape[0] == gate.matrix.shape[1] and len(gate.indices) == after
+        return isinstance(gate, after)
+
+    def insert(self, circuit, rng=None) -> list:
+        out = []
+        for gate in circuit:
+            out.append(gate)
+            for after, what in self._rules:
+                if not self._matches(after, gate):
+                    continue
+                channel = what if isinstance(what, KrausChannel) else what(gate)
+                if channel.num_qubits == len(gate.indices):
+                    out.append(Channel(channel, list(gate.indices), rng))
+                elif channel.num_qubits == 1:
+                    out += [Channel(channel, [q], rng) for q in gate.indices]       # one per leg
+                else:
+                    raise ValueError(f"a two-qubit channel cannot follow {gate}")
+        return out
+
+
+def run_density(circuit, initial_state, *, device: int = 0) -> DensityState:
+    """The circuit on the density matrix of ``initial_state`` (a ket or a matrix), channels applied exactly."""
+    state = np.asarray(initial_state)
+    rho = DensityState.from_ket(state, device) if state.ndim == 1 else DensityState.from_numpy(state, device)
+    for gate in circuit:
+        out = gate.apply(rho)
+        if isinstance(out, tuple):
+            raise ValueError("run_density does not take measurements")
+        rho = out
+    return rho
+
+
+def run_trajectories(circuit, initial_state, shots: int, *, terms=None, observable=None, seed=None, device: int = 0) -> dict:
+    """``shots`` quantum trajectories of ``circuit`` from the ket ``initial_state``; the value of a shot is
+    ``<psi|H|psi>`` for the Pauli sum ``terms``, or ``observable(register)``.  Every shot runs on a fresh copy of one
+    uploaded register; all draws come from ``np.random.default_rng(seed)`` in call order.  Returns ``mean``, ``stderr``,
+    ``values`` and the ``branches`` each shot logged."""
+    if (terms is None) == (observable is None):
+        raise ValueError("give terms or observable")
+    rng = np.random.default_rng(seed)
+    start = DeviceState.from_numpy(np.asarray(initial_state), device)
+    work = start.copy()
+    values = np.zeros(int(shots), dtype=np.float64)
+    branches = []
+    terms = list(terms) if terms is not None else None
+    try:
+        for s in range(int(shots)):
+            start.copy_into(work)
+            state = work
+            for gate in circuit:
+                if isinstance(gate, Channel):
+                    state = state.apply_channel(gate.channel, gate.indices, rng=rng)
+                else:
+                    state = gate.apply(state)
+                    if isinstance(state, tuple):
+                        raise ValueError("run_trajectories does not take measurements")
+            values[s] = float(np.real(state.expect_pauli_sum(terms) if terms is not None else observable(state)))
+            branches.append(state.channel_log()[0])
+    finally:
+        start.close()
+        work.close()
+    mean = float(values.mean()) if shots else 0.0
+    stderr = float(values.std(ddof=1) / np.sqrt(shots)) if shots > 1 else 0.0
+    return {"mean": mean, "stderr": stderr, "values": values, "branches": branches}

@@ -387,6 +387,24 @@ int qsv_density_expect_paulis(qsv_state *rho, int n_terms, const int *term_offse
  * significant bit of i and j.  What a caller of the reference gets from npq.ket2dm (numpy_quantum.py:110-113)
  * followed by a partial trace -- without the 2^N x 2^N matrix. */
 int qsv_reduced_density(qsv_state *st, int k, const int *qubits, double *rho);
+/* ---- subsystem read-out past six qubits (csrc/qsv_subsystem.hip) ----
+ * The reduced state of 1 <= k <= min(n, 12) distinct qubits of the n-qubit ket, LEFT ON THE DEVICE: `rho` is a register of
+ * 2k qubits that the library allocated (qsv_create; not a view, not `ket`) on the same device, and receives the 2^k x 2^k
+ * matrix row-major in the layout of a density register, row and column index bit k-1-j <-> qubits[j] (the order of
+ * qsv_reduced_density); every other qubit is traced out.  rho_A = M M^dagger runs on the f64 matrix cores, the output cut
+ * into 64-row blocks over workgroups and the traced index into slices; registers below 14 qubits and shapes with fewer than
+ * 64 traced settings take a per-entry kernel (qsv_last_kernel of the ket: k_subsys_tile / k_subsys_entry).  Both
+ * registers' queues are flushed; the work is enqueued on the ket's stream and the call does not wait for it (if `rho` lives
+ * on another stream, that stream is waited for first, and ordering its later work is the caller's).  The matrix as stored
+ * is exactly Hermitian with a real diagonal, and sums are taken in a fixed order: two calls give the same bits.
+ * QSV_EINVAL for null pointers, k outside 1 .. min(n, 12), qubits repeated or out of range, a `rho` of another size, on
+ * another device, equal to `ket` or a view; QSV_ESTATE for a mode register: each before any launch. */
+int qsv_reduced_density_state(qsv_state *ket, int k, const int *qubits, qsv_state *rho);
+/* The marginal distribution of 1 <= k <= min(n, 26) distinct qubits: out[i] = sum over the other qubits of |amp|^2, 2^k
+ * doubles on the host, index bit k-1-j <-> qubits[j]; k = n is the permuted |amplitude|^2.  One read pass over the
+ * register, fixed summation order, one synchronisation (k_marginal_stream where the traced index is long, else
+ * k_marginal_entry). */
+int qsv_marginal_probabilities(qsv_state *st, int k, const int *qubits, double *out);
 /* <a| rho |a> for an n-qubit ket `ket` and a density matrix `rho` held row-major as a 2n-qubit register (the layout
  * Gate.apply uses for U rho U^dagger): the ket / density-matrix branches of npq.fidelity (numpy_quantum.py:153-156).
  * npq.purity (numpy_quantum.py:164-166) of such a register is qsv_norm2: tr(rho rho) = sum |rho_ij|^2 for a

@@ -8,3 +8,4 @@ __version__ = "0.1.0"
 
 from .diagonal import DiagonalOperator  # noqa: E402,F401  (binds nothing until the first operator is made)
 from . import noise  # noqa: E402,F401  (Kraus channels, noise models, trajectories; binds nothing until a channel is used)
+from . import entanglement  # noqa: E402,F401  (subsystem read-out: reduced states, marginals, entropies; binds nothing until called)

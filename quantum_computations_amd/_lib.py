@@ -92,6 +92,8 @@ SIGNATURES: dict[str, list] = {
     "qsv_channel_log_read": [_state_p, C.POINTER(C.c_int32), _dbl_p, C.c_uint64, _u64_p],
     "qsv_density_expect_paulis": [_state_p, C.c_int, _int_p, _int_p, C.c_char_p, _dbl_p],
     "qsv_reduced_density": [_state_p, C.c_int, _int_p, C.c_void_p],
+    "qsv_reduced_density_state": [_state_p, C.c_int, _int_p, _state_p],
+    "qsv_marginal_probabilities": [_state_p, C.c_int, _int_p, _dbl_p],
     "qsv_expect_density": [_state_p, _state_p, _dbl_p, _dbl_p],
     "qsv_sample": [_state_p, C.c_int, C.c_void_p, C.c_void_p],
     "qsv_create_qudit": [C.c_int, C.c_int, C.c_int, C.POINTER(_state_p)],

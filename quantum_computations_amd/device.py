@@ -629,6 +629,44 @@ class DeviceState:
         _lib.call("qsv_reduced_density", self._h, len(qubits), _ints(qubits), _ptr(out))
         return out
 
+    # ---- subsystems (entanglement.py) ---------------------------------------
+    def reduced_density_state(self, qubits) -> "DensityState":
+        """The reduced state of ``qubits`` (at most 12; everything else traced out) as a ``DensityState`` on this device:
+        ``M M^dagger`` on the matrix cores, nothing downloaded.  Bit order as in ``reduced_density``."""
+        from . import entanglement
+        return entanglement.reduced_density_state(self, qubits)
+
+    def marginal_probabilities(self, qubits) -> np.ndarray:
+        """Probabilities of the ``2^k`` outcomes of ``qubits`` (at most 26), ``qubits[0]`` the most significant bit."""
+        from . import entanglement
+        return entanglement.marginal_probabilities(self, qubits)
+
+    def subsystem_purity(self, qubits) -> float:
+        """``tr(rho_A^2)`` of the cut ``qubits | rest``, taken on its smaller side; no spectrum and no download."""
+        from . import entanglement
+        return entanglement.subsystem_purity(self, qubits)
+
+    def renyi2_entropy(self, qubits, base: float = np.e) -> float:
+        """``-log tr(rho_A^2)`` (``subsystem_purity``)."""
+        from . import entanglement
+        return entanglement.renyi2_entropy(self, qubits, base)
+
+    def schmidt_values(self, qubits) -> np.ndarray:
+        """Schmidt coefficients of the cut ``qubits | rest``, descending (``min(k, n - k) <= 12``)."""
+        from . import entanglement
+        return entanglement.schmidt_values(self, qubits)
+
+    def entanglement_entropy(self, qubits, alpha: float = 1.0, base: float = np.e, *, return_info: bool = False):
+        """Entanglement entropy of the cut ``qubits | rest``: von Neumann for ``alpha = 1``, else Renyi.  The cut is taken
+        on its smaller side, so any bipartition works while ``min(k, n - k) <= 12``; a wider one raises ``ValueError``."""
+        from . import entanglement
+        return entanglement.entanglement_entropy(self, qubits, alpha, base, return_info=return_info)
+
+    def mutual_information(self, a, b, base: float = np.e) -> float:
+        """``S(A) + S(B) - S(AB)`` for two disjoint qubit sets."""
+        from . import entanglement
+        return entanglement.mutual_information(self, a, b, base)
+
     def expect_density(self, rho: "DensityState") -> complex:
         """``<self| rho |self>`` for a density matrix held on the device (the ket / matrix branch of ``npq.fidelity``)."""
         re, im = C.c_double(), C.c_double()
@@ -797,6 +835,23 @@ class DensityState(DeviceState):
     def purity(self) -> float:
         """``tr(rho rho)`` for a hermitian ``rho`` (``npq.purity``): the squared norm of the flattened register."""
         return self.norm2()
+
+    def eigenvalues(self) -> np.ndarray:
+        """The spectrum of ``rho``, ascending and clipped at 0: ``numpy.linalg.eigvalsh`` on the downloaded matrix.  Not
+        a device computation -- 12 qubits cost a 256 MiB download and several seconds on the host."""
+        from . import entanglement
+        return entanglement.spectrum_of(self.to_numpy())
+
+    def von_neumann_entropy(self, base: float = np.e) -> float:
+        """``-tr(rho log rho)`` from ``eigenvalues`` (the same host cost)."""
+        from . import entanglement
+        return entanglement.entropy_of(self.eigenvalues(), 1.0, base)
+
+    def reduced_density_state(self, qubits):
+        raise ValueError("reduced_density_state is not defined for a density register: its partial trace is out of scope")
+
+    def marginal_probabilities(self, qubits):
+        raise ValueError("marginal_probabilities is not defined for a density register")
 
     def fidelity_with_ket(self, ket: DeviceState) -> float:
         return ket.expect_density(self).real

@@ -211,6 +211,51 @@ def fidelity(a, b) -> float:
     return np.sqrt(spectrum).sum() ** 2
 
 
+def _kept_first(state: np.ndarray, qubits) -> np.ndarray:
+    """A host ket as the ``(2^k, 2^(n-k))`` matrix whose row index is the setting of ``qubits`` (``qubits[0]`` the most
+    significant bit) and whose column index is the setting of every other qubit."""
+    state = np.asarray(state)
+    n = state.shape[0].bit_length() - 1
+    qubits = [int(q) for q in qubits]
+    if state.ndim != 1 or state.shape[0] != 1 << n:
+        raise ValueError("State has wrong dimensions.")
+    if not qubits or len(set(qubits)) != len(qubits) or any(not 0 <= q < n for q in qubits):
+        raise ValueError("Indices must be distinct qubits of the register.")
+    rest = [q for q in range(n) if q not in qubits]
+    return state.reshape((2,) * n).transpose(qubits + rest).reshape(1 << len(qubits), -1)
+
+
+def reduced_density(state, qubits):
+    """The reduced density matrix of ``qubits``, every other qubit traced out; ``qubits[0]`` is the most significant bit
+    of both indices.  A host ket gives a host matrix (``M M^dagger``); a ``DeviceState`` gives a ``DensityState`` on its
+    device (at most 12 qubits, ``DeviceState.reduced_density_state``) -- the split ``fidelity`` has."""
+    from ..device import DeviceState
+    if isinstance(state, DeviceState):
+        return state.reduced_density_state(qubits)
+    m = _kept_first(state, qubits)
+    return m @ m.conj().T
+
+
+def marginal_probabilities(state, qubits) -> np.ndarray:
+    """Probabilities of the ``2^k`` outcomes of ``qubits`` with every other qubit summed over (host ket or
+    ``DeviceState``)."""
+    from ..device import DeviceState
+    if isinstance(state, DeviceState):
+        return state.marginal_probabilities(qubits)
+    m = _kept_first(state, qubits)
+    return np.sum(m.real ** 2 + m.imag ** 2, axis=1)
+
+
+def entanglement_entropy(state, qubits, alpha: float = 1.0, base: float = np.e) -> float:
+    """Entanglement entropy of the cut ``qubits | rest`` of a pure state: von Neumann for ``alpha = 1``, else Renyi.  A
+    host ket goes through the singular values of the reshaped ket; a ``DeviceState`` through its reduced state."""
+    from ..device import DeviceState
+    from ..entanglement import entropy_of
+    if isinstance(state, DeviceState):
+        return state.entanglement_entropy(qubits, alpha, base)
+    return entropy_of(np.linalg.svd(_kept_first(state, qubits), compute_uv=False) ** 2, alpha, base)
+
+
 def purity(rho) -> float:
     """``tr(rho rho)`` of a hermitian density matrix (numpy_quantum.py:164-166); a ``DensityState`` is reduced on
     the device."""

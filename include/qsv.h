@@ -382,6 +382,43 @@ int qsv_channel_log_read(qsv_state *st, int32_t *branches, double *probs, uint64
  * of qubits.  The whole list is validated before the flush. */
 int qsv_density_expect_paulis(qsv_state *rho, int n_terms, const int *term_offsets, const int *qubits, const char *paulis,
                               double *values);
+/* ---- trajectory ensembles: many shots of a noisy circuit in one register (csrc/qsv_ensemble.hip) ----
+ * An ensemble is a register of n_total qubits that the library allocated (qsv_create), read as 2^(n_total - member_qubits)
+ * MEMBERS of member_qubits qubits each: member m holds the amplitudes [m 2^member_qubits, (m + 1) 2^member_qubits), i.e. the
+ * member index is the leading n_total - member_qubits qubits of the register and member qubit q is register qubit
+ * q + (n_total - member_qubits).  Any gate on register qubits of the member part acts on every member alike, deferred gates
+ * included; the calls below are the steps that differ from member to member.  `qubits` are MEMBER qubits, 0 .. member_qubits - 1.
+ *  - qsv_ensemble_broadcast copies member 0 into every other member (device-to-device, the filled part doubling).
+ *  - qsv_ensemble_apply_channel is one trajectory step of every member at once, each with its own draw u01[m] and its own
+ *    forced[m] (forced = NULL or forced[m] = -1: draw): the branch rule of qsv_apply_channel member by member.  A read pass
+ *    leaves every member's reduced density matrix of the target qubits in parts, a select kernel adds a member's parts in
+ *    index order, takes the member's branch and writes K_j sqrt(total / w_j) to the member's matrix slot, an in-place update
+ *    pass multiplies every group of amplitudes by the matrix of its own member.  For a mixed-unitary channel the weights are
+ *    the stored p_j: no read pass.  How a member's sums are formed depends on member_qubits, the target qubits and
+ *    QSV_OPT_GRID_CAP only, never on the number of members: a member's results are bit-identical wherever it sits.
+ *    Every call flushes the deferred queue (its matrix differs per member, so it cannot be queued), is enqueued on the
+ *    register's stream and returns without waiting; the draws travel through a pinned ring.
+ *  - Every call appends one STEP, (j, w_j / total) per member, to the register's ensemble log.  The device part holds 256
+ *    steps (fewer beyond 16384 members); a call that finds it full drains it first -- the only time the call synchronises.
+ *    qsv_ensemble_log_read: *steps = steps pending; with capacity_steps >= *steps they are copied out as [steps][members]
+ *    and the log is cleared, otherwise nothing is copied or cleared.  The ensemble log and the log of qsv_apply_channel are
+ *    separate and each keeps its own order.  member_qubits may change between calls only while the ensemble log is empty
+ *    (QSV_ESTATE otherwise).
+ *  - qsv_ensemble_norm2: out[m] = <psi_m|psi_m>.  qsv_ensemble_expect_pauli_sum: values[m] = sum_t coeffs[t] <psi_m|P_t|psi_m>
+ *    (coeffs real, one per term, NULL = all 1; term list as in qsv_expect_pauli_sum) and, if term_values is given,
+ *    term_values[m * n_terms + t]; the passes of qsv_expect_pauli_sum, each followed by a per-member sum on the device in a
+ *    fixed order; one synchronisation at the end.  Both flush the queue.
+ * QSV_EINVAL for null pointers, member_qubits outside k .. n_total (1 .. n_total for the read-outs, 0 .. n_total for the
+ * broadcast), target or term qubits >= member_qubits or repeated, any u01[m] outside [0, 1), any forced[m] outside
+ * -1 .. n_kraus - 1, a channel on another device, a view; QSV_ESTATE for a mode register: each before any launch and with the
+ * deferred queue untouched. */
+int qsv_ensemble_broadcast(qsv_state *st, int member_qubits);
+int qsv_ensemble_apply_channel(qsv_state *st, int member_qubits, qsv_channel *c, const int *qubits, const double *u01 /* members */,
+                               const int *forced /* NULL or members, -1 = draw */);
+int qsv_ensemble_log_read(qsv_state *st, int32_t *branches, double *probs /* [steps][members] */, uint64_t capacity_steps, uint64_t *steps);
+int qsv_ensemble_norm2(qsv_state *st, int member_qubits, double *out /* members */);
+int qsv_ensemble_expect_pauli_sum(qsv_state *st, int member_qubits, int n_terms, const int *term_offsets, const int *qubits, const char *paulis,
+                                  const double *coeffs, double *values /* members */, double *term_values /* NULL or [members][n_terms] */);
 /* Reduced density matrix of the k <= 6 qubits `qubits` (all others traced out) in one read pass over the register:
  * rho[i][j] = sum_rest psi[i, rest] conj(psi[j, rest]), written row-major as 4^k complex numbers, qubits[0] the most
  * significant bit of i and j.  What a caller of the reference gets from npq.ket2dm (numpy_quantum.py:110-113)

@@ -91,6 +91,11 @@ SIGNATURES: dict[str, list] = {
     "qsv_apply_channel": [_state_p, _state_p, _int_p, C.c_double, C.c_int],
     "qsv_channel_log_read": [_state_p, C.POINTER(C.c_int32), _dbl_p, C.c_uint64, _u64_p],
     "qsv_density_expect_paulis": [_state_p, C.c_int, _int_p, _int_p, C.c_char_p, _dbl_p],
+    "qsv_ensemble_broadcast": [_state_p, C.c_int],
+    "qsv_ensemble_apply_channel": [_state_p, C.c_int, _state_p, _int_p, _dbl_p, _int_p],
+    "qsv_ensemble_log_read": [_state_p, C.POINTER(C.c_int32), _dbl_p, C.c_uint64, _u64_p],
+    "qsv_ensemble_norm2": [_state_p, C.c_int, _dbl_p],
+    "qsv_ensemble_expect_pauli_sum": [_state_p, C.c_int, C.c_int, _int_p, _int_p, C.c_char_p, _dbl_p, _dbl_p, _dbl_p],
     "qsv_reduced_density": [_state_p, C.c_int, _int_p, C.c_void_p],
     "qsv_reduced_density_state": [_state_p, C.c_int, _int_p, _state_p],
     "qsv_marginal_probabilities": [_state_p, C.c_int, _int_p, _dbl_p],

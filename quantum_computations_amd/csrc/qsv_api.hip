@@ -389,6 +389,7 @@ int qsv_destroy(qsv_state *st) {
     if (st->partials_host) (void)hipHostFree(st->partials_host);
     if (st->dev_matrix) (void)hipFree(st->dev_matrix);
     if (st->channel_work && st->channel_work_free) st->channel_work_free(st->channel_work);
+    if (st->ensemble_work && st->ensemble_work_free) st->ensemble_work_free(st->ensemble_work);
     if (st->stage_dev) (void)hipFree(st->stage_dev);
     if (st->stage_host) (void)hipHostFree(st->stage_host);
     for (hipEvent_t ev : st->stage_done)

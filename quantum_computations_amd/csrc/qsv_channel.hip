@@ -22,15 +22,6 @@ using namespace qsv_channel_layout;
 static_assert(CH_BLOCK == QSV_BLOCK && CH_REDUCE_BLOCKS == QSV_REDUCE_BLOCKS && CH_LANE_BITS == QSV_LANE_BITS &&
               CH_MIN_STREAM_QUBITS == qsv_readout_layout::RO_MIN_QUBITS, "qsv_channel_layout.h mirrors qsv_internal.h");
 
-struct qsv_channel {
-    int device = 0;
-    int k = 0, D = 0, n_kraus = 0;
-    bool mixed_unitary = false;
-    std::vector<double> p;            // mixed-unitary: E_j = p_j I
-    std::vector<double> unitaries;    // mixed-unitary: K_j / sqrt(p_j) (zeros where p_j = 0), n_kraus x D x D complex
-    double *dev = nullptr;            // K_0 .. K_{n-1}, then E_0 .. E_{n-1}: D x D complex each, row-major
-};
-
 namespace {
 
 // A register's channel workspace (device) and its branch log.  Entries are kept in call order; an entry whose branch was

@@ -1,0 +1,707 @@
+// Trajectory ensembles (gfx950, wave64): 2^b independent n-qubit kets side by side in one (n + b)-qubit register, member m at
+// the amplitudes [m 2^n, (m + 1) 2^n), and the member-wise forms of the steps that do not batch by themselves (DESIGN.md
+// section 23).  A general channel call is two passes over the register and no host synchronisation:
+//   k_ens_channel_rdm     reads the register once and leaves, per member and part, that part's share of the member's reduced
+//                         density matrix of the target qubits (real numbers, rdm_pair_slot order);
+//   k_ens_channel_select  16 threads per member: the member's parts added in index order, then k_channel_select's steps one
+//                         for one -- weights, the choice against the member's own draw, K_j sqrt(total / w_j) into the
+//                         member's matrix slot, (j, w_j / total) into the member's column of the device log;
+//   k_ens_channel_apply   one in-place pass, every group of 2^k amplitudes multiplied by the matrix of its own member.
+// k_ens_expect_pauli_group / k_ens_sum_parts give <psi_m|P_t|psi_m> per member for the passes of qsv_pauli_plan.h.
+// The per-item bodies are those of k_channel_rdm, k_channel_apply and k_expect_pauli_group on a register of 2^n amplitudes;
+// what is new is the member dimension and where the sums stop.  Launch shapes: qsv_ensemble_layout.h.
+
+#include "qsv_device.h"
+#include "qsv_ensemble_layout.h"
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+using namespace qsv_channel_layout;
+using namespace qsv_ensemble_layout;
+using qsv_readout_layout::PauliPass;
+using qsv_readout_layout::PauliPassArgs;
+using qsv_readout_layout::pauli_pass_args;
+
+static_assert(CH_BLOCK == QSV_BLOCK && CH_LANE_BITS == QSV_LANE_BITS, "qsv_channel_layout.h mirrors qsv_internal.h");
+
+namespace {
+
+// A register's ensemble workspace (device), its pinned ring of draws and its branch log.  Every step of the log is chosen on
+// the device: the first `host_steps` steps are already in host memory, the next `used` sit in the device slots 0 .. used-1.
+struct EnsembleWork {
+    int device = 0;
+    int n = -1;                       // member qubits the workspace was sized for
+    EnsWorkspace ws;
+    double *dev = nullptr;            // ws.doubles doubles
+    double *ring = nullptr;           // pinned host: [ws.slots][members][2], the draws of the step that will fill that log slot
+    int used = 0;
+    std::vector<int32_t> branches;    // [host steps][members]
+    std::vector<double> probs;
+};
+
+void free_ensemble_work(void *p) {
+    EnsembleWork *w = static_cast<EnsembleWork *>(p);
+    if (!w) return;
+    (void)hipSetDevice(w->device);
+    if (w->dev) (void)hipFree(w->dev);
+    if (w->ring) (void)hipHostFree(w->ring);
+    delete w;
+}
+
+EnsembleWork *work_of(qsv_state *st) {
+    if (!st->ensemble_work) {
+        EnsembleWork *w = new EnsembleWork;
+        w->device = st->device;
+        st->ensemble_work = w;
+        st->ensemble_work_free = free_ensemble_work;
+    }
+    return static_cast<EnsembleWork *>(st->ensemble_work);
+}
+
+uint64_t pending_steps(const EnsembleWork *w) { return w->ws.members ? w->branches.size() / w->ws.members + w->used : 0; }
+
+// Device log -> host entries.  One copy and one synchronisation; the only time qsv_ensemble_apply_channel may wait.
+int drain(qsv_state *st, EnsembleWork *w) {
+    if (w->used == 0) return QSV_OK;
+    const size_t count = static_cast<size_t>(w->used) * w->ws.members;
+    std::vector<double> host(2 * count);
+    QSV_HIP(hipMemcpyAsync(host.data(), w->dev + w->ws.log, sizeof(double) * host.size(), hipMemcpyDeviceToHost, st->stream));
+    QSV_HIP(hipStreamSynchronize(st->stream));
+    for (size_t e = 0; e < count; ++e) {
+        w->branches.push_back(static_cast<int32_t>(host[2 * e]));
+        w->probs.push_back(host[2 * e + 1]);
+    }
+    w->used = 0;
+    return QSV_OK;
+}
+
+// Sized at the first call; re-made when the member size changes (only with an empty log: its rows have `members` columns).
+int ensure_workspace(qsv_state *st, EnsembleWork *w, int n, uint64_t members) {
+    if (w->dev && w->n == n && w->ws.members == members) return QSV_OK;
+    QSV_HIP(hipStreamSynchronize(st->stream));
+    if (w->dev) (void)hipFree(w->dev);
+    if (w->ring) (void)hipHostFree(w->ring);
+    w->dev = nullptr;
+    w->ring = nullptr;
+    w->n = -1;
+    const EnsWorkspace ws = ens_workspace(n, members);
+    if (hipMalloc(reinterpret_cast<void **>(&w->dev), sizeof(double) * ws.doubles) != hipSuccess) {
+        w->dev = nullptr;
+        return qsv_fail(QSV_ENOMEM, "device allocation of the ensemble workspace failed");
+    }
+    if (hipHostMalloc(reinterpret_cast<void **>(&w->ring), sizeof(double) * 2 * members * ws.slots, hipHostMallocDefault) != hipSuccess) {
+        (void)hipFree(w->dev);
+        w->dev = nullptr;
+        w->ring = nullptr;
+        return qsv_fail(QSV_ENOMEM, "pinned allocation of the ensemble draws failed");
+    }
+    w->ws = ws;
+    w->n = n;
+    w->used = 0;
+    return QSV_OK;
+}
+
+// ---- device -----------------------------------------------------------------------------------------------------------------
+
+// x conj(y)
+__device__ __forceinline__ amp_t mul_conj(amp_t x, amp_t y) {
+    return amp_t{fma(x.x, y.x, x.y * y.y), fma(x.y, y.x, -(x.x * y.y))};
+}
+template <int KL>
+__device__ __forceinline__ int glo_of(const ChannelArgs &g, int l) {
+    int v = 0;
+    if constexpr (KL >= 1) v |= (l & 1) ? g.glo[1] : 0;
+    if constexpr (KL >= 2) v |= (l & 2) ? g.glo[2] : 0;
+    return v;
+}
+template <int KL>
+__device__ __forceinline__ int own_combination(const ChannelArgs &g) {
+    const int lane = threadIdx.x & 63;
+    int l = 0;
+    if constexpr (KL >= 1) l |= (lane >> g.lbit[0]) & 1;
+    if constexpr (KL >= 2) l |= ((lane >> g.lbit[1]) & 1) << 1;
+    return l;
+}
+
+// What a thread works on in unit `unit` (ens_thread of qsv_ensemble_layout.h, step for step).
+struct Mine {
+    uint64_t group, part, member, first, stride, items;
+    uint32_t local;
+    bool live;       // member < members
+};
+__device__ __forceinline__ Mine mine(const EnsArgs &e, uint64_t unit) {
+    Mine t;
+    const uint32_t tid = threadIdx.x;
+    const bool shared = e.item_bits < ENS_BLOCK_BITS;
+    t.group = unit >> e.part_bits;
+    t.part = unit & ((1ull << e.part_bits) - 1ull);
+    t.member = (t.group << e.share_bits) + (shared ? tid >> e.item_bits : 0u);
+    t.local = shared ? tid & ((1u << e.item_bits) - 1u) : tid;
+    t.first = (t.part << ENS_BLOCK_BITS) + t.local;
+    t.stride = static_cast<uint64_t>(QSV_BLOCK) << e.part_bits;
+    t.items = 1ull << e.item_bits;
+    t.live = t.member < e.members;
+    return t;
+}
+
+// The sums of R doubles per thread, member by member: partials[(member * P + part) * R + e].  A member of fewer than 64 items
+// is a run of aligned lanes and is summed by a butterfly over that run alone; from 64 items on the waves of a member are
+// added in index order through LDS.  The order of every addition depends on the thread's place inside its member only.
+// Every thread of the workgroup must call this (shuffles and barriers).
+template <int R>
+__device__ __forceinline__ void member_store_sums(double (&v)[R], const EnsArgs &e, const Mine &t, double *__restrict__ partials) {
+    const int segment = 1 << (e.item_bits < 6 ? e.item_bits : 6);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        if (o < segment) {     // wave-uniform
+#pragma unroll
+            for (int r = 0; r < R; ++r) v[r] += __shfl_xor(v[r], o, 64);
+        }
+    }
+    if (e.item_bits < 6) {     // one part; the first lane of the member's run holds its sums
+        if (t.local == 0 && t.live) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) partials[t.member * R + r] = v[r];
+        }
+        return;
+    }
+    __shared__ double sums[QSV_BLOCK / 64][R];
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) sums[threadIdx.x >> 6][r] = v[r];
+    }
+    __syncthreads();
+    const int wave_bits = e.item_bits - 6 < 2 ? e.item_bits - 6 : 2;     // log2 of the waves of one member in this workgroup
+    const int sharing = (QSV_BLOCK / 64) >> wave_bits;                    // members in this workgroup
+    if (threadIdx.x < sharing * R) {
+        const int s = threadIdx.x / R, r = threadIdx.x % R;
+        const uint64_t member = (t.group << e.share_bits) + s;
+        if (member < e.members) {
+            double sum = 0.0;
+            for (int wv = 0; wv < (1 << wave_bits); ++wv) sum += sums[(s << wave_bits) + wv][r];
+            partials[((member << e.part_bits) + t.part) * R + r] = sum;
+        }
+    }
+    __syncthreads();     // the next unit writes sums again
+}
+
+// k_channel_rdm's item body on member-local indices.  Read-only.
+template <int K, int KL, bool NT>
+__global__ __launch_bounds__(QSV_BLOCK) void k_ens_channel_rdm(const amp_t *__restrict__ a, const ChannelArgs g, const EnsArgs e,
+                                                               double *__restrict__ partials) {
+    constexpr int KH = K - KL, NH = 1 << KH, NL = 1 << KL, D = 1 << K, R = D * D;
+    const int l_own = own_combination<KL>(g);
+    for (uint64_t unit = blockIdx.x; unit < e.units; unit += gridDim.x) {
+        const Mine t = mine(e, unit);
+        amp_t acc[NH][NH][NL];
+#pragma unroll
+        for (int h = 0; h < NH; ++h)
+#pragma unroll
+            for (int j = 0; j < NH; ++j)
+#pragma unroll
+                for (int dl = 0; dl < NL; ++dl) acc[h][j][dl] = amp_t{0.0, 0.0};
+        if (t.live) {
+            // KL > 0: the items of a member are a multiple of 64 and `live` is the same for a whole wave: a wave is in the
+            // loop as a whole
+            const amp_t *am = a + (t.member << e.n);
+            for (uint64_t w = t.first; w < t.items; w += t.stride) {
+                const uint64_t base = deposit(w, g);
+                amp_t x[NH];
+#pragma unroll
+                for (int h = 0; h < NH; ++h) x[h] = ld<NT>(am + base + g.hoff[h]);
+#pragma unroll
+                for (int j = 0; j < NH; ++j)
+#pragma unroll
+                    for (int dl = 0; dl < NL; ++dl) {
+                        const amp_t y = dl == 0 ? x[j] : shfl_xor_amp(x[j], g.lxor[dl]);
+#pragma unroll
+                        for (int h = 0; h < NH; ++h) {
+                            if (KL == 0 && h > j) continue;
+                            const amp_t p = mul_conj(x[h], y);
+                            acc[h][j][dl].x += p.x;
+                            acc[h][j][dl].y += p.y;
+                        }
+                    }
+            }
+        }
+        double v[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) v[r] = 0.0;
+#pragma unroll
+        for (int h = 0; h < NH; ++h)
+#pragma unroll
+            for (int j = 0; j < NH; ++j)
+#pragma unroll
+                for (int dl = 0; dl < NL; ++dl) {
+                    if (KL == 0 && h > j) continue;
+                    int r = g.ghi[h] | glo_of<KL>(g, l_own), c = g.ghi[j] | glo_of<KL>(g, l_own ^ dl);
+                    const double re = acc[h][j][dl].x;
+                    double im = acc[h][j][dl].y;
+                    if (KL == 0 && r > c) {
+                        const int s = r;
+                        r = c;
+                        c = s;
+                        im = -im;
+                    }
+                    int slot = D;      // rdm_pair_slot, walked in its own order
+#pragma unroll
+                    for (int rr = 0; rr < D; ++rr) {
+                        v[rr] += (r == rr && c == rr) ? re : 0.0;
+#pragma unroll
+                        for (int cc = rr + 1; cc < D; ++cc) {
+                            const bool hit = r == rr && c == cc;
+                            v[slot] += hit ? re : 0.0;
+                            v[slot + 1] += hit ? im : 0.0;
+                            slot += 2;
+                        }
+                    }
+                }
+        member_store_sums<R>(v, e, t, partials);
+    }
+}
+
+// 16 threads per member, 16 members per workgroup.  partials: [members][P][R] (unused for a mixed-unitary channel, whose
+// weights are the stored p_j = E_j[0][0]); chan: K_0 .. K_{n-1} then E_0 .. E_{n-1}; draws: [members][2] = u, forced branch
+// (-1: draw); matrix: [members][32]; log: [members][2] of this step.  The steps of k_channel_select, one member per group.
+__global__ __launch_bounds__(QSV_BLOCK) void k_ens_channel_select(const double *__restrict__ partials, int parts, const double *__restrict__ chan,
+                                                                  int n_kraus, int D, int mixed, const double *__restrict__ draws, uint64_t members,
+                                                                  double *__restrict__ matrix, double *__restrict__ log) {
+    constexpr int GROUPS = QSV_BLOCK / ENS_SELECT_LANES;
+    __shared__ double rho[GROUPS][16];
+    __shared__ double wt[GROUPS][CH_MAX_KRAUS];
+    __shared__ int chosen[GROUPS];
+    __shared__ double scale[GROUPS];
+    const int s = threadIdx.x / ENS_SELECT_LANES, t = threadIdx.x % ENS_SELECT_LANES, DD = D * D;
+    for (uint64_t first = static_cast<uint64_t>(blockIdx.x) * GROUPS; first < members; first += static_cast<uint64_t>(gridDim.x) * GROUPS) {
+        const uint64_t m = first + s;
+        const bool live = m < members;
+        if (live && !mixed && t < DD) {
+            const double *p = partials + m * parts * DD + t;
+            double sum = 0.0;
+            for (int q = 0; q < parts; ++q) sum += p[static_cast<size_t>(q) * DD];      // index order
+            rho[s][t] = sum;
+        }
+        __syncthreads();
+        if (live && t < n_kraus) {
+            const double *E = chan + 2 * static_cast<size_t>(DD) * (n_kraus + t);
+            if (mixed) {
+                wt[s][t] = E[0];
+            } else {
+                double d = 0.0;
+                for (int r = 0; r < D; ++r) d += E[2 * (r * D + r)] * rho[s][r];
+                int slot = D;
+                double off = 0.0;
+                for (int r = 0; r < D; ++r)
+                    for (int c = r + 1; c < D; ++c) {
+                        off += E[2 * (r * D + c)] * rho[s][slot] + E[2 * (r * D + c) + 1] * rho[s][slot + 1];
+                        slot += 2;
+                    }
+                wt[s][t] = d + 2.0 * off;
+            }
+        }
+        __syncthreads();
+        if (live && t == 0) {
+            double total = 0.0;
+            for (int j = 0; j < n_kraus; ++j) total += wt[s][j];
+            const double u = draws[2 * m];
+            int pick = static_cast<int>(draws[2 * m + 1]);
+            if (pick < 0) {
+                const double target = u * total;
+                double run = 0.0;
+                int last = -1;
+                for (int j = 0; j < n_kraus && pick < 0; ++j) {
+                    run += wt[s][j];
+                    if (wt[s][j] > 0.0) last = j;
+                    if (run > target && wt[s][j] > 0.0) pick = j;
+                }
+                if (pick < 0) pick = last < 0 ? 0 : last;
+            }
+            const double wj = wt[s][pick];
+            const bool alive = wj > 0.0 && total > 0.0;
+            chosen[s] = pick;
+            scale[s] = alive ? sqrt(total / wj) : 0.0;
+            log[2 * m] = static_cast<double>(pick);
+            log[2 * m + 1] = alive ? wj / total : 0.0;
+        }
+        __syncthreads();
+        if (live && t < DD) {
+            const double *Kj = chan + 2 * static_cast<size_t>(DD) * chosen[s];
+            const double sc = scale[s];
+            // a scale of 0 writes zeros whatever K_j holds (0 * inf would not)
+            matrix[32 * m + 2 * t] = sc != 0.0 ? Kj[2 * t] * sc : 0.0;
+            matrix[32 * m + 2 * t + 1] = sc != 0.0 ? Kj[2 * t + 1] * sc : 0.0;
+        }
+        __syncthreads();     // the next round writes the shared arrays again
+    }
+}
+
+// k_channel_apply's item body on member-local indices, with the matrix of the thread's own member.  Where a unit lies in one
+// member (256 items or more) the member index is the same for the whole workgroup and the entries are fetched once per unit,
+// before the item loop; where members share a unit the index differs between the threads of a wave and each fetches its own.
+template <int K, int KL, bool NT>
+__global__ __launch_bounds__(QSV_BLOCK) void k_ens_channel_apply(amp_t *__restrict__ a, const ChannelArgs g, const EnsArgs e,
+                                                                 const double *__restrict__ matrix) {
+    constexpr int KH = K - KL, NH = 1 << KH, NL = 1 << KL, D = 1 << K;
+    const int l_own = own_combination<KL>(g);
+    for (uint64_t unit = blockIdx.x; unit < e.units; unit += gridDim.x) {
+        const Mine t = mine(e, unit);
+        if (!t.live) continue;     // whole waves (KL > 0), and no barrier in this kernel
+        const double *m = matrix + 32 * t.member;
+        cplx mm[NH][NH][NL];
+#pragma unroll
+        for (int h = 0; h < NH; ++h)
+#pragma unroll
+            for (int j = 0; j < NH; ++j)
+#pragma unroll
+                for (int dl = 0; dl < NL; ++dl) {
+                    const int r = g.ghi[h] | glo_of<KL>(g, l_own), c = g.ghi[j] | glo_of<KL>(g, l_own ^ dl);
+                    mm[h][j][dl] = cplx{m[2 * (r * D + c)], m[2 * (r * D + c) + 1]};
+                }
+        amp_t *am = a + (t.member << e.n);
+        for (uint64_t w = t.first; w < t.items; w += t.stride) {
+            const uint64_t base = deposit(w, g);
+            amp_t x[NH], out[NH];
+#pragma unroll
+            for (int h = 0; h < NH; ++h) {
+                x[h] = ld<NT>(am + base + g.hoff[h]);
+                out[h] = amp_t{0.0, 0.0};
+            }
+#pragma unroll
+            for (int j = 0; j < NH; ++j)
+#pragma unroll
+                for (int dl = 0; dl < NL; ++dl) {
+                    const amp_t y = dl == 0 ? x[j] : shfl_xor_amp(x[j], g.lxor[dl]);
+#pragma unroll
+                    for (int h = 0; h < NH; ++h) out[h] = cfma(mm[h][j][dl], y, out[h]);
+                }
+#pragma unroll
+            for (int h = 0; h < NH; ++h) st<NT>(am + base + g.hoff[h], out[h]);
+        }
+    }
+}
+
+// k_expect_pauli_group's item body on member-local indices (g.items is not used: the items of a member are e.item_bits).
+constexpr int ENS_PAULI_ITEMS = 4;
+template <int T, bool DIAG>
+__global__ __launch_bounds__(QSV_BLOCK) void k_ens_expect_pauli_group(const amp_t *__restrict__ a, const PauliPassArgs g, const EnsArgs e,
+                                                                     double *__restrict__ partials) {
+    for (uint64_t unit = blockIdx.x; unit < e.units; unit += gridDim.x) {
+        const Mine t = mine(e, unit);
+        double acc[T];
+#pragma unroll
+        for (int k = 0; k < T; ++k) acc[k] = 0.0;
+        auto add = [&](uint64_t i, double re, double im) {
+#pragma unroll
+            for (int k = 0; k < T; ++k) {
+                const double v = (!DIAG && ((g.odd >> k) & 1u)) ? im : re;
+                acc[k] += (__popcll(i & g.zmask[k]) & 1) ? -v : v;
+            }
+        };
+        if (t.live) {
+            const amp_t *am = a + (t.member << e.n);
+            uint64_t w = t.first;
+            // ENS_PAULI_ITEMS independent items are loaded before any is used, as in k_expect_pauli_group; they are added in
+            // item order, so the sums are those of the plain loop below
+            for (; w + (ENS_PAULI_ITEMS - 1) * t.stride < t.items; w += ENS_PAULI_ITEMS * t.stride) {
+                uint64_t i[ENS_PAULI_ITEMS];
+                amp_t x[ENS_PAULI_ITEMS], y[ENS_PAULI_ITEMS];
+#pragma unroll
+                for (int u = 0; u < ENS_PAULI_ITEMS; ++u) {
+                    i[u] = DIAG ? w + u * t.stride : insert_zero(w + u * t.stride, g.pivot);
+                    y[u] = am[i[u]];
+                    if constexpr (!DIAG) x[u] = am[i[u] ^ g.xmask];
+                }
+#pragma unroll
+                for (int u = 0; u < ENS_PAULI_ITEMS; ++u) {
+                    if constexpr (DIAG) add(i[u], y[u].x * y[u].x + y[u].y * y[u].y, 0.0);
+                    else add(i[u], x[u].x * y[u].x + x[u].y * y[u].y, x[u].x * y[u].y - x[u].y * y[u].x);   // conj(x) * y
+                }
+            }
+            for (; w < t.items; w += t.stride) {
+                const uint64_t i = DIAG ? w : insert_zero(w, g.pivot);
+                const amp_t y = am[i];
+                if constexpr (DIAG) {
+                    add(i, y.x * y.x + y.y * y.y, 0.0);
+                } else {
+                    const amp_t x = am[i ^ g.xmask];
+                    add(i, x.x * y.x + x.y * y.y, x.x * y.y - x.y * y.x);
+                }
+            }
+        }
+        member_store_sums<T>(acc, e, t, partials);
+    }
+}
+
+// out[m * R + r] = sum over the parts of member m of partials[(m * P + p) * R + r], in index order
+__global__ __launch_bounds__(QSV_BLOCK) void k_ens_sum_parts(const double *__restrict__ partials, uint64_t members, int parts, int R,
+                                                             double *__restrict__ out) {
+    const uint64_t count = members * R, stride = static_cast<uint64_t>(gridDim.x) * QSV_BLOCK;
+    for (uint64_t i = blockIdx.x * static_cast<uint64_t>(QSV_BLOCK) + threadIdx.x; i < count; i += stride) {
+        const uint64_t m = i / R;
+        const int r = static_cast<int>(i % R);
+        const double *p = partials + m * parts * R + r;
+        double sum = 0.0;
+        for (int q = 0; q < parts; ++q) sum += p[static_cast<size_t>(q) * R];
+        out[i] = sum;
+    }
+}
+
+template <class F>
+void with_shape(int k, int kl, bool nt, F &&f) {
+    with_bool(nt, [&](auto NT) {
+        if (k == 1 && kl == 0) f(std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{}, NT);
+        else if (k == 1) f(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{}, NT);
+        else if (kl == 0) f(std::integral_constant<int, 2>{}, std::integral_constant<int, 0>{}, NT);
+        else if (kl == 1) f(std::integral_constant<int, 2>{}, std::integral_constant<int, 1>{}, NT);
+        else f(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{}, NT);
+    });
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------
+
+// what every ensemble call refuses about the register and the member size
+int check_ensemble(const qsv_state *st, int member_qubits, int least) {
+    if (!st) return qsv_fail(QSV_EINVAL, "null pointer");
+    if (st->kind != 0) return qsv_fail(QSV_ESTATE, "this call needs a qubit register");
+    if (!st->owns_data) return qsv_fail(QSV_EINVAL, "an ensemble lives in a register the library allocated, not in a view");
+    if (member_qubits < least || member_qubits > st->n)
+        return qsv_fail(QSV_EINVAL, "member_qubits must lie between " + std::to_string(least) + " and the register's " + std::to_string(st->n) + " qubits");
+    return QSV_OK;
+}
+
+int check_member_qubits(int member_qubits, int count, const int *qubits) {
+    for (int i = 0; i < count; ++i) {
+        if (qubits[i] < 0) return qsv_fail(QSV_EINVAL, "Non-negative index");
+        if (qubits[i] >= member_qubits)
+            return qsv_fail(QSV_EINVAL, "qubit index " + std::to_string(qubits[i]) + " out of range for members of " + std::to_string(member_qubits) + " qubits");
+        for (int j = 0; j < i; ++j)
+            if (qubits[i] == qubits[j]) return qsv_fail(QSV_EINVAL, "Indices must be distinct.");
+    }
+    return QSV_OK;
+}
+
+// values[pass offset + m * width + t] for every pass, summed per member on the device; one copy, one synchronisation
+int expect_passes(qsv_state *st, int n, const std::vector<qsv_pauli_plan::Pass> &passes, std::vector<double> *host, std::vector<size_t> *offsets,
+                  std::vector<int> *widths) {
+    const uint64_t members = st->amps >> n;
+    size_t doubles = 0, most_partials = 0;
+    struct Launch { PauliPass pass; EnsArgs e; };
+    std::vector<Launch> launches;
+    for (const qsv_pauli_plan::Pass &p : passes) {
+        const PauliPass pass = pauli_pass_args(p, 1ull << n);
+        if (!pass.ok) return qsv_fail(QSV_EINVAL, "bad Pauli pass");
+        const int item_bits = p.pivot < 0 ? n : n - 1;
+        const EnsArgs e = ens_args(n, members, item_bits, part_bits(item_bits, st->grid_cap));
+        launches.push_back({pass, e});
+        offsets->push_back(doubles);
+        widths->push_back(pass.width);
+        doubles += static_cast<size_t>(members) * pass.width;
+        most_partials = std::max(most_partials, (static_cast<size_t>(members) << e.part_bits) * pass.width);
+    }
+    int rc = qsvk_ensure_matrix(st, sizeof(double) * (doubles + most_partials));
+    if (rc) return rc;
+    double *values = st->dev_matrix, *partials = st->dev_matrix + doubles;
+    for (size_t k = 0; k < passes.size(); ++k) {
+        const Launch &l = launches[k];
+        with_pow2<1, 8>(l.pass.width, [&](auto W) { with_bool(passes[k].pivot < 0, [&](auto DIAG) {
+            hipLaunchKernelGGL((k_ens_expect_pauli_group<W.value, DIAG.value>), dim3(ens_grid(l.e, st->grid_cap)), dim3(QSV_BLOCK), 0, st->stream,
+                               static_cast<const amp_t *>(st->data), l.pass.g, l.e, partials);
+        }); });
+        rc = check_launch();
+        if (rc) return rc;
+        const uint64_t count = members * l.pass.width;
+        hipLaunchKernelGGL(k_ens_sum_parts, dim3(grid_for(count, QSV_BLOCK, QSV_REDUCE_BLOCKS)), dim3(QSV_BLOCK), 0, st->stream,
+                           static_cast<const double *>(partials), members, 1 << l.e.part_bits, l.pass.width, values + (*offsets)[k]);
+        rc = check_launch();
+        if (rc) return rc;
+    }
+    snprintf(st->last_kernel, sizeof(st->last_kernel), "k_ens_expect_pauli_group");
+    host->assign(doubles, 0.0);
+    QSV_HIP(hipMemcpyAsync(host->data(), values, sizeof(double) * doubles, hipMemcpyDeviceToHost, st->stream));
+    QSV_HIP(hipStreamSynchronize(st->stream));
+    return QSV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qsv_ensemble_broadcast(qsv_state *st, int member_qubits) {
+    int rc = check_ensemble(st, member_qubits, 0);
+    if (rc) return rc;
+    rc = qsv_flush(st);
+    if (rc) return rc;
+    QSV_HIP(hipSetDevice(st->device));
+    // the filled part doubles with every copy; source and destination never meet
+    for (uint64_t filled = 1ull << member_qubits; filled < st->amps; filled *= 2) {
+        rc = qsvk_copy(st->data + filled, st->data, filled, st->stream);
+        if (rc) return rc;
+    }
+    return QSV_OK;
+}
+
+int qsv_ensemble_apply_channel(qsv_state *st, int member_qubits, qsv_channel *c, const int *qubits, const double *u01, const int *forced) {
+    if (!st || !c || !qubits || !u01) return qsv_fail(QSV_EINVAL, "null pointer");
+    int rc = check_ensemble(st, member_qubits, c->k);
+    if (rc) return rc;
+    if (st->device != c->device) return qsv_fail(QSV_EINVAL, "register and channel on different devices");
+    rc = check_member_qubits(member_qubits, c->k, qubits);
+    if (rc) return rc;
+    const int n = member_qubits;
+    const uint64_t members = st->amps >> n;
+    for (uint64_t m = 0; m < members; ++m) {
+        if (!(u01[m] >= 0.0 && u01[m] < 1.0)) return qsv_fail(QSV_EINVAL, "every draw must lie in [0, 1)");
+        if (forced && (forced[m] < -1 || forced[m] >= c->n_kraus)) return qsv_fail(QSV_EINVAL, "forced branch out of range");
+    }
+    EnsembleWork *work = work_of(st);
+    if (work->dev && (work->n != n || work->ws.members != members) && pending_steps(work) > 0)
+        return qsv_fail(QSV_ESTATE, "read the ensemble log before changing the member size");
+    rc = qsv_flush(st);
+    if (rc) return rc;
+    QSV_HIP(hipSetDevice(st->device));
+    rc = ensure_workspace(st, work, n, members);
+    if (rc) return rc;
+    if (work->used == work->ws.slots) {
+        rc = drain(st, work);
+        if (rc) return rc;
+    }
+    // the draws: the ring slot of this step's log slot, which the drain above (or the log read) has made free
+    double *slot = work->ring + 2 * members * static_cast<size_t>(work->used);
+    for (uint64_t m = 0; m < members; ++m) {
+        slot[2 * m] = u01[m];
+        slot[2 * m + 1] = forced ? static_cast<double>(forced[m]) : -1.0;
+    }
+    double *partials = work->dev + work->ws.partials, *matrix = work->dev + work->ws.matrix, *draws = work->dev + work->ws.draws;
+    double *log = work->dev + work->ws.log + 2 * members * static_cast<size_t>(work->used);
+    QSV_HIP(hipMemcpyAsync(draws, slot, sizeof(double) * 2 * members, hipMemcpyHostToDevice, st->stream));
+    int bits[2] = {0, 0};
+    for (int i = 0; i < c->k; ++i) bits[i] = n - 1 - qubits[i];
+    const ChannelPlan plan = ens_channel_plan(n, c->k, bits, ens_lanes(n, st->readout_variant != 1));
+    const bool nt = st->nontemporal != 0;
+    const int item_bits = n - plan.kh;
+    const EnsArgs read = ens_args(n, members, item_bits, part_bits(item_bits, st->grid_cap));
+    const EnsArgs update = ens_args(n, members, item_bits, apply_part_bits(item_bits, st->grid_cap));
+    if (!c->mixed_unitary) {
+        with_shape(plan.k, plan.kl, nt, [&](auto K, auto KL, auto NT) {
+            hipLaunchKernelGGL((k_ens_channel_rdm<K.value, KL.value, NT.value>), dim3(ens_grid(read, st->grid_cap)), dim3(QSV_BLOCK), 0, st->stream,
+                               static_cast<const amp_t *>(st->data), plan.g, read, partials);
+        });
+        rc = check_launch();
+        if (rc) return rc;
+    }
+    const uint64_t select_blocks = (members + QSV_BLOCK / ENS_SELECT_LANES - 1) / (QSV_BLOCK / ENS_SELECT_LANES);
+    hipLaunchKernelGGL(k_ens_channel_select, dim3(static_cast<unsigned>(std::min<uint64_t>(select_blocks, CH_MAX_BLOCKS))), dim3(QSV_BLOCK), 0, st->stream,
+                       static_cast<const double *>(partials), 1 << read.part_bits, static_cast<const double *>(c->dev), c->n_kraus, c->D,
+                       c->mixed_unitary ? 1 : 0, static_cast<const double *>(draws), members, matrix, log);
+    rc = check_launch();
+    if (rc) return rc;
+    ++work->used;     // the log slot is written from here on, whatever becomes of the update pass
+    with_shape(plan.k, plan.kl, nt, [&](auto K, auto KL, auto NT) {
+        hipLaunchKernelGGL((k_ens_channel_apply<K.value, KL.value, NT.value>), dim3(ens_grid(update, st->grid_cap)), dim3(QSV_BLOCK), 0, st->stream,
+                           st->data, plan.g, update, static_cast<const double *>(matrix));
+    });
+    snprintf(st->last_kernel, sizeof(st->last_kernel), "k_ens_channel_apply<%d, %d, %s>%s", plan.k, plan.kl, nt ? "true" : "false",
+             c->mixed_unitary ? " after k_ens_channel_select" : " after k_ens_channel_rdm");
+    return check_launch();
+}
+
+int qsv_ensemble_log_read(qsv_state *st, int32_t *branches, double *probs, uint64_t capacity_steps, uint64_t *steps) {
+    if (!st || !steps) return qsv_fail(QSV_EINVAL, "null pointer");
+    if (capacity_steps && (!branches || !probs)) return qsv_fail(QSV_EINVAL, "null pointer");
+    EnsembleWork *work = static_cast<EnsembleWork *>(st->ensemble_work);
+    const uint64_t pending = work ? pending_steps(work) : 0;
+    *steps = pending;
+    if (pending == 0 || capacity_steps < pending) return QSV_OK;
+    QSV_HIP(hipSetDevice(st->device));
+    QSV_HIP(hipStreamSynchronize(st->stream));
+    const int rc = drain(st, work);
+    if (rc) return rc;
+    std::memcpy(branches, work->branches.data(), sizeof(int32_t) * work->branches.size());
+    std::memcpy(probs, work->probs.data(), sizeof(double) * work->probs.size());
+    work->branches.clear();
+    work->probs.clear();
+    return QSV_OK;
+}
+
+int qsv_ensemble_norm2(qsv_state *st, int member_qubits, double *out) {
+    if (!st || !out) return qsv_fail(QSV_EINVAL, "null pointer");
+    int rc = check_ensemble(st, member_qubits, 1);
+    if (rc) return rc;
+    rc = qsv_flush(st);
+    if (rc) return rc;
+    QSV_HIP(hipSetDevice(st->device));
+    // the diagonal pass with a zero zmask: sum |psi_i|^2 per member
+    std::vector<qsv_pauli_plan::Pass> plan(1);
+    plan[0].zmask.push_back(0);
+    plan[0].n_y.push_back(0);
+    plan[0].index.push_back(0);
+    std::vector<double> host;
+    std::vector<size_t> offsets;
+    std::vector<int> widths;
+    rc = expect_passes(st, member_qubits, plan, &host, &offsets, &widths);
+    if (rc) return rc;
+    const uint64_t members = st->amps >> member_qubits;
+    for (uint64_t m = 0; m < members; ++m) out[m] = host[m * widths[0]];
+    return QSV_OK;
+}
+
+int qsv_ensemble_expect_pauli_sum(qsv_state *st, int member_qubits, int n_terms, const int *term_offsets, const int *qubits, const char *paulis,
+                                  const double *coeffs, double *values, double *term_values) {
+    if (!st || !values) return qsv_fail(QSV_EINVAL, "null pointer");
+    if (n_terms < 0) return qsv_fail(QSV_EINVAL, "negative number of Pauli terms");
+    if (n_terms > 0 && !term_offsets) return qsv_fail(QSV_EINVAL, "null pointer");
+    int rc = check_ensemble(st, member_qubits, 1);
+    if (rc) return rc;
+    // the whole list is checked and turned into masks of member bits before anything is flushed or launched
+    const int n = member_qubits;
+    std::vector<qsv_pauli_plan::Term> terms(static_cast<size_t>(n_terms));
+    for (int t = 0; t < n_terms; ++t) {
+        const int first = term_offsets[t], len = term_offsets[t + 1] - first;
+        if (first < 0 || len < 0) return qsv_fail(QSV_EINVAL, "Pauli term offsets must start at or above 0 and never decrease");
+        if (len > 64) return qsv_fail(QSV_EINVAL, "bad Pauli string length");
+        if (len > 0 && (!qubits || !paulis)) return qsv_fail(QSV_EINVAL, "null pointer");
+        rc = check_member_qubits(n, len, len ? qubits + first : nullptr);
+        if (rc) return rc;
+        for (int j = first; j < first + len; ++j) {
+            const uint64_t bit = 1ull << (n - 1 - qubits[j]);
+            switch (paulis[j]) {
+                case 'I': case 'i': break;
+                case 'X': case 'x': terms[t].xmask |= bit; break;
+                case 'Z': case 'z': terms[t].zmask |= bit; break;
+                case 'Y': case 'y': terms[t].xmask |= bit; terms[t].zmask |= bit; break;
+                default: return qsv_fail(QSV_EINVAL, "Pauli letters must be I, X, Y or Z");
+            }
+        }
+    }
+    const uint64_t members = st->amps >> n;
+    for (uint64_t m = 0; m < members; ++m) values[m] = 0.0;
+    if (n_terms == 0) return QSV_OK;
+    rc = qsv_flush(st);
+    if (rc) return rc;
+    QSV_HIP(hipSetDevice(st->device));
+    const std::vector<qsv_pauli_plan::Pass> plan = qsv_pauli_plan::plan(terms);
+    std::vector<double> host;
+    std::vector<size_t> offsets;
+    std::vector<int> widths;
+    rc = expect_passes(st, n, plan, &host, &offsets, &widths);
+    if (rc) return rc;
+    std::vector<double> per_term(static_cast<size_t>(n_terms));
+    for (uint64_t m = 0; m < members; ++m) {
+        for (size_t k = 0; k < plan.size(); ++k) {
+            const qsv_pauli_plan::Pass &p = plan[k];
+            for (size_t t = 0; t < p.zmask.size(); ++t)
+                per_term[p.index[t]] = qsv_pauli_plan::pair_scale(p.pivot, p.n_y[t]) * host[offsets[k] + m * widths[k] + t];
+        }
+        double sum = 0.0;
+        for (int t = 0; t < n_terms; ++t) {     // in the caller's order
+            sum += (coeffs ? coeffs[t] : 1.0) * per_term[t];
+            if (term_values) term_values[m * n_terms + t] = per_term[t];
+        }
+        values[m] = sum;
+    }
+    return QSV_OK;
+}
+
+}  // extern "C"

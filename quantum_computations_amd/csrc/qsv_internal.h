@@ -116,6 +116,19 @@ struct qsv_state {
     // Kraus channels (qsv_channel.hip): the register's workspace and branch log, and how qsv_destroy frees them
     void *channel_work = nullptr;
     void (*channel_work_free)(void *) = nullptr;
+    // trajectory ensembles (qsv_ensemble.hip): workspace, draw ring and the ensemble's own branch log, freed the same way
+    void *ensemble_work = nullptr;
+    void (*ensemble_work_free)(void *) = nullptr;
+};
+
+// A Kraus channel (made by qsv_channel_create in qsv_channel.hip; read by qsv_ensemble.hip too).
+struct qsv_channel {
+    int device = 0;
+    int k = 0, D = 0, n_kraus = 0;
+    bool mixed_unitary = false;
+    std::vector<double> p;            // mixed-unitary: E_j = p_j I
+    std::vector<double> unitaries;    // mixed-unitary: K_j / sqrt(p_j) (zeros where p_j = 0), n_kraus x D x D complex
+    double *dev = nullptr;            // K_0 .. K_{n-1}, then E_0 .. E_{n-1}: D x D complex each, row-major
 };
 
 constexpr int QSV_REDUCE_BLOCKS = 1024;

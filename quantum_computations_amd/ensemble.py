@@ -1,0 +1,144 @@
+"""Trajectory ensembles: many shots of a noisy circuit in one register.
+
+``members = 2^b`` independent ``n``-qubit kets sit side by side in one ``(n + b)``-qubit :class:`DeviceState`, member ``m`` at the
+amplitudes ``[m 2^n, (m + 1) 2^n)``: the member index is the leading ``b`` qubits of the register, member qubit ``q`` is
+register qubit ``q + b``.  A unitary on member qubits is one pass over the register for all members, deferred gates included;
+what differs from member to member -- the branch a Kraus channel takes, norms, Pauli values -- goes through the
+``qsv_ensemble_*`` entry points.  Qubit indices of this class are MEMBER qubits.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .device import DeviceState, _check_terms, _flat_terms, _ints, _real_terms
+
+
+class TrajectoryEnsemble:
+    """``members`` kets of ``member_qubits`` qubits in one register (``.state``)."""
+
+    def __init__(self, state: DeviceState, member_qubits: int):
+        total = DeviceState.num_qubits.fget(state)
+        if not 0 <= int(member_qubits) <= total:
+            raise ValueError("member_qubits must lie between 0 and the register's qubits")
+        self.state = state
+        self.member_qubits = int(member_qubits)
+        self.member_bits = total - self.member_qubits
+        self.members = 1 << self.member_bits
+
+    @classmethod
+    def from_ket(cls, ket, members: int, device: int = 0) -> "TrajectoryEnsemble":
+        """Every member a copy of ``ket``; ``members`` is a power of two."""
+        ket = np.asarray(ket)
+        if ket.ndim != 1:
+            raise ValueError("State has wrong dimensions.")
+        size = ket.shape[0]
+        if size == 0 or size & (size - 1):
+            raise ValueError("Given array is not a qubit state nor operator")
+        members = int(members)
+        if members < 1 or members & (members - 1):
+            raise ValueError("the number of members must be a power of two")
+        n = size.bit_length() - 1
+        ens = cls(DeviceState.zeros(n + members.bit_length() - 1, device), n)
+        try:
+            ens.reset(ket)
+        except BaseException:
+            ens.close()
+            raise
+        return ens
+
+    def reset(self, ket) -> "TrajectoryEnsemble":
+        """Every member becomes ``ket`` again: one upload of a member and a broadcast on the device."""
+        ket = np.asarray(ket)
+        if ket.shape != (1 << self.member_qubits,):
+            raise ValueError("the ket does not have the size of a member")
+        self.state.upload(ket, 0)
+        _lib.call("qsv_ensemble_broadcast", self.state._h, self.member_qubits)
+        return self
+
+    def close(self) -> None:
+        if self.state is not None:
+            self.state.close()
+        self.state = None
+
+    # ---- circuit elements -------------------------------------------------------------------------------------------------
+    def apply(self, gate) -> "TrajectoryEnsemble":
+        """A unitary gate on member qubits goes to the register and acts on every member; a ``noise.Channel`` is one
+        trajectory step of every member."""
+        from .noise import Channel
+        if isinstance(gate, Channel):
+            return self.apply_channel(gate.channel, gate.indices, rng=gate.rng)
+        if any(not 0 <= int(q) < self.member_qubits for q in gate.indices):
+            raise ValueError(f"qubit index out of range for members of {self.member_qubits} qubits")
+        matrix = getattr(gate, "matrix", None)
+        if matrix is None or matrix.shape[0] != matrix.shape[1]:
+            raise ValueError("an ensemble takes unitary gates and channels; measurements are not supported")
+        shifted = gate.copy()
+        shifted.indices = [int(q) + self.member_bits for q in gate.indices]
+        if getattr(shifted, "sources", None):
+            shifted.sources = None            # a fused block's parts carry register indices of their own: apply its matrix
+        out = shifted.apply(self.state)
+        if isinstance(out, tuple):
+            raise ValueError("an ensemble takes unitary gates and channels; measurements are not supported")
+        return self
+
+    def apply_channel(self, channel, qubits, *, u=None, forced=None, rng=None) -> "TrajectoryEnsemble":
+        """One trajectory step per member.  ``u``: one draw in ``[0, 1)`` per member (default: ``rng.random(members)``, or
+        the global ``np.random``); ``forced``: ``None`` or one branch per member, ``-1`` = draw."""
+        qubits = [int(q) for q in qubits]
+        if len(qubits) != channel.num_qubits:
+            raise ValueError(f"the channel acts on {channel.num_qubits} qubits, got {len(qubits)}")
+        if u is None:
+            u = rng.random(self.members) if rng is not None else np.random.random(self.members)
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+        if u.shape[0] != self.members:
+            raise ValueError("one draw per member")
+        fbuf = None
+        if forced is not None:
+            fbuf = np.ascontiguousarray(forced, dtype=np.int32).reshape(-1)
+            if fbuf.shape[0] != self.members:
+                raise ValueError("one forced branch per member (-1 = draw)")
+        _lib.call("qsv_ensemble_apply_channel", self.state._h, self.member_qubits, channel.handle(self.state.device), _ints(qubits),
+                  u.ctypes.data_as(C.POINTER(C.c_double)), None if fbuf is None else fbuf.ctypes.data_as(C.POINTER(C.c_int)))
+        return self
+
+    def channel_log(self) -> tuple[np.ndarray, np.ndarray]:
+        """``(branches[steps, members], probs[steps, members])`` since the last read, in call order; clears the log."""
+        steps = C.c_uint64(0)
+        _lib.call("qsv_ensemble_log_read", self.state._h, None, None, 0, C.byref(steps))
+        branches = np.zeros((steps.value, self.members), dtype=np.int32)
+        probs = np.zeros((steps.value, self.members), dtype=np.float64)
+        if steps.value:
+            _lib.call("qsv_ensemble_log_read", self.state._h, branches.ctypes.data_as(C.POINTER(C.c_int32)),
+                      probs.ctypes.data_as(C.POINTER(C.c_double)), steps.value, C.byref(steps))
+        return branches, probs
+
+    # ---- read-out -----------------------------------------------------------------------------------------------------------
+    def norm2(self) -> np.ndarray:
+        out = np.zeros(self.members, dtype=np.float64)
+        _lib.call("qsv_ensemble_norm2", self.state._h, self.member_qubits, out.ctypes.data_as(C.POINTER(C.c_double)))
+        return out
+
+    def expect_pauli_sum(self, terms, *, return_terms: bool = False):
+        """``values[m] = sum_t c_t <psi_m|P_t|psi_m>`` for ``terms = [(c, letters, member qubits), ...]`` with real ``c``;
+        with ``return_terms`` also the ``[members, T]`` values of the single strings."""
+        terms = _real_terms(terms, "an ensemble's expect_pauli_sum")
+        _check_terms(terms, self.member_qubits)
+        count, offsets, qubits, letters, cbuf = _flat_terms(terms)
+        coeffs = np.ascontiguousarray(cbuf[0::2])
+        values = np.zeros(self.members, dtype=np.float64)
+        per_term = np.zeros((self.members, count), dtype=np.float64)
+        _lib.call("qsv_ensemble_expect_pauli_sum", self.state._h, self.member_qubits, count, offsets, qubits, letters,
+                  coeffs.ctypes.data_as(C.POINTER(C.c_double)), values.ctypes.data_as(C.POINTER(C.c_double)),
+                  per_term.ctypes.data_as(C.POINTER(C.c_double)) if return_terms else None)
+        return (values, per_term) if return_terms else values
+
+    def member(self, m: int) -> np.ndarray:
+        """Member ``m`` as a NumPy ket."""
+        m = int(m)
+        if not 0 <= m < self.members:
+            raise ValueError("no such member")
+        size = 1 << self.member_qubits
+        return self.state.download(m * size, size)

@@ -334,11 +334,65 @@ def run_density(circuit, initial_state, *, device: int = 0) -> DensityState:
     return rho
 
 
-def run_trajectories(circuit, initial_state, shots: int, *, terms=None, observable=None, seed=None, device: int = 0) -> dict:
+def _run_trajectories_batched(circuit, initial_state, shots: int, terms, seed, device: int, batch: int) -> dict:
+    """``run_trajectories(batch=...)``: chunks of ``batch`` shots, each chunk one :class:`ensemble.TrajectoryEnsemble`."""
+    from .ensemble import TrajectoryEnsemble
+    shots, batch = int(shots), int(batch)
+    if batch < 1 or batch & (batch - 1):
+        raise ValueError("batch must be a power of two")
+    circuit = list(circuit)
+    for gate in circuit:
+        if not isinstance(gate, Channel) and (getattr(gate, "matrix", None) is None or gate.matrix.shape[0] != gate.matrix.shape[1]):
+            raise ValueError("run_trajectories does not take measurements")
+    n_channels = sum(isinstance(gate, Channel) for gate in circuit)
+    # entry [s, c] is the c-th scalar the serial loop draws in shot s: the same stream, number for number
+    draws = np.random.default_rng(seed).random((shots, n_channels))
+    values = np.zeros(shots, dtype=np.float64)
+    branches = []
+    terms = list(terms)
+    ens = TrajectoryEnsemble.from_ket(np.asarray(initial_state), batch, device) if shots else None
+    try:
+        for first in range(0, shots, batch):
+            count = min(batch, shots - first)
+            if first:
+                ens.reset(np.asarray(initial_state))
+            c = 0
+            for gate in circuit:
+                if isinstance(gate, Channel):
+                    u = np.zeros(batch, dtype=np.float64)          # surplus members of the last chunk: u = 0, discarded below
+                    u[:count] = draws[first:first + count, c]
+                    ens.apply_channel(gate.channel, gate.indices, u=u)
+                    c += 1
+                else:
+                    ens.apply(gate)
+            values[first:first + count] = ens.expect_pauli_sum(terms)[:count]
+            logged = ens.channel_log()[0]
+            branches += [np.ascontiguousarray(logged[:, m]) for m in range(count)]
+    finally:
+        if ens is not None:
+            ens.close()
+    mean = float(values.mean()) if shots else 0.0
+    stderr = float(values.std(ddof=1) / np.sqrt(shots)) if shots > 1 else 0.0
+    return {"mean": mean, "stderr": stderr, "values": values, "branches": branches}
+
+
+def run_trajectories(circuit, initial_state, shots: int, *, terms=None, observable=None, seed=None, device: int = 0,
+                     batch: int | None = None) -> dict:
     """``shots`` quantum trajectories of ``circuit`` from the ket ``initial_state``; the value of a shot is
     ``<psi|H|psi>`` for the Pauli sum ``terms``, or ``observable(register)``.  Every shot runs on a fresh copy of one
     uploaded register; all draws come from ``np.random.default_rng(seed)`` in call order.  Returns ``mean``, ``stderr``,
-    ``values`` and the ``branches`` each shot logged."""
+    ``values`` and the ``branches`` each shot logged.
+
+    ``batch=B`` (a power of two) runs the shots ``B`` at a time as the members of one register
+    (:class:`~quantum_computations_amd.ensemble.TrajectoryEnsemble`): one pass per gate for all of them.  The draws are
+    the serial loop's, so a seeded batched run takes the serial run's branches.  It needs ``terms`` with real
+    coefficients; ``observable`` sees one register and is refused."""
+    if batch is not None:
+        if observable is not None:
+            raise ValueError("observable= sees one register: a batched run takes terms")
+        if terms is None:
+            raise ValueError("give terms or observable")
+        return _run_trajectories_batched(circuit, initial_state, shots, terms, seed, device, batch)
     if (terms is None) == (observable is None):
         raise ValueError("give terms or observable")
     rng = np.random.default_rng(seed)

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""TEST INFRASTRUCTURE: build the AddressSanitizer + UBSan host-side binary of libqsv.
+"""TEST INFRASTRUCTURE: build the AddressSanitizer + UBSan host-side binaries of libqsv.
 
-    python tests/sanitize/build.py            # -> tests/sanitize/_build/qsv_host_san
+    python tests/sanitize/build.py [driver ...]     # -> tests/sanitize/_build/<driver>, all drivers when none is named
 
-Every HIP source of the library is compiled with ``clang++ -x hip --offload-host-only`` (host code only: the kernels'
-bodies are not compiled at all) and ``-fsanitize=address,undefined -fno-sanitize-recover=all``, then linked with
-``hip_stub.cpp`` (a host-memory stand-in for the HIP runtime) and ``driver.cpp``.  No GPU and no libamdhip64 involved;
-GPU sanitizers are not available on this pool.
+Every HIP source of the library (the list is ``quantum_computations_amd.build.SOURCES`` itself) is compiled once with
+``clang++ -x hip --offload-host-only`` (host code only: the kernels' bodies are not compiled at all) and
+``-fsanitize=address,undefined -fno-sanitize-recover=all``.  That one set of objects, with ``hip_stub.cpp`` (a host-memory
+stand-in for the HIP runtime), is linked with each ``<driver>.cpp`` of this directory into a stand-alone program with its
+own ``main``.  No GPU and no libamdhip64 involved, nothing is loaded into Python; GPU sanitizers are not available on this
+pool.
 """
 from __future__ import annotations
 
@@ -17,54 +19,61 @@ from pathlib import Path
 
 HERE = Path(__file__).resolve().parent
 REPO = HERE.parent.parent
-CSRC = REPO / "quantum_computations_amd" / "csrc"
+if str(REPO) not in sys.path:
+    sys.path.insert(0, str(REPO))
+
+from quantum_computations_amd.build import CSRC, HEADERS, SOURCES  # noqa: E402  (touches neither the GPU nor libqsv.so)
+
 OUT = HERE / "_build"
 CLANG = Path("/opt/rocm/lib/llvm/bin/clang++")
-SOURCES = ["qsv_api.hip", "qsv_kernels.hip", "qsv_readout.hip", "qsv_pauli.hip", "qsv_qudit.hip", "qsv_gemm.hip", "qsv_decomp.hip",
-           "qsv_circuit.hip"]
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g", "-O1"]
 INC = [f"-I{REPO / 'include'}", f"-I{CSRC}"]
+DRIVERS = sorted(p.stem for p in HERE.glob("*driver.cpp"))
 
 
 def stale(target: Path, deps: list[Path]) -> bool:
     return not target.exists() or any(d.stat().st_mtime > target.stat().st_mtime for d in deps)
 
 
-def build(verbose: bool = False) -> Path:
+def build(driver: str = "driver", verbose: bool = False) -> Path:
     if not CLANG.exists():
         raise RuntimeError(f"{CLANG} not found: the sanitized host build needs the ROCm clang")
     OUT.mkdir(exist_ok=True)
-    headers = [CSRC / "qsv_internal.h", CSRC / "qsv_device.h", CSRC / "qsv_linalg.h", CSRC / "qsv_plan.h", CSRC / "qsv_layout.h",
-               CSRC / "qsv_readout_layout.h", REPO / "include" / "qsv.h"]
-    objs = []
 
     def run(cmd):
         if verbose:
             print(" ".join(map(str, cmd)), flush=True)
         subprocess.run(cmd, check=True)
 
+    def compile_host(name: str) -> Path:
+        obj = OUT / (name + ".o")
+        if stale(obj, [HERE / name, HERE / "driver_common.h"] + HEADERS):
+            run([CLANG, "-std=c++17", *SAN, *INC, "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-c", HERE / name, "-o", obj])
+        return obj
+
+    objs = []
     for name in SOURCES:
         obj = OUT / (name + ".o")
-        if stale(obj, [CSRC / name] + headers):
+        if stale(obj, [CSRC / name] + HEADERS):
             run([CLANG, "-x", "hip", "--offload-host-only", "--rocm-path=/opt/rocm", "-nogpulib", "-std=c++17", *SAN, *INC,
                  "-c", CSRC / name, "-o", obj])
         objs.append(obj)
-    for name in ("hip_stub.cpp", "driver.cpp"):
-        obj = OUT / (name + ".o")
-        if stale(obj, [HERE / name] + headers):
-            run([CLANG, "-std=c++17", *SAN, *INC, "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-c", HERE / name, "-o", obj])
-        objs.append(obj)
+    objs.append(compile_host("hip_stub.cpp"))
     # the host stubs reference the embedded device image of each translation unit; there is none in a host-only build
     fat = OUT / "fatbins.c"
     names = set()
     for obj in objs:
         names |= set(re.findall(r"U (__hip_fatbin_\w+)", subprocess.run(["nm", str(obj)], capture_output=True, text=True).stdout))
-    fat.write_text("".join(f"const char {n}[8] = {{0}};\n" for n in sorted(names)))
-    exe = OUT / "qsv_host_san"
+    text = "".join(f"const char {n}[8] = {{0}};\n" for n in sorted(names))
+    if not fat.exists() or fat.read_text() != text:
+        fat.write_text(text)
+    objs.append(compile_host(driver + ".cpp"))
+    exe = OUT / driver
     if stale(exe, objs + [fat]):
         run([CLANG, *SAN, "-x", "c", fat, "-x", "none", *objs, "-ldl", "-lpthread", "-o", exe])
     return exe
 
 
 if __name__ == "__main__":
-    print(build(verbose=True))
+    for name in sys.argv[1:] or DRIVERS:
+        print(build(name, verbose=True))

@@ -1,10 +1,15 @@
 // TEST INFRASTRUCTURE: drives the host side of the noise entry points (qsv_channel_*, qsv_apply_channel,
-// qsv_channel_log_read, qsv_density_expect_paulis) -- every refusal (a channel on another device too: stub_devices), the
+// qsv_channel_log_read, qsv_density_expect_paulis) -- every refusal (a channel on another device too: qsv_stub_devices), the
 // host-side branch pick of mixed-unitary channels, the launch shapes of the kernel path for 1 to 18 qubits and the branch
 // log -- under ASan + UBSan against hip_stub.cpp
 // (device memory is zeroed host memory and kernels do not run, so a branch "chosen on the device" reads back as (0, 0.0)).
 // Launches are counted: a mixed-unitary call on a deferring register adds none at call time, a general call adds the same
 // fixed number whatever the number of Kraus operators.
+// Walks: null pointers, bad sizes and devices, draws outside [0, 1), forced branches out of range, qubits repeated or out of
+// range, mode registers, a channel on another device, density registers with an odd number of qubits, bad term lists -- each
+// refused before any launch and with the deferred queue left as it was -- and then valid calls for 1 to 18 qubits on every
+// target bit, with and without the streaming forms and the grid cap.  A log of 900 entries, 600 of them in device slots, is
+// read back complete and in call order.
 // Exit code 0 = every expectation held and no sanitizer report (reports abort: -fno-sanitize-recover).
 #include <cmath>
 #include <cstdio>
@@ -12,42 +17,10 @@
 #include <limits>
 #include <vector>
 
-#include "qsv.h"
-
-extern "C" unsigned long qsv_stub_launches;
-
-// The library's calls of these two go through here (linked with --wrap, build_channel.py): hip_stub.cpp has one device,
-// and the refusal of a channel on another device needs a register on a second one.
-static int stub_devices = 1;
-extern "C" int __wrap_hipGetDeviceCount(int *n) { *n = stub_devices; return 0; }
-extern "C" int __wrap_hipSetDevice(int d) { return d >= 0 && d < stub_devices ? 0 : 101 /* hipErrorInvalidDevice */; }
-
-static int failures = 0;
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: expectation failed: %s (last error: %s)\n", __FILE__, __LINE__, #cond, qsv_last_error()); \
-            ++failures;                                                           \
-        }                                                                         \
-    } while (0)
+#include "driver_common.h"
 
 constexpr int GENERAL_LAUNCHES = 4;     // read pass, sum of the partials, select, update pass
 
-// exactly as many doubles as the call may read
-static std::vector<double> amplitude_damping(double gamma) {
-    return {1, 0, 0, 0, 0, 0, std::sqrt(1 - gamma), 0, /* K1 */ 0, 0, std::sqrt(gamma), 0, 0, 0, 0, 0};
-}
-static std::vector<double> bit_flip(double p) {
-    return {std::sqrt(1 - p), 0, 0, 0, 0, 0, std::sqrt(1 - p), 0, /* K1 */ 0, 0, std::sqrt(p), 0, std::sqrt(p), 0, 0, 0};
-}
-// `count` operators on k qubits, each a multiple of a diagonal matrix that is not a multiple of the identity
-static std::vector<double> general(int k, int count) {
-    const int D = 1 << k;
-    std::vector<double> out(static_cast<size_t>(2) * D * D * count, 0.0);
-    for (int j = 0; j < count; ++j)
-        for (int r = 0; r < D; ++r) out[2 * (static_cast<size_t>(D) * D * j + r * D + r)] = std::sqrt((1.0 + r) / ((1.0 + D) * count));
-    return out;
-}
 // 16 two-qubit Paulis, equal weights: mixed-unitary (only X and Z letters, so every entry is real)
 static std::vector<double> flat_two_qubit(int count) {
     std::vector<double> out(static_cast<size_t>(2) * 16 * count, 0.0);
@@ -67,15 +40,6 @@ static qsv_channel *make(int k, int count, const std::vector<double> &kraus, int
     EXPECT(qsv_channel_info(c, &kk, &nn, &mixed) == QSV_OK && kk == k && nn == count && mixed == want_mixed);
     EXPECT(qsv_channel_info(c, nullptr, nullptr, nullptr) == QSV_OK);
     return c;
-}
-
-struct Stats {
-    uint64_t queued = 0, launched = 0;
-};
-static Stats stats_of(qsv_state *st) {
-    Stats s;
-    EXPECT(qsv_defer_stats(st, &s.queued, &s.launched) == QSV_OK);
-    return s;
 }
 
 // every refusal of qsv_apply_channel on a register of n qubits; nothing may be launched and the queue stays as it was
@@ -318,7 +282,7 @@ int main() {
 
     // ---- a channel on another device ----------------------------------------------------------------------------------------------------
     {
-        stub_devices = 2;
+        qsv_stub_devices = 2;
         qsv_state *far = nullptr, *near = nullptr;
         qsv_channel *far_channel = nullptr;
         const double h[8] = {0.5, 0, 0.5, 0, 0.5, 0, -0.5, 0};
@@ -335,11 +299,10 @@ int main() {
         EXPECT(qsv_channel_log_read(far, nullptr, nullptr, 0, &count) == QSV_OK && count == 0);
         EXPECT(qsv_apply_channel(far, far_channel, &q, 0.5, -1) == QSV_OK && qsv_apply_channel(near, one, &q, 0.5, -1) == QSV_OK);
         EXPECT(qsv_destroy(far) == QSV_OK && qsv_destroy(near) == QSV_OK && qsv_channel_destroy(far_channel) == QSV_OK);
-        stub_devices = 1;
+        qsv_stub_devices = 1;
     }
 
     for (qsv_channel *c : {one, one16, two, two16, mixed, mixed16, single}) EXPECT(qsv_channel_destroy(c) == QSV_OK);
     EXPECT(qsv_destroy(modes) == QSV_OK);
-    std::printf("sanitized channel driver: %lu kernel launches prepared, %d failed expectations\n", qsv_stub_launches, failures);
-    return failures ? 1 : 0;
+    return finish("channel");
 }

@@ -3,6 +3,11 @@
 // download, the scratch slices and the launch of every pass -- under ASan + UBSan against hip_stub.cpp (device memory is
 // zeroed host memory and kernels do not run).  Launches are counted: one per build whatever the number of terms, one per
 // register x diagonal pass.
+// Walks: null handles, bad sizes and devices, options other than the grid cap, windows of upload and download out of
+// bounds, X / Y letters, qubits out of range or repeated, 65 letters, registers and diagonals of different sizes, a
+// destination that is too small or meets its source, mode registers -- each refused before any launch and with every
+// deferred queue left alone -- and then valid calls for 0 to 18 qubits with 0, 1, 2, 63, 64, 65 and 200 terms, windows at
+// both ends and `accumulate`.
 // Exit code 0 = every expectation held and no sanitizer report (reports abort: -fno-sanitize-recover).
 #include <cmath>
 #include <cstdio>
@@ -10,18 +15,7 @@
 #include <string>
 #include <vector>
 
-#include "qsv.h"
-
-extern "C" unsigned long qsv_stub_launches;
-
-static int failures = 0;
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: expectation failed: %s (last error: %s)\n", __FILE__, __LINE__, #cond, qsv_last_error()); \
-            ++failures;                                                           \
-        }                                                                         \
-    } while (0)
+#include "driver_common.h"
 
 // exactly as many entries as the call may read: a read past the caller's arrays is an ASan report
 struct Terms {
@@ -304,6 +298,5 @@ int main() {
         for (qsv_state *st : {low, mid, high, owned, modes}) EXPECT(qsv_destroy(st) == QSV_OK);
         EXPECT(qsv_diag_destroy(d) == QSV_OK);
     }
-    std::printf("sanitized diagonal driver: %lu kernel launches prepared, %d failed expectations\n", qsv_stub_launches, failures);
-    return failures ? 1 : 0;
+    return finish("diagonal");
 }

@@ -5,6 +5,11 @@
 // is zeroed host memory and kernels do not run, so every branch "chosen on the device" reads back as (0, 0.0)).
 // Launches are counted: a general call adds the same three (read pass, select, update pass) whatever the number of Kraus
 // operators and of members, a mixed-unitary call has no read pass.
+// Walks: null pointers, a member size outside k .. n_total, target and term qubits outside a member or repeated, a draw
+// outside [0, 1) or a forced branch out of range in any member, mode registers, views, a channel on another device -- each
+// refused before any launch and with the deferred queue left as it was.  A log of 300 steps, more than its device slots, is
+// read back complete; what it holds is the stand-in's zeroed memory, its order is checked on the device
+// (tests/test_gpu_ensemble.py).
 // Exit code 0 = every expectation held and no sanitizer report (reports abort: -fno-sanitize-recover).
 #include <cmath>
 #include <cstdio>
@@ -13,43 +18,11 @@
 #include <limits>
 #include <vector>
 
-#include "qsv.h"
-
-extern "C" unsigned long qsv_stub_launches;
-
-// The library's calls of these two go through here (linked with --wrap, build_ensemble.py): hip_stub.cpp has one device,
-// and the refusal of a channel on another device needs a register on a second one.
-static int stub_devices = 1;
-extern "C" int __wrap_hipGetDeviceCount(int *n) { *n = stub_devices; return 0; }
-extern "C" int __wrap_hipSetDevice(int d) { return d >= 0 && d < stub_devices ? 0 : 101 /* hipErrorInvalidDevice */; }
-
-static int failures = 0;
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: expectation failed: %s (last error: %s)\n", __FILE__, __LINE__, #cond, qsv_last_error()); \
-            ++failures;                                                           \
-        }                                                                         \
-    } while (0)
+#include "driver_common.h"
 
 constexpr int GENERAL_LAUNCHES = 3;     // read pass, select, update pass
 constexpr int MIXED_LAUNCHES = 2;       // select, update pass
 constexpr int PASS_LAUNCHES = 2;        // a Pauli pass and the per-member sum of its parts
-
-static std::vector<double> amplitude_damping(double gamma) {
-    return {1, 0, 0, 0, 0, 0, std::sqrt(1 - gamma), 0, /* K1 */ 0, 0, std::sqrt(gamma), 0, 0, 0, 0, 0};
-}
-static std::vector<double> bit_flip(double p) {
-    return {std::sqrt(1 - p), 0, 0, 0, 0, 0, std::sqrt(1 - p), 0, /* K1 */ 0, 0, std::sqrt(p), 0, std::sqrt(p), 0, 0, 0};
-}
-// `count` operators on k qubits, each a multiple of a diagonal matrix that is not a multiple of the identity
-static std::vector<double> general(int k, int count) {
-    const int D = 1 << k;
-    std::vector<double> out(static_cast<size_t>(2) * D * D * count, 0.0);
-    for (int j = 0; j < count; ++j)
-        for (int r = 0; r < D; ++r) out[2 * (static_cast<size_t>(D) * D * j + r * D + r)] = std::sqrt((1.0 + r) / ((1.0 + D) * count));
-    return out;
-}
 
 static qsv_channel *make(int k, int count, const std::vector<double> &kraus, int want_mixed) {
     qsv_channel *c = nullptr;
@@ -57,15 +30,6 @@ static qsv_channel *make(int k, int count, const std::vector<double> &kraus, int
     EXPECT(qsv_channel_create(k, count, kraus.data(), 0, &c) == QSV_OK && c != nullptr);
     EXPECT(qsv_channel_info(c, nullptr, nullptr, &mixed) == QSV_OK && mixed == want_mixed);
     return c;
-}
-
-struct Stats {
-    uint64_t queued = 0, launched = 0;
-};
-static Stats stats_of(qsv_state *st) {
-    Stats s;
-    EXPECT(qsv_defer_stats(st, &s.queued, &s.launched) == QSV_OK);
-    return s;
 }
 
 // every refusal on a register of n + b qubits read as 2^b members of n >= 2 qubits; nothing may be launched, logged or flushed
@@ -298,7 +262,7 @@ int main() {
 
     // ---- a channel on another device ---------------------------------------------------------------------------------------------------
     {
-        stub_devices = 2;
+        qsv_stub_devices = 2;
         qsv_state *far = nullptr, *near = nullptr;
         qsv_channel *far_channel = nullptr;
         EXPECT(qsv_create(8, 1, &far) == QSV_OK && qsv_create(8, 0, &near) == QSV_OK);
@@ -313,12 +277,11 @@ int main() {
         EXPECT(qsv_ensemble_log_read(far, nullptr, nullptr, 0, &steps) == QSV_OK && steps == 0);
         EXPECT(qsv_ensemble_apply_channel(far, 6, far_channel, &q, u.data(), nullptr) == QSV_OK && qsv_ensemble_apply_channel(near, 6, one, &q, u.data(), nullptr) == QSV_OK);
         EXPECT(qsv_destroy(far) == QSV_OK && qsv_destroy(near) == QSV_OK && qsv_channel_destroy(far_channel) == QSV_OK);
-        stub_devices = 1;
+        qsv_stub_devices = 1;
     }
 
     for (qsv_channel *c : {one, one16, two, two16, mixed}) EXPECT(qsv_channel_destroy(c) == QSV_OK);
     EXPECT(qsv_destroy(modes) == QSV_OK && qsv_destroy(view) == QSV_OK);
     std::free(view_memory);
-    std::printf("sanitized ensemble driver: %lu kernel launches prepared, %d failed expectations\n", qsv_stub_launches, failures);
-    return failures ? 1 : 0;
+    return finish("ensemble");
 }

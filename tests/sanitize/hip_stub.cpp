@@ -14,11 +14,12 @@
 
 extern "C" unsigned long qsv_stub_launches = 0;
 extern "C" unsigned long qsv_stub_bytes_copied = 0;
+extern "C" int qsv_stub_devices = 1;  // a driver sets 2 to put a register on a second device and walk the "other device" refusals
 
 extern "C" {
 
-hipError_t hipGetDeviceCount(int *n) { *n = 1; return hipSuccess; }
-hipError_t hipSetDevice(int d) { return d == 0 ? hipSuccess : hipErrorInvalidDevice; }
+hipError_t hipGetDeviceCount(int *n) { *n = qsv_stub_devices; return hipSuccess; }
+hipError_t hipSetDevice(int d) { return d >= 0 && d < qsv_stub_devices ? hipSuccess : hipErrorInvalidDevice; }
 hipError_t hipDeviceSynchronize() { return hipSuccess; }
 hipError_t hipDeviceGetAttribute(int *v, hipDeviceAttribute_t, int) { *v = 256; return hipSuccess; }
 hipError_t hipFuncSetAttribute(const void *, hipFuncAttribute, int) { return hipSuccess; }

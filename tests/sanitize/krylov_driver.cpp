@@ -2,24 +2,17 @@
 // the argument builders, the slices of the scratch buffer and the launch of every pass -- under ASan + UBSan against
 // hip_stub.cpp (device memory is zeroed host memory and kernels do not run).  The number of launches of every valid call
 // is compared with ceil(operands / 8).
+// Walks: null handles and arrays, a null entry inside an array, negative counts, the destination among the sources, views
+// whose windows meet the destination's, registers of different sizes, a destination that is too small, mode registers --
+// each refused before any launch and with every deferred queue left alone -- and then valid calls with 0 to 40 operands on
+// registers of 1 to 18 qubits and on views (repeated and overlapping sources, x_k = y), with and without beta and the norm.
 // Exit code 0 = every expectation held and no sanitizer report (reports abort: -fno-sanitize-recover).
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
-#include "qsv.h"
-
-extern "C" unsigned long qsv_stub_launches;
-
-static int failures = 0;
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: expectation failed: %s (last error: %s)\n", __FILE__, __LINE__, #cond, qsv_last_error()); \
-            ++failures;                                                           \
-        }                                                                         \
-    } while (0)
+#include "driver_common.h"
 
 static uint64_t passes_of(int operands) { return static_cast<uint64_t>((operands + 7) / 8); }
 
@@ -174,6 +167,5 @@ int main() {
         expect_valid(owned, {low, mid, high});
         for (qsv_state *st : {low, mid, high, owned, modes}) EXPECT(qsv_destroy(st) == QSV_OK);
     }
-    std::printf("sanitized Krylov driver: %lu kernel launches prepared, %d failed expectations\n", qsv_stub_launches, failures);
-    return failures ? 1 : 0;
+    return finish("Krylov");
 }

@@ -2,24 +2,16 @@
 // branch, the parsing of the flattened term list, the greedy planner and the launch of every pass -- under ASan + UBSan
 // against hip_stub.cpp (device memory is zeroed host memory and kernels do not run).  The number of launches of every
 // valid call is compared with a model of the greedy rule written here on the letters themselves.
+// Walks: null pointers, a negative count, decreasing offsets, a term of 65 letters, repeated and out-of-range qubits, a bad
+// letter, a mode register -- each refused before any launch and with the deferred queue left alone -- and then valid lists
+// on registers of 1 to 18 qubits and on a view.
 // Exit code 0 = every expectation held and no sanitizer report (reports abort: -fno-sanitize-recover).
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include "qsv.h"
-
-extern "C" unsigned long qsv_stub_launches;
-
-static int failures = 0;
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: expectation failed: %s (last error: %s)\n", __FILE__, __LINE__, #cond, qsv_last_error()); \
-            ++failures;                                                           \
-        }                                                                         \
-    } while (0)
+#include "driver_common.h"
 
 struct Terms {
     std::vector<int> offsets = {0}, qubits;
@@ -207,6 +199,5 @@ int main() {
         EXPECT(qsv_apply_pauli_rotation(st, 1, &q, "Z", 0.1) == QSV_ESTATE);
         EXPECT(qsv_destroy(st) == QSV_OK);
     }
-    std::printf("sanitized Pauli-rotation driver: %lu kernel launches prepared, %d failed expectations\n", qsv_stub_launches, failures);
-    return failures ? 1 : 0;
+    return finish("Pauli-rotation");
 }

@@ -1,24 +1,16 @@
 // TEST INFRASTRUCTURE: drives the host side of qsv_expect_pauli_sum -- every validation branch, the parsing of the
 // flattened term list, the planner and the launch / partial-sum bookkeeping of every pass -- under ASan + UBSan against
 // hip_stub.cpp (device memory is zeroed host memory and kernels do not run: every expectation value comes back 0).
+// Walks: null pointers, a negative count, decreasing offsets, a term of 65 letters, repeated and out-of-range qubits, a bad
+// letter -- each refused before any launch -- and then valid lists on registers of 1 to 18 qubits, on a view and on a mode
+// register: parsing, planning, one launch per planned pass, the copy of the partials and their sums.
 // Exit code 0 = every expectation held and no sanitizer report (reports abort: -fno-sanitize-recover).
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include "qsv.h"
-
-extern "C" unsigned long qsv_stub_launches;
-
-static int failures = 0;
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: expectation failed: %s (last error: %s)\n", __FILE__, __LINE__, #cond, qsv_last_error()); \
-            ++failures;                                                           \
-        }                                                                         \
-    } while (0)
+#include "driver_common.h"
 
 struct Terms {
     std::vector<int> offsets = {0}, qubits;
@@ -133,6 +125,5 @@ int main() {
         EXPECT(run(st, t, nullptr, values, &re, &im, &passes) == QSV_ESTATE);
         EXPECT(qsv_destroy(st) == QSV_OK);
     }
-    std::printf("sanitized Pauli-sum driver: %lu kernel launches prepared, %d failed expectations\n", qsv_stub_launches, failures);
-    return failures ? 1 : 0;
+    return finish("Pauli-sum");
 }

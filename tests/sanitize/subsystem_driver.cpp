@@ -1,41 +1,18 @@
 // TEST INFRASTRUCTURE: drives the host side of the subsystem read-out (qsv_reduced_density_state,
-// qsv_marginal_probabilities) -- every refusal (a density register on another device too: stub_devices), then valid calls
+// qsv_marginal_probabilities) -- every refusal (a density register on another device too: qsv_stub_devices), then valid calls
 // for 1 to 18 qubits on several placements, with and without a grid cap and with a deferred queue pending -- under
 // ASan + UBSan against hip_stub.cpp (device memory is zeroed host memory and kernels do not run, so a marginal reads back
 // as zeros).  Launches are counted: the matrix-core form is two launches (k_subsys_tile, k_subsys_finish), the per-entry
 // form one; the streaming marginal two (k_marginal_stream, k_sum_partials), the per-entry marginal one.
+// Walks: null pointers, k = 0, k = 13, k > n, a marginal of 27 qubits, qubits repeated or out of range, a density register
+// of the wrong size, on another device, equal to the ket or a view, mode registers -- each refused before any launch and
+// with the deferred queue left as it was -- and then a call that finds gates queued on both registers.
 // Exit code 0 = every expectation held and no sanitizer report (reports abort: -fno-sanitize-recover).
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
-#include "qsv.h"
-
-extern "C" unsigned long qsv_stub_launches;
-
-// The library's calls of these two go through here (linked with --wrap, build_subsystem.py): hip_stub.cpp has one device,
-// and the refusal of a density register on another device needs a register on a second one.
-static int stub_devices = 1;
-extern "C" int __wrap_hipGetDeviceCount(int *n) { *n = stub_devices; return 0; }
-extern "C" int __wrap_hipSetDevice(int d) { return d >= 0 && d < stub_devices ? 0 : 101 /* hipErrorInvalidDevice */; }
-
-static int failures = 0;
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: expectation failed: %s (last error: %s)\n", __FILE__, __LINE__, #cond, qsv_last_error()); \
-            ++failures;                                                           \
-        }                                                                         \
-    } while (0)
-
-struct Stats {
-    uint64_t queued = 0, launched = 0;
-};
-static Stats stats_of(qsv_state *st) {
-    Stats s;
-    EXPECT(qsv_defer_stats(st, &s.queued, &s.launched) == QSV_OK);
-    return s;
-}
+#include "driver_common.h"
 
 static bool last_kernel_is(qsv_state *st, const char *want) {
     char name[96] = "";
@@ -50,7 +27,7 @@ static void refusals(int n) {
     void *ptr = nullptr;
     EXPECT(qsv_device_ptr(owner, &ptr) == QSV_OK && ptr != nullptr);
     EXPECT(qsv_create_view(4, 0, ptr, 16, nullptr, &view) == QSV_OK);
-    stub_devices = 2;
+    qsv_stub_devices = 2;
     EXPECT(qsv_create(4, 1, &far) == QSV_OK);
     if (n >= 22) {                                       // something pending, so that a refusal that flushed would show
         const double h[8] = {0.7071067811865476, 0, 0.7071067811865476, 0, 0.7071067811865476, 0, -0.7071067811865476, 0};
@@ -97,7 +74,7 @@ static void refusals(int n) {
     EXPECT(now.queued == was.queued && now.launched == was.launched);
     EXPECT(qsv_stub_launches == before && out[0] == 7.0 && out[3] == 7.0);
     for (qsv_state *st : {ket, rho, modes, small, view, owner, far}) EXPECT(qsv_destroy(st) == QSV_OK);
-    stub_devices = 1;
+    qsv_stub_devices = 1;
 }
 
 // kept qubits of placement p (0 = the lowest bits, 1 = the top bits reversed, 2 = from bit 6 up, or rotated where they do not fit)
@@ -174,6 +151,5 @@ int main() {
     for (int n = 1; n <= 18; ++n) valid_calls(n, 0);
     valid_calls(16, 2);
     flushes_both_queues();
-    std::printf("sanitized subsystem driver: %lu launches, %d failed expectations\n", qsv_stub_launches, failures);
-    return failures ? 1 : 0;
+    return finish("subsystem");
 }

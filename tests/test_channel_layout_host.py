@@ -9,31 +9,21 @@ caps.  Also the slots of the reduced density matrix and the branch rule against 
 """
 from __future__ import annotations
 
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import hostcheck
 import noise_reference as R
-import test_defer_plan_host as base
 
 BLOCK, REDUCE_BLOCKS, MAX_BLOCKS, LANE_BITS, MIN_STREAM = 256, 1024, (1 << 24) - 1, 6, 14
 
 
 @pytest.fixture(scope="module")
 def ask(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("channel_layout") / "channel_layout_driver"
-    subprocess.run([base.compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-fno-omit-frame-pointer", f"-I{base.CSRC}", str(base.HERE / "layout" / "channel_layout_driver.cpp"), "-o", str(exe)],
-                   check=True)
+    exe = hostcheck.compile_driver(hostcheck.HERE / "layout" / "channel_layout_driver.cpp", tmp_path_factory.mktemp("channel_layout"))
 
     def run(requests, number=int):
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-        proc = subprocess.run([str(exe)], input="\n".join(requests) + "\n", capture_output=True, text=True, env=env, timeout=600)
-        assert proc.returncode == 0 and "runtime error" not in proc.stderr and "Sanitizer" not in proc.stderr, proc.stderr[-4000:]
-        lines = proc.stdout.split("\n")[:-1]
-        assert len(lines) == len(requests)
+        lines = hostcheck.ask(exe, requests, timeout=600)
         return [[[number(x) for x in part.split()] for part in line.split("|")] for line in lines]
     return run
 

@@ -9,13 +9,11 @@ gates applied one by one EXACTLY.
 """
 from __future__ import annotations
 
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-import test_defer_plan_host as base
+import defer_plan_model as base
+import hostcheck
 from quantum_computations_amd import workloads as W
 
 REG_BITS, TILE_BITS = 4, 12
@@ -23,22 +21,14 @@ REG_BITS, TILE_BITS = 4, 12
 
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
-    out = {}
-    for name in ("plan_driver", "groups_driver"):
-        exe = tmp_path_factory.mktemp(name) / name
-        subprocess.run([base.compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", f"-I{base.CSRC}",
-                        str(base.HERE / "defer_plan" / f"{name}.cpp"), "-o", str(exe)], check=True)
-        out[name] = exe
-    return out
+    return {name: hostcheck.compile_driver(hostcheck.HERE / "defer_plan" / f"{name}.cpp", tmp_path_factory.mktemp(name))
+            for name in ("plan_driver", "groups_driver")}
 
 
 def cut(driver, passes):
     """passes: [[need mask per gate]] -> per pass, [(first, count, (reg0..reg3))]."""
     text = "".join(f"{len(p)} " + " ".join(str(m) for m in p) + "\n" for p in passes)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    proc = subprocess.run([str(driver)], input=text, capture_output=True, text=True, env=env, timeout=600)
-    assert proc.returncode == 0 and "runtime error" not in proc.stderr and "Sanitizer" not in proc.stderr, proc.stderr[-4000:]
+    proc = hostcheck.run_clean(driver, text, timeout=600)
     cuts, lines = [], iter(proc.stdout.split("\n"))
     for line in lines:
         if not line.startswith("groups "):

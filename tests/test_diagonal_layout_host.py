@@ -10,14 +10,11 @@ combination of the partials, ties of the extrema included.
 """
 from __future__ import annotations
 
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import diagonal_reference as R
-import test_defer_plan_host as base
+import hostcheck
 
 BLOCK, REDUCE_BLOCKS, MAX_BLOCKS = 256, 1024, (1 << 24) - 1
 PACK_OK, PACK_NULL, PACK_OFFSETS, PACK_LENGTH, PACK_RANGE, PACK_REPEAT, PACK_LETTER = range(7)
@@ -26,17 +23,10 @@ SLOTS = {"expect": 4, "transition": 2, "phase_adjoint": 2, "extrema": 4}
 
 @pytest.fixture(scope="module")
 def ask(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("diagonal_layout") / "diagonal_layout_driver"
-    subprocess.run([base.compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-fno-omit-frame-pointer", f"-I{base.CSRC}", str(base.HERE / "layout" / "diagonal_layout_driver.cpp"), "-o", str(exe)],
-                   check=True)
+    exe = hostcheck.compile_driver(hostcheck.HERE / "layout" / "diagonal_layout_driver.cpp", tmp_path_factory.mktemp("diagonal_layout"))
 
     def run(requests):
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-        proc = subprocess.run([str(exe)], input="\n".join(requests) + "\n", capture_output=True, text=True, env=env, timeout=600)
-        assert proc.returncode == 0 and "runtime error" not in proc.stderr and "Sanitizer" not in proc.stderr, proc.stderr[-4000:]
-        lines = proc.stdout.split("\n")[:-1]
-        assert len(lines) == len(requests)
+        lines = hostcheck.ask(exe, requests, timeout=600)
         return [[part.split() for part in line.split("|")] for line in lines]
     return run
 

@@ -9,30 +9,20 @@ of the scratch buffer per pass and slot, and the host sums.
 """
 from __future__ import annotations
 
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-import test_defer_plan_host as base
+import hostcheck
 
 BLOCK, REDUCE_BLOCKS, MAX_BLOCKS, PER_PASS = 256, 1024, (1 << 24) - 1, 8
 
 
 @pytest.fixture(scope="module")
 def ask(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("krylov_layout") / "krylov_layout_driver"
-    subprocess.run([base.compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-fno-omit-frame-pointer", f"-I{base.CSRC}", str(base.HERE / "layout" / "krylov_layout_driver.cpp"), "-o", str(exe)],
-                   check=True)
+    exe = hostcheck.compile_driver(hostcheck.HERE / "layout" / "krylov_layout_driver.cpp", tmp_path_factory.mktemp("krylov_layout"))
 
     def run(requests):
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-        proc = subprocess.run([str(exe)], input="\n".join(requests) + "\n", capture_output=True, text=True, env=env, timeout=600)
-        assert proc.returncode == 0 and "runtime error" not in proc.stderr and "Sanitizer" not in proc.stderr, proc.stderr[-4000:]
-        lines = proc.stdout.split("\n")[:-1]
-        assert len(lines) == len(requests)
+        lines = hostcheck.ask(exe, requests, timeout=600)
         return [[part.split() for part in line.split("|")] for line in lines]
     return run
 

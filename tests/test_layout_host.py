@@ -10,13 +10,14 @@ for bit against the gates applied one by one) and the choice of kernel form.
 from __future__ import annotations
 
 import itertools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import test_defer_plan_host as base
+import defer_plan_model as base
+import hostcheck
+from defer_plan_model import interleaved, op_line, random_pass_list
+from hostcheck import floats, nums, text
 from oracle import dv_oracle as O
 from quantum_computations_amd import workloads as W
 
@@ -28,36 +29,13 @@ PASS_D2, PASS_D2X, PASS_D4, PASS_D4X, PASS_D4HL, PASS_PAIR, PASS_DIAG_T, PASS_DI
 
 @pytest.fixture(scope="module")
 def ask(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("layout") / "layout_driver"
-    subprocess.run([base.compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-fno-omit-frame-pointer", f"-I{base.CSRC}", str(base.HERE / "layout" / "layout_driver.cpp"), "-o", str(exe)],
-                   check=True)
+    exe = hostcheck.compile_driver(hostcheck.HERE / "layout" / "layout_driver.cpp", tmp_path_factory.mktemp("layout"))
 
     def run(requests):
         """requests: [str] -> one answer line per request, as a list of '|'-separated token lists."""
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-        proc = subprocess.run([str(exe)], input="\n".join(requests) + "\n", capture_output=True, text=True, env=env, timeout=600)
-        assert proc.returncode == 0 and "runtime error" not in proc.stderr and "Sanitizer" not in proc.stderr, proc.stderr[-4000:]
-        lines = proc.stdout.split("\n")[:-1]
-        assert len(lines) == len(requests)
+        lines = hostcheck.ask(exe, requests, timeout=600)
         return [[part.split() for part in line.split("|")] for line in lines]
     return run
-
-
-def nums(tokens):
-    return [int(t) for t in tokens]
-
-
-def floats(tokens):
-    return np.array([float.fromhex(t) for t in tokens])
-
-
-def text(values):
-    return " ".join(repr(float(v)) for v in values)
-
-
-def interleaved(m):
-    return np.stack([np.real(m), np.imag(m)], axis=-1).reshape(-1)
 
 
 # ---- split and stand-ins ------------------------------------------------------------------------------------------------
@@ -353,15 +331,6 @@ def tile12_takes(n, k, bits, ctrl):
     return not (min(bits) < (3 if k == 1 else 6) or Wn < 64 or Wn % 64)
 
 
-def op_line(r):
-    kind = {"dense": 0, "pair": 1, "diag": 2, "phase": 3}[r.kind]
-    m = np.zeros(32)
-    flat = interleaved(np.atleast_1d(r.m)) if r.kind != "pair" else np.zeros(0)
-    m[:flat.size] = flat
-    t = r.targets + [-1, -1]
-    return f"{kind} {len(r.targets)} {t[0]} {t[1]} {len(r.ctrl)} " + " ".join(map(str, r.ctrl)) + " " + text(m)
-
-
 def record_as_rec(n, r, form, code, rc, tc, tz0, tz1, m, q, tindex):
     """One PassGate record as a gate on TILE indices (what the kernel does with it), re-expressed in the caller's leg order
     so that the model sums products in the order of the gate applied on its own."""
@@ -400,37 +369,6 @@ def record_as_rec(n, r, form, code, rc, tc, tz0, tz1, m, q, tindex):
         return base.Rec("diag", [q[code // 4], q[code % 4]], [], d), cmask
     assert form == PASS_DIAG_M and tz0 not in regs
     return base.Rec("diag", [q[code], tz0], [], d), cmask
-
-
-def random_pass_list(rng, n, tile):
-    """Every kind of queued gate with its targets on tile bits; controls on any bit >= 3."""
-    tbits = list(range(6)) + [b for b in range(6, n) if (tile >> b) & 1]
-    recs = []
-    for _ in range(int(rng.integers(8, 40))):
-        kind = int(rng.integers(9))
-        t = [int(b) for b in rng.choice(tbits, size=2, replace=False)]
-        free = [b for b in range(3, n) if b not in t]
-        c = [int(b) for b in rng.choice(free, size=int(rng.integers(1, 3)), replace=False)]
-        if kind == 0:
-            recs.append(base.Rec("dense", t[:1], [], W.haar_unitary(2, rng)))
-        elif kind == 1:
-            recs.append(base.Rec("dense", t, [], W.haar_unitary(4, rng)))
-        elif kind == 2:
-            recs.append(base.Rec("dense", t[:1], c[:1], base.X))                       # CX
-        elif kind == 3:
-            recs.append(base.Rec("dense", t[:1], c, W.haar_unitary(2, rng)))           # controlled-U
-        elif kind == 4:
-            hi = [int(b) for b in rng.choice(tbits[6:], size=2, replace=False)]
-            recs.append(base.Rec("pair", hi, [], base.X))                              # SWAP of two bits >= 6
-        elif kind == 5:
-            recs.append(base.Rec("diag", t[:1], c[:int(rng.integers(0, 2))], np.exp(1j * rng.standard_normal(2))))
-        elif kind == 6:
-            recs.append(base.Rec("diag", t, [], np.exp(1j * rng.standard_normal(4))))
-        elif kind == 7:
-            recs.append(base.Rec("phase", [], c, np.exp(1j * rng.standard_normal())))
-        else:
-            recs.append(base.Rec("phase", [], c[:1] + [f for f in free if f not in c][:1], -1.0))    # CZ
-    return recs
 
 
 def test_pass_records_reproduce_the_gates_applied_one_by_one(ask):

@@ -9,33 +9,26 @@ of a record outside its named fields must be zero.
 from __future__ import annotations
 
 import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import test_defer_plan_host as base
-from test_layout_host import nums, op_line, random_pass_list
+import defer_plan_model as base
+import hostcheck
+from defer_plan_model import op_line, random_pass_list
+from hostcheck import nums
 from quantum_computations_amd import workloads as W
 
 CTL_NONE, CTL_REG, CTL_THREAD = range(3)
-GOLDEN = base.HERE / "golden" / "pass_records_uncontrolled.json"
+GOLDEN = hostcheck.HERE / "golden" / "pass_records_uncontrolled.json"
 
 
 @pytest.fixture(scope="module")
 def ask(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("pass_variants") / "pass_variants_driver"
-    subprocess.run([base.compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-fno-omit-frame-pointer", f"-I{base.CSRC}", str(base.HERE / "layout" / "pass_variants_driver.cpp"), "-o", str(exe)],
-                   check=True)
+    exe = hostcheck.compile_driver(hostcheck.HERE / "layout" / "pass_variants_driver.cpp", tmp_path_factory.mktemp("pass_variants"))
 
     def run(requests):
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-        proc = subprocess.run([str(exe)], input="\n".join(requests) + "\n", capture_output=True, text=True, env=env, timeout=600)
-        assert proc.returncode == 0 and "runtime error" not in proc.stderr and "Sanitizer" not in proc.stderr, proc.stderr[-4000:]
-        lines = proc.stdout.split("\n")[:-1]
-        assert len(lines) == len(requests)
+        lines = hostcheck.ask(exe, requests, timeout=600)
         return [[part.split() for part in line.split("|")] for line in lines]
     return run
 

@@ -8,13 +8,10 @@ of one pass (each pair visited once through the index whose pivot bit is clear) 
 """
 from __future__ import annotations
 
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-import test_defer_plan_host as base
+import hostcheck
 from quantum_computations_amd.dv_simulator import numpy_quantum as npq
 
 MASK64 = (1 << 64) - 1
@@ -22,19 +19,12 @@ MASK64 = (1 << 64) - 1
 
 @pytest.fixture(scope="module")
 def ask(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("pauli_plan") / "plan_driver"
-    subprocess.run([base.compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-fno-omit-frame-pointer", f"-I{base.CSRC}", str(base.HERE / "pauli_plan" / "plan_driver.cpp"), "-o", str(exe)],
-                   check=True)
+    exe = hostcheck.compile_driver(hostcheck.HERE / "pauli_plan" / "plan_driver.cpp", tmp_path_factory.mktemp("pauli_plan"))
 
     def run(term_lists):
         """term_lists: [[(xmask, zmask), ...]] -> [(cap, [pass dict, ...])], one per list."""
         requests = [" ".join([str(len(terms))] + [f"{x:x} {z:x}" for x, z in terms]) for terms in term_lists]
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-        proc = subprocess.run([str(exe)], input="\n".join(requests) + "\n", capture_output=True, text=True, env=env, timeout=600)
-        assert proc.returncode == 0 and "runtime error" not in proc.stderr and "Sanitizer" not in proc.stderr, proc.stderr[-4000:]
-        lines = proc.stdout.split("\n")[:-1]
-        assert len(lines) == len(requests)
+        lines = hostcheck.ask(exe, requests, timeout=600)
         plans = []
         for line in lines:
             head, *parts = [part.split() for part in line.split("|")]

@@ -15,13 +15,24 @@ import itertools
 import numpy as np
 import pytest
 
+import hostcheck
+import pauli_operator_reference as P
 import pauli_rotation_reference as R
-import test_pauli_plan_host as PP
+from hostcheck import floats, nums, text
 from oracle import dv_oracle as O
-from test_layout_host import ask, floats, nums, text  # noqa: F401  (ask: the sanitized driver, as a fixture)
 
 RO_MIN_QUBITS = 14
 RDM_LOADS = 4
+
+
+@pytest.fixture(scope="module")
+def ask(tmp_path_factory):
+    exe = hostcheck.compile_driver(hostcheck.HERE / "layout" / "layout_driver.cpp", tmp_path_factory.mktemp("readout_layout"))
+
+    def run(requests):
+        """requests: [str] -> one answer line per request, as a list of '|'-separated token lists."""
+        return [[part.split() for part in line.split("|")] for line in hostcheck.ask(exe, requests, timeout=600)]
+    return run
 
 
 def deposit_bits(value, positions):
@@ -290,17 +301,18 @@ def test_pauli_pass_args(ask):
     answers = ask([f"paulisum {n} {len(terms)} " + " ".join(f"{x} {z}" for x, z in terms) for terms in lists])
     widths = set()
     for terms, answer in zip(lists, answers):
-        passes = PP.model(terms, 8)
+        passes = P.sum_plan(terms, 8)
         assert len(answer) == len(passes) + 1 and answer[-1] == []
         for p, tokens in zip(passes, answer):
             ok, width, items, xmask, pivot, odd, *zmask = nums(tokens)
             count = len(p["zmask"])
+            low = (p["xmask"] & -p["xmask"]).bit_length() - 1      # the lowest flipped bit; -1: a diagonal pass
             assert ok == 1 and width == width_of(count) and width >= count
-            assert items == ((1 << n) if p["pivot"] < 0 else (1 << n) // 2)
-            assert xmask == p["xmask"] and pivot == max(p["pivot"], 0)
+            assert items == ((1 << n) if low < 0 else (1 << n) // 2)
+            assert xmask == p["xmask"] and pivot == max(low, 0)
             assert zmask == p["zmask"] + [0] * (8 - count)
             assert odd == sum((y & 1) << t for t, y in enumerate(p["n_y"]))
-            widths.add((width, p["pivot"] < 0))
+            widths.add((width, low < 0))
     assert widths == {(w, d) for w in (1, 2, 4, 8) for d in (False, True)}
     raw = [f"passraw {n} 3 0 {c} " + " ".join("5 1" for _ in range(c)) for c in (0, 1, 8, 9)]
     assert [nums(a[0])[0] for a in ask(raw)] == [0, 1, 1, 0], "1 .. 8 terms"

@@ -1,15 +1,15 @@
 """AddressSanitizer + UBSan pass over the HOST side of libqsv (CPU only).
 
-``tests/sanitize/build.py`` compiles every HIP source host-only with ``-fsanitize=address,undefined`` against a
-host-memory stand-in for the HIP runtime; ``tests/sanitize/driver.cpp`` then walks the C ABI: every validation branch
-(null pointers, out-of-range / duplicate qubits, bad sizes, caller-owned views without room) and the launch
-preparation of every kernel family -- enumeration tables, matrix re-indexing for every leg order and bit placement,
-controls folded into matrices, permutation lookup tables, block / plane tables of the mode kernels -- on registers
-from 0 to 18 qubits and cutoffs 2 to 32.  Kernels do not execute (there is no device code in this build).
+``tests/sanitize/build.py`` compiles every HIP source of the library host-only with ``-fsanitize=address,undefined`` and
+links that one set of objects, with a host-memory stand-in for the HIP runtime (``tests/sanitize/hip_stub.cpp``), with each
+driver of ``tests/sanitize``: a stand-alone program with its own ``main`` that walks the validation branches and the launch
+preparation of one group of C-ABI entry points (the head comment of each ``.cpp`` says which).  Kernels do not execute
+(there is no device code in this build), and nothing is loaded into Python under a sanitizer.
 """
 from __future__ import annotations
 
 import os
+import re
 import subprocess
 import sys
 from pathlib import Path
@@ -19,19 +19,33 @@ import pytest
 HERE = Path(__file__).resolve().parent
 sys.path.insert(0, str(HERE / "sanitize"))
 
+# driver, launches it must exceed (it really went through the launch paths), seconds
+DRIVERS = [
+    ("driver", 5000, 900),
+    ("pauli_sum_driver", 100, 600),
+    ("pauli_rotation_driver", 1000, 600),
+    ("pauli_operator_driver", 1000, 600),
+    ("krylov_driver", 1000, 600),
+    ("diagonal_driver", 1000, 600),
+    ("channel_driver", 1000, 600),
+    ("ensemble_driver", 1000, 600),
+    ("subsystem_driver", 500, 600),
+]
 
-def test_host_side_is_clean_under_asan_and_ubsan():
+
+@pytest.mark.parametrize("driver,min_launches,timeout", DRIVERS, ids=["host" if d == "driver" else d.replace("_driver", "") for d, _, _ in DRIVERS])
+def test_host_side_is_clean_under_asan_and_ubsan(driver, min_launches, timeout):
     import build as san_build
 
     if not san_build.CLANG.exists():
         pytest.skip("ROCm clang not installed")
-    exe = san_build.build()
+    exe = san_build.build(driver)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:halt_on_error=1",
                UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    proc = subprocess.run([str(exe)], capture_output=True, text=True, timeout=900, env=env)
+    proc = subprocess.run([str(exe)], capture_output=True, text=True, timeout=timeout, env=env)
     report = proc.stdout[-2000:] + proc.stderr[-6000:]
     assert "ERROR: AddressSanitizer" not in report and "runtime error:" not in report and "LeakSanitizer" not in report, report
     assert proc.returncode == 0, report
     assert "0 failed expectations" in proc.stdout
-    launches = int(proc.stdout.split("sanitized host driver: ")[1].split()[0])
-    assert launches > 5000          # the driver really went through the launch paths
+    launches = int(re.search(r"sanitized \S+ driver: (\d+) kernel launches prepared", proc.stdout).group(1))
+    assert launches > min_launches

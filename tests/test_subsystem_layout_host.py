@@ -10,13 +10,10 @@ domain the design states.  The marginal plan (k up to 26) gets the same ownershi
 """
 from __future__ import annotations
 
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-import test_defer_plan_host as base
+import hostcheck
 
 BLOCK, LANE_BITS, MIN_TILED, MAX_K, MARG_MAX_K = 256, 6, 14, 12, 26
 ROWS, TILE_GROUPS, PART_BYTES = 64, 64, 8 * 2 * 64 * 64
@@ -26,17 +23,10 @@ MARG_WAVES, MARG_PARTIALS = 4096, 1 << 22
 
 @pytest.fixture(scope="module")
 def ask(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("subsystem_layout") / "subsystem_layout_driver"
-    subprocess.run([base.compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-fno-omit-frame-pointer", f"-I{base.CSRC}", str(base.HERE / "layout" / "subsystem_layout_driver.cpp"), "-o", str(exe)],
-                   check=True)
+    exe = hostcheck.compile_driver(hostcheck.HERE / "layout" / "subsystem_layout_driver.cpp", tmp_path_factory.mktemp("subsystem_layout"))
 
     def run(requests):
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-        proc = subprocess.run([str(exe)], input="\n".join(requests) + "\n", capture_output=True, text=True, env=env, timeout=900)
-        assert proc.returncode == 0 and "runtime error" not in proc.stderr and "Sanitizer" not in proc.stderr, proc.stderr[-4000:]
-        lines = proc.stdout.split("\n")[:-1]
-        assert len(lines) == len(requests)
+        lines = hostcheck.ask(exe, requests, timeout=900)
         return [[[int(x) for x in part.split()] for part in line.split("|")] for line in lines]
     return run
 

@@ -419,6 +419,38 @@ int qsv_ensemble_log_read(qsv_state *st, int32_t *branches, double *probs /* [st
 int qsv_ensemble_norm2(qsv_state *st, int member_qubits, double *out /* members */);
 int qsv_ensemble_expect_pauli_sum(qsv_state *st, int member_qubits, int n_terms, const int *term_offsets, const int *qubits, const char *paulis,
                                   const double *coeffs, double *values /* members */, double *term_values /* NULL or [members][n_terms] */);
+/* ---- ensembles: per-member measurement, classical bits and feed-forward (csrc/qsv_ensemble.hip) ----
+ * Every member owns one uint64_t of CLASSICAL BITS, zero at creation, in a device allocation of its own that is made on the
+ * first of the calls below, re-made and zeroed when member_qubits changes (only while the ensemble log is empty, QSV_ESTATE
+ * otherwise) and freed with the register.
+ *  - qsv_ensemble_measure is a projective measurement of member qubit `qubit` in every member at once; the qubit STAYS in the
+ *    register.  eig_s = (Re, Im) of e_s[0], e_s[1].  phi_s = (e_s^T on the qubit) psi_m with the eigenvectors unconjugated, as
+ *    in qsv_measure; w_s = |phi_s|^2, total = w_0 + w_1.  The outcome is forced[m] if it is >= 0, else the first s with
+ *    w_0 + .. + w_s > u01[m] total (the last positive one if rounding leaves none): the branch rule of
+ *    qsv_ensemble_apply_channel.  The member becomes v_s (x) phi_s sqrt(total / w_s) with v_s = conj(e_s) (after = 0) or
+ *    |0> (after = 1); a forced outcome of weight 0 zeroes the member and logs probability 0; no inf or nan is produced.
+ *    bit >= 0: bit `bit` of the member's word becomes the outcome.  The call appends one STEP (outcome, w_s / total) to the
+ *    ensemble log exactly like a channel call, so qsv_ensemble_log_read keeps call order across channels and measurements.
+ *    Three launches: the read pass and the update pass of a one-qubit channel call, and between them k_ens_measure_select,
+ *    which has the eigenvectors in its kernel arguments: nothing is uploaded but the draws, through the pinned ring.
+ *  - qsv_ensemble_apply_conditional applies the k-qubit matrix (k = 1 or 2) to the members whose word satisfies
+ *    (word & all_of) == all_of && (word & none_of) == 0; all others are left bit-identical and their amplitudes are neither
+ *    read nor written.  Both masks 0: every member.  One launch, nothing logged.
+ *  - qsv_ensemble_bits_read copies the words out (one copy, one synchronisation); qsv_ensemble_bits_write sets them
+ *    (bits = NULL: all zero; one copy, the words are staged before the call returns).
+ * measure and apply_conditional flush the deferred queue, are enqueued on the register's stream and return without waiting.
+ * QSV_EINVAL for null pointers, member_qubits outside k .. n_total (1 .. n_total for measure, 0 .. n_total for the bits), qubits
+ * >= member_qubits or repeated, any u01[m] outside [0, 1), any forced[m] outside -1 .. 1, bit outside -1 .. 63, after outside
+ * 0 .. 1, k outside 1 .. 2, all_of & none_of != 0, a view; QSV_ESTATE for a mode register: each before any launch and with the
+ * deferred queue untouched. */
+int qsv_ensemble_measure(qsv_state *st, int member_qubits, int qubit, const double eig0[4], const double eig1[4],
+                         int after /* 0 keep, 1 reset */, int bit /* 0..63, -1 = none */,
+                         const double *u01 /* members */, const int *forced /* NULL or members: -1 draw, 0, 1 */);
+int qsv_ensemble_apply_conditional(qsv_state *st, int member_qubits, int k /* 1 or 2 */, const int *qubits,
+                                   const double *matrix /* 4^k complex, row-major, qubits[0] most significant */,
+                                   uint64_t all_of, uint64_t none_of);
+int qsv_ensemble_bits_read(qsv_state *st, int member_qubits, uint64_t *bits /* members */);
+int qsv_ensemble_bits_write(qsv_state *st, int member_qubits, const uint64_t *bits /* NULL = clear all */);
 /* Reduced density matrix of the k <= 6 qubits `qubits` (all others traced out) in one read pass over the register:
  * rho[i][j] = sum_rest psi[i, rest] conj(psi[j, rest]), written row-major as 4^k complex numbers, qubits[0] the most
  * significant bit of i and j.  What a caller of the reference gets from npq.ket2dm (numpy_quantum.py:110-113)

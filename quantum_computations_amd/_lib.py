@@ -95,6 +95,10 @@ SIGNATURES: dict[str, list] = {
     "qsv_ensemble_apply_channel": [_state_p, C.c_int, _state_p, _int_p, _dbl_p, _int_p],
     "qsv_ensemble_log_read": [_state_p, C.POINTER(C.c_int32), _dbl_p, C.c_uint64, _u64_p],
     "qsv_ensemble_norm2": [_state_p, C.c_int, _dbl_p],
+    "qsv_ensemble_measure": [_state_p, C.c_int, C.c_int, _dbl_p, _dbl_p, C.c_int, C.c_int, _dbl_p, _int_p],
+    "qsv_ensemble_apply_conditional": [_state_p, C.c_int, C.c_int, _int_p, _dbl_p, C.c_uint64, C.c_uint64],
+    "qsv_ensemble_bits_read": [_state_p, C.c_int, _u64_p],
+    "qsv_ensemble_bits_write": [_state_p, C.c_int, _u64_p],
     "qsv_ensemble_expect_pauli_sum": [_state_p, C.c_int, C.c_int, _int_p, _int_p, C.c_char_p, _dbl_p, _dbl_p, _dbl_p],
     "qsv_reduced_density": [_state_p, C.c_int, _int_p, C.c_void_p],
     "qsv_reduced_density_state": [_state_p, C.c_int, _int_p, _state_p],

@@ -7,12 +7,17 @@
 //                         for one -- weights, the choice against the member's own draw, K_j sqrt(total / w_j) into the
 //                         member's matrix slot, (j, w_j / total) into the member's column of the device log;
 //   k_ens_channel_apply   one in-place pass, every group of 2^k amplitudes multiplied by the matrix of its own member.
+// A measurement is the same two passes around k_ens_measure_select, which has the two eigenvectors in
+// its kernel arguments, takes the member's outcome by the same rule and writes it to one of the member's 64 classical bits;
+// k_ens_apply_conditional is k_ens_channel_apply with one matrix for all members and a predicate on those bits: members
+// that do not take the gate are neither read nor written.
 // k_ens_expect_pauli_group / k_ens_sum_parts give <psi_m|P_t|psi_m> per member for the passes of qsv_pauli_plan.h.
 // The per-item bodies are those of k_channel_rdm, k_channel_apply and k_expect_pauli_group on a register of 2^n amplitudes;
 // what is new is the member dimension and where the sums stop.  Launch shapes: qsv_ensemble_layout.h.
 
 #include "qsv_device.h"
 #include "qsv_ensemble_layout.h"
+#include "qsv_ensemble_control_layout.h"
 
 #include <cmath>
 #include <cstring>
@@ -20,6 +25,9 @@
 
 using namespace qsv_channel_layout;
 using namespace qsv_ensemble_layout;
+using qsv_ensemble_control_layout::ConditionalArgs;
+using qsv_ensemble_control_layout::cond_grid;
+using qsv_ensemble_control_layout::MeasureArgs;
 using qsv_readout_layout::PauliPass;
 using qsv_readout_layout::PauliPassArgs;
 using qsv_readout_layout::pauli_pass_args;
@@ -39,6 +47,9 @@ struct EnsembleWork {
     int used = 0;
     std::vector<int32_t> branches;    // [host steps][members]
     std::vector<double> probs;
+    uint64_t *bits = nullptr;         // device: one word of classical bits per member, an allocation of its own
+    int bits_n = -1;                  // member qubits and members the words were made for
+    uint64_t bits_members = 0;
 };
 
 void free_ensemble_work(void *p) {
@@ -47,6 +58,7 @@ void free_ensemble_work(void *p) {
     (void)hipSetDevice(w->device);
     if (w->dev) (void)hipFree(w->dev);
     if (w->ring) (void)hipHostFree(w->ring);
+    if (w->bits) (void)hipFree(w->bits);
     delete w;
 }
 
@@ -100,6 +112,31 @@ int ensure_workspace(qsv_state *st, EnsembleWork *w, int n, uint64_t members) {
     w->ws = ws;
     w->n = n;
     w->used = 0;
+    return QSV_OK;
+}
+
+// The classical bits: made and zeroed at the first call that needs them, re-made and zeroed when the member size changes.
+int ensure_bits(qsv_state *st, EnsembleWork *w, int n, uint64_t members) {
+    if (w->bits && w->bits_n == n && w->bits_members == members) return QSV_OK;
+    if (w->bits) {
+        QSV_HIP(hipStreamSynchronize(st->stream));
+        (void)hipFree(w->bits);
+        w->bits = nullptr;
+    }
+    if (hipMalloc(reinterpret_cast<void **>(&w->bits), qsv_ensemble_control_layout::bits_bytes(members)) != hipSuccess) {
+        w->bits = nullptr;
+        return qsv_fail(QSV_ENOMEM, "device allocation of the ensemble's classical bits failed");
+    }
+    w->bits_n = n;
+    w->bits_members = members;
+    QSV_HIP(hipMemsetAsync(w->bits, 0, qsv_ensemble_control_layout::bits_bytes(members), st->stream));
+    return QSV_OK;
+}
+
+// the member size may change only while the log is empty: its rows have `members` columns
+int check_member_size(const EnsembleWork *w, int n, uint64_t members) {
+    if (w->dev && (w->n != n || w->ws.members != members) && pending_steps(w) > 0)
+        return qsv_fail(QSV_ESTATE, "read the ensemble log before changing the member size");
     return QSV_OK;
 }
 
@@ -382,6 +419,145 @@ __global__ __launch_bounds__(QSV_BLOCK) void k_ens_channel_apply(amp_t *__restri
     }
 }
 
+// One thread per member.  The steps of k_ens_channel_select for the two rank-1 operators K_s = v_s e_s^T of a measurement,
+// E_s = K_s^dagger K_s = conj(e_s) e_s^T: the member's parts added in index order, w_s = tr(E_s rho), the choice against
+// the member's own draw, K_s sqrt(total / w_s) into the member's matrix slot, (s, w_s / total) into the member's column of
+// the log -- and the outcome into bit c.bit of the member's word (a plain store: nobody else writes that word).
+__global__ __launch_bounds__(QSV_BLOCK) void k_ens_measure_select(const double *__restrict__ partials, int parts, const MeasureArgs c,
+                                                                  const double *__restrict__ draws, uint64_t members, double *__restrict__ matrix,
+                                                                  double *__restrict__ log, uint64_t *__restrict__ bits) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * QSV_BLOCK;
+    for (uint64_t m = static_cast<uint64_t>(blockIdx.x) * QSV_BLOCK + threadIdx.x; m < members; m += stride) {
+        double rho[4] = {0.0, 0.0, 0.0, 0.0};     // rho00, rho11, Re rho01, Im rho01
+        const double *p = partials + m * parts * 4;
+        for (int q = 0; q < parts; ++q)            // index order
+#pragma unroll
+            for (int r = 0; r < 4; ++r) rho[r] += p[static_cast<size_t>(q) * 4 + r];
+        double wt[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const double ar = c.eig[s][0], ai = c.eig[s][1], br = c.eig[s][2], bi = c.eig[s][3];
+            const double d = (ar * ar + ai * ai) * rho[0] + (br * br + bi * bi) * rho[1];
+            const double off = (ar * br + ai * bi) * rho[2] + (ar * bi - ai * br) * rho[3];     // E01 = conj(e[0]) e[1]
+            wt[s] = d + 2.0 * off;
+        }
+        const double total = wt[0] + wt[1];
+        const double u = draws[2 * m];
+        int pick = static_cast<int>(draws[2 * m + 1]);
+        if (pick < 0) {
+            const double target = u * total;
+            double run = 0.0;
+            int last = -1;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                run += wt[j];
+                if (wt[j] > 0.0) last = j;
+                if (pick < 0 && run > target && wt[j] > 0.0) pick = j;
+            }
+            if (pick < 0) pick = last < 0 ? 0 : last;
+        }
+        const double wj = pick ? wt[1] : wt[0];
+        const bool alive = wj > 0.0 && total > 0.0;
+        const double sc = alive ? sqrt(total / wj) : 0.0;
+        log[2 * m] = static_cast<double>(pick);
+        log[2 * m + 1] = alive ? wj / total : 0.0;
+        // K[r][c] = v[r] e[c] sc, v = conj(e) (keep) or |0> (reset); a scale of 0 writes zeros whatever e holds
+        const double er[2] = {pick ? c.eig[1][0] : c.eig[0][0], pick ? c.eig[1][2] : c.eig[0][2]};
+        const double ei[2] = {pick ? c.eig[1][1] : c.eig[0][1], pick ? c.eig[1][3] : c.eig[0][3]};
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const double vr = c.after ? (r == 0 ? 1.0 : 0.0) : er[r], vi = c.after ? 0.0 : -ei[r];
+#pragma unroll
+            for (int col = 0; col < 2; ++col) {
+                matrix[32 * m + 2 * (r * 2 + col)] = sc != 0.0 ? (vr * er[col] - vi * ei[col]) * sc : 0.0;
+                matrix[32 * m + 2 * (r * 2 + col) + 1] = sc != 0.0 ? (vr * ei[col] + vi * er[col]) * sc : 0.0;
+            }
+        }
+        if (c.bit >= 0) {
+            const uint64_t mask = 1ull << c.bit, word = bits[m];
+            bits[m] = pick ? word | mask : word & ~mask;
+        }
+    }
+}
+
+// k_ens_channel_apply's item body and index arithmetic with ONE matrix, in the kernel arguments and fetched once, for the
+// members whose classical bits satisfy (word & all_of) == all_of && (word & none_of) == 0.  Where a unit lies in one member
+// (256 items or more) the member index comes from the unit, the word is loaded once per unit -- a chunk of units per load -- and the
+// whole workgroup skips the unit; where members share a unit every thread tests the word of its own member.  With KL > 0 a wave lies in one
+// member (n >= 6), so every shfl_xor partner of a lane has the lane's predicate and a wave is in the item loop as a whole
+// (cond_partner_member of qsv_ensemble_control_layout.h).  No barrier.  A member that does not take the gate is neither
+// read nor written.
+template <int K, int KL, bool NT>
+__global__ __launch_bounds__(QSV_BLOCK) void k_ens_apply_conditional(amp_t *__restrict__ a, const ChannelArgs g, const EnsArgs e, const ConditionalArgs c,
+                                                                     const uint64_t *__restrict__ bits) {
+    constexpr int KH = K - KL, NH = 1 << KH, NL = 1 << KL, D = 1 << K;
+    const int l_own = own_combination<KL>(g);
+    cplx mm[NH][NH][NL];
+#pragma unroll
+    for (int h = 0; h < NH; ++h)
+#pragma unroll
+        for (int j = 0; j < NH; ++j)
+#pragma unroll
+            for (int dl = 0; dl < NL; ++dl) {
+                const int r = g.ghi[h] | glo_of<KL>(g, l_own), col = g.ghi[j] | glo_of<KL>(g, l_own ^ dl);
+                mm[h][j][dl] = cplx{c.m[2 * (r * D + col)], c.m[2 * (r * D + col) + 1]};
+            }
+    // the items of unit `unit` that are this thread's
+    auto work = [&](const Mine &t) {
+        amp_t *am = a + (t.member << e.n);
+        for (uint64_t w = t.first; w < t.items; w += t.stride) {
+            const uint64_t base = deposit(w, g);
+            amp_t x[NH], out[NH];
+#pragma unroll
+            for (int h = 0; h < NH; ++h) {
+                x[h] = ld<NT>(am + base + g.hoff[h]);
+                out[h] = amp_t{0.0, 0.0};
+            }
+#pragma unroll
+            for (int j = 0; j < NH; ++j)
+#pragma unroll
+                for (int dl = 0; dl < NL; ++dl) {
+                    const amp_t y = dl == 0 ? x[j] : shfl_xor_amp(x[j], g.lxor[dl]);
+#pragma unroll
+                    for (int h = 0; h < NH; ++h) out[h] = cfma(mm[h][j][dl], y, out[h]);
+                }
+#pragma unroll
+            for (int h = 0; h < NH; ++h) st<NT>(am + base + g.hoff[h], out[h]);
+        }
+    };
+    if (e.item_bits >= ENS_BLOCK_BITS) {
+        // A unit lies in one member.  A workgroup takes chunks of 2^chunk_bits consecutive units: lane l of every wave fetches
+        // the word of unit (chunk << chunk_bits) + l (cond_batch_unit), the ballot is the same wave-uniform mask in all four
+        // waves, and the workgroup works through the units whose bit is set: a unit that is skipped costs nothing but its
+        // share of this load.
+        const uint32_t lane = threadIdx.x & 63u;
+        const uint64_t chunks = (e.units + (1ull << c.chunk_bits) - 1ull) >> c.chunk_bits;
+        for (uint64_t chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x) {
+            const uint64_t first = chunk << c.chunk_bits, candidate = first + lane;
+            bool take = false;
+            if (lane < (1u << c.chunk_bits) && candidate < e.units) {
+                const uint64_t word = bits[(candidate >> e.part_bits) << e.share_bits];
+                take = (word & c.all_of) == c.all_of && (word & c.none_of) == 0;
+            }
+            unsigned long long todo = __ballot(take);
+            while (todo) {
+                const int l = __ffsll(todo) - 1;
+                todo &= todo - 1;
+                work(mine(e, first + static_cast<uint64_t>(l)));     // live: with 256 items or more per member every unit is
+            }
+        }
+        return;
+    }
+    // Members share a unit: every thread tests the word of its own member (whole waves where KL > 0)
+    for (uint64_t unit = blockIdx.x; unit < e.units; unit += gridDim.x) {
+        const Mine t = mine(e, unit);
+        if (!t.live) continue;
+        const uint64_t word = bits[t.member];
+        if ((word & c.all_of) != c.all_of || (word & c.none_of) != 0) continue;
+        work(t);
+    }
+}
+
 // k_expect_pauli_group's item body on member-local indices (g.items is not used: the items of a member are e.item_bits).
 constexpr int ENS_PAULI_ITEMS = 4;
 template <int T, bool DIAG>
@@ -622,6 +798,150 @@ int qsv_ensemble_log_read(qsv_state *st, int32_t *branches, double *probs, uint6
     std::memcpy(probs, work->probs.data(), sizeof(double) * work->probs.size());
     work->branches.clear();
     work->probs.clear();
+    return QSV_OK;
+}
+
+int qsv_ensemble_measure(qsv_state *st, int member_qubits, int qubit, const double eig0[4], const double eig1[4], int after, int bit,
+                         const double *u01, const int *forced) {
+    if (!st || !eig0 || !eig1 || !u01) return qsv_fail(QSV_EINVAL, "null pointer");
+    int rc = check_ensemble(st, member_qubits, 1);
+    if (rc) return rc;
+    rc = check_member_qubits(member_qubits, 1, &qubit);
+    if (rc) return rc;
+    if (after < 0 || after > 1) return qsv_fail(QSV_EINVAL, "after is 0 (keep the eigenvector) or 1 (reset to |0>)");
+    if (bit < -1 || bit > 63) return qsv_fail(QSV_EINVAL, "a member has the classical bits 0 .. 63 (-1: none)");
+    const int n = member_qubits;
+    const uint64_t members = st->amps >> n;
+    for (uint64_t m = 0; m < members; ++m) {
+        if (!(u01[m] >= 0.0 && u01[m] < 1.0)) return qsv_fail(QSV_EINVAL, "every draw must lie in [0, 1)");
+        if (forced && (forced[m] < -1 || forced[m] > 1)) return qsv_fail(QSV_EINVAL, "forced outcome out of range");
+    }
+    EnsembleWork *work = work_of(st);
+    rc = check_member_size(work, n, members);
+    if (rc) return rc;
+    rc = qsv_flush(st);
+    if (rc) return rc;
+    QSV_HIP(hipSetDevice(st->device));
+    rc = ensure_workspace(st, work, n, members);
+    if (rc) return rc;
+    rc = ensure_bits(st, work, n, members);
+    if (rc) return rc;
+    if (work->used == work->ws.slots) {
+        rc = drain(st, work);
+        if (rc) return rc;
+    }
+    double *slot = work->ring + 2 * members * static_cast<size_t>(work->used);
+    for (uint64_t m = 0; m < members; ++m) {
+        slot[2 * m] = u01[m];
+        slot[2 * m + 1] = forced ? static_cast<double>(forced[m]) : -1.0;
+    }
+    double *partials = work->dev + work->ws.partials, *matrix = work->dev + work->ws.matrix, *draws = work->dev + work->ws.draws;
+    double *log = work->dev + work->ws.log + 2 * members * static_cast<size_t>(work->used);
+    QSV_HIP(hipMemcpyAsync(draws, slot, sizeof(double) * 2 * members, hipMemcpyHostToDevice, st->stream));
+    const int bits[2] = {n - 1 - qubit, 0};
+    const ChannelPlan plan = ens_channel_plan(n, 1, bits, ens_lanes(n, st->readout_variant != 1));
+    const bool nt = st->nontemporal != 0;
+    const int item_bits = n - plan.kh;
+    const EnsArgs read = ens_args(n, members, item_bits, part_bits(item_bits, st->grid_cap));
+    const EnsArgs update = ens_args(n, members, item_bits, apply_part_bits(item_bits, st->grid_cap));
+    MeasureArgs args;
+    std::memcpy(args.eig[0], eig0, sizeof(double) * 4);
+    std::memcpy(args.eig[1], eig1, sizeof(double) * 4);
+    args.after = after;
+    args.bit = bit;
+    with_shape(1, plan.kl, nt, [&](auto K, auto KL, auto NT) {
+        hipLaunchKernelGGL((k_ens_channel_rdm<K.value, KL.value, NT.value>), dim3(ens_grid(read, st->grid_cap)), dim3(QSV_BLOCK), 0, st->stream,
+                           static_cast<const amp_t *>(st->data), plan.g, read, partials);
+    });
+    rc = check_launch();
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_ens_measure_select, dim3(grid_for(members, QSV_BLOCK, static_cast<int>(CH_MAX_BLOCKS))), dim3(QSV_BLOCK), 0, st->stream,
+                       static_cast<const double *>(partials), 1 << read.part_bits, args, static_cast<const double *>(draws), members, matrix, log,
+                       work->bits);
+    rc = check_launch();
+    if (rc) return rc;
+    ++work->used;     // the log slot is written from here on, whatever becomes of the update pass
+    with_shape(1, plan.kl, nt, [&](auto K, auto KL, auto NT) {
+        hipLaunchKernelGGL((k_ens_channel_apply<K.value, KL.value, NT.value>), dim3(ens_grid(update, st->grid_cap)), dim3(QSV_BLOCK), 0, st->stream,
+                           st->data, plan.g, update, static_cast<const double *>(matrix));
+    });
+    snprintf(st->last_kernel, sizeof(st->last_kernel), "k_ens_channel_apply<1, %d, %s> after k_ens_measure_select after k_ens_channel_rdm", plan.kl,
+             nt ? "true" : "false");
+    return check_launch();
+}
+
+int qsv_ensemble_apply_conditional(qsv_state *st, int member_qubits, int k, const int *qubits, const double *matrix, uint64_t all_of,
+                                   uint64_t none_of) {
+    if (!st || !qubits || !matrix) return qsv_fail(QSV_EINVAL, "null pointer");
+    if (k < 1 || k > 2) return qsv_fail(QSV_EINVAL, "a conditional gate acts on 1 or 2 qubits");
+    int rc = check_ensemble(st, member_qubits, k);
+    if (rc) return rc;
+    rc = check_member_qubits(member_qubits, k, qubits);
+    if (rc) return rc;
+    if (!qsv_ensemble_control_layout::masks_ok(all_of, none_of)) return qsv_fail(QSV_EINVAL, "a bit cannot be asked to be both set and clear");
+    const int n = member_qubits;
+    const uint64_t members = st->amps >> n;
+    EnsembleWork *work = work_of(st);
+    rc = check_member_size(work, n, members);
+    if (rc) return rc;
+    rc = qsv_flush(st);
+    if (rc) return rc;
+    QSV_HIP(hipSetDevice(st->device));
+    rc = ensure_bits(st, work, n, members);
+    if (rc) return rc;
+    int bits[2] = {0, 0};
+    for (int i = 0; i < k; ++i) bits[i] = n - 1 - qubits[i];
+    const ChannelPlan plan = ens_channel_plan(n, k, bits, ens_lanes(n, st->readout_variant != 1));
+    const bool nt = st->nontemporal != 0;
+    const int item_bits = n - plan.kh;
+    const EnsArgs update = ens_args(n, members, item_bits, apply_part_bits(item_bits, st->grid_cap));
+    ConditionalArgs args;
+    std::memset(&args, 0, sizeof(args));
+    std::memcpy(args.m, matrix, sizeof(double) * 2 * (size_t(1) << (2 * k)));
+    args.all_of = all_of;
+    args.none_of = none_of;
+    args.chunk_bits = qsv_ensemble_control_layout::cond_unit_uniform(update) ? qsv_ensemble_control_layout::cond_chunk_bits(update.units) : 0;
+    with_shape(k, plan.kl, nt, [&](auto K, auto KL, auto NT) {
+        hipLaunchKernelGGL((k_ens_apply_conditional<K.value, KL.value, NT.value>), dim3(cond_grid(update, st->grid_cap)), dim3(QSV_BLOCK), 0, st->stream,
+                           st->data, plan.g, update, args, static_cast<const uint64_t *>(work->bits));
+    });
+    snprintf(st->last_kernel, sizeof(st->last_kernel), "k_ens_apply_conditional<%d, %d, %s>", k, plan.kl, nt ? "true" : "false");
+    return check_launch();
+}
+
+int qsv_ensemble_bits_read(qsv_state *st, int member_qubits, uint64_t *bits) {
+    if (!st || !bits) return qsv_fail(QSV_EINVAL, "null pointer");
+    int rc = check_ensemble(st, member_qubits, 0);
+    if (rc) return rc;
+    const uint64_t members = st->amps >> member_qubits;
+    EnsembleWork *work = work_of(st);
+    rc = check_member_size(work, member_qubits, members);
+    if (rc) return rc;
+    QSV_HIP(hipSetDevice(st->device));
+    rc = ensure_bits(st, work, member_qubits, members);
+    if (rc) return rc;
+    QSV_HIP(hipMemcpyAsync(bits, work->bits, qsv_ensemble_control_layout::bits_bytes(members), hipMemcpyDeviceToHost, st->stream));
+    QSV_HIP(hipStreamSynchronize(st->stream));
+    return QSV_OK;
+}
+
+int qsv_ensemble_bits_write(qsv_state *st, int member_qubits, const uint64_t *bits) {
+    if (!st) return qsv_fail(QSV_EINVAL, "null pointer");
+    int rc = check_ensemble(st, member_qubits, 0);
+    if (rc) return rc;
+    const uint64_t members = st->amps >> member_qubits;
+    EnsembleWork *work = work_of(st);
+    rc = check_member_size(work, member_qubits, members);
+    if (rc) return rc;
+    QSV_HIP(hipSetDevice(st->device));
+    rc = ensure_bits(st, work, member_qubits, members);
+    if (rc) return rc;
+    if (!bits) {
+        QSV_HIP(hipMemsetAsync(work->bits, 0, qsv_ensemble_control_layout::bits_bytes(members), st->stream));
+        return QSV_OK;
+    }
+    // pageable memory: the copy has left the caller's buffer when this returns, and is ordered on the register's stream
+    QSV_HIP(hipMemcpyAsync(work->bits, bits, qsv_ensemble_control_layout::bits_bytes(members), hipMemcpyHostToDevice, st->stream));
     return QSV_OK;
 }
 

@@ -5,6 +5,10 @@ amplitudes ``[m 2^n, (m + 1) 2^n)``: the member index is the leading ``b`` qubit
 register qubit ``q + b``.  A unitary on member qubits is one pass over the register for all members, deferred gates included;
 what differs from member to member -- the branch a Kraus channel takes, norms, Pauli values -- goes through the
 ``qsv_ensemble_*`` entry points.  Qubit indices of this class are MEMBER qubits.
+
+Every member also owns 64 classical bits on the device (section 24): ``measure`` projects a qubit of every member, each
+with its own draw, and writes the member's outcome to one of them; ``apply_conditional`` applies a gate to the members
+whose bits satisfy a condition and leaves the others untouched -- feed-forward without a host round trip.
 """
 from __future__ import annotations
 
@@ -27,6 +31,7 @@ class TrajectoryEnsemble:
         self.member_qubits = int(member_qubits)
         self.member_bits = total - self.member_qubits
         self.members = 1 << self.member_bits
+        self._measured: list[int] = []        # the classical bit of the k-th measurement since reset(): ClassicalControl's indices
 
     @classmethod
     def from_ket(cls, ket, members: int, device: int = 0) -> "TrajectoryEnsemble":
@@ -56,6 +61,8 @@ class TrajectoryEnsemble:
             raise ValueError("the ket does not have the size of a member")
         self.state.upload(ket, 0)
         _lib.call("qsv_ensemble_broadcast", self.state._h, self.member_qubits)
+        self.set_bits(None)
+        self._measured = []
         return self
 
     def close(self) -> None:
@@ -64,12 +71,28 @@ class TrajectoryEnsemble:
         self.state = None
 
     # ---- circuit elements -------------------------------------------------------------------------------------------------
-    def apply(self, gate) -> "TrajectoryEnsemble":
+    def apply(self, gate, *, u=None) -> "TrajectoryEnsemble":
         """A unitary gate on member qubits goes to the register and acts on every member; a ``noise.Channel`` is one
-        trajectory step of every member."""
-        from .noise import Channel
+        trajectory step of every member; a ``noise.Measure`` measures every member (the k-th since ``reset()`` writes
+        classical bit k unless it names a ``bit``); a ``ClassicalControl`` is taken by the members whose outcomes satisfy it,
+        its indices being positions in the list of measurements, as in ``Simulator.run``.  ``u``: the draws of a channel or
+        a measurement, one per member."""
+        from .dv_simulator.simulator import ClassicalControl
+        from .noise import Channel, Measure, _control_masks
         if isinstance(gate, Channel):
-            return self.apply_channel(gate.channel, gate.indices, rng=gate.rng)
+            return self.apply_channel(gate.channel, gate.indices, u=u, rng=gate.rng)
+        if isinstance(gate, Measure):
+            bit = gate.bit
+            if bit is None:
+                bit = len(self._measured)
+                if bit > 63:
+                    raise ValueError("a member has 64 classical bits: reuse bits with bit=")
+            self.measure(gate.indices[0], gate.theta, gate.phi, u=u, result=gate.result, reset=gate.reset, bit=bit, rng=gate.rng)
+            self._measured.append(bit)
+            return self
+        if isinstance(gate, ClassicalControl):
+            positive, negative = _control_masks(gate, self._measured)
+            return self.apply_conditional(gate.gate, positive, negative)
         if any(not 0 <= int(q) < self.member_qubits for q in gate.indices):
             raise ValueError(f"qubit index out of range for members of {self.member_qubits} qubits")
         matrix = getattr(gate, "matrix", None)
@@ -103,6 +126,79 @@ class TrajectoryEnsemble:
         _lib.call("qsv_ensemble_apply_channel", self.state._h, self.member_qubits, channel.handle(self.state.device), _ints(qubits),
                   u.ctypes.data_as(C.POINTER(C.c_double)), None if fbuf is None else fbuf.ctypes.data_as(C.POINTER(C.c_int)))
         return self
+
+    def measure(self, q: int, theta: float = 0.0, phi: float = 0.0, *, u=None, result=None, reset: bool = False, bit=None,
+                rng=None) -> "TrajectoryEnsemble":
+        """Measure member qubit ``q`` of every member along ``(theta, phi)``; the qubit stays (``reset``: in ``|0>``).
+        ``u``: one draw per member (default ``rng.random(members)`` or the global ``np.random``); ``result``: ``None``, one
+        forced outcome for all, or one per member with ``-1`` = draw; ``bit``: the classical bit that takes the outcome
+        (``None``: it is only logged).  The step is appended to ``channel_log()``."""
+        from .noise import Measure
+        e0, e1 = Measure(q, theta, phi).eigenvectors()
+        if u is None:
+            u = rng.random(self.members) if rng is not None else np.random.random(self.members)
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+        if u.shape[0] != self.members:
+            raise ValueError("one draw per member")
+        fbuf = None
+        if result is not None:
+            fbuf = np.ascontiguousarray(np.broadcast_to(np.asarray(result, dtype=np.int32), (self.members,)) if np.ndim(result) == 0
+                                        else np.asarray(result, dtype=np.int32).reshape(-1))
+            if fbuf.shape[0] != self.members:
+                raise ValueError("one forced outcome per member (-1 = draw)")
+        eig0 = np.ascontiguousarray(np.asarray(e0, dtype=np.complex128).reshape(2)).view(np.float64)
+        eig1 = np.ascontiguousarray(np.asarray(e1, dtype=np.complex128).reshape(2)).view(np.float64)
+        _lib.call("qsv_ensemble_measure", self.state._h, self.member_qubits, int(q), eig0.ctypes.data_as(C.POINTER(C.c_double)),
+                  eig1.ctypes.data_as(C.POINTER(C.c_double)), 1 if reset else 0, -1 if bit is None else int(bit),
+                  u.ctypes.data_as(C.POINTER(C.c_double)), None if fbuf is None else fbuf.ctypes.data_as(C.POINTER(C.c_int)))
+        return self
+
+    def apply_conditional(self, gate, positive=(), negative=()) -> "TrajectoryEnsemble":
+        """``gate`` (a 1- or 2-qubit unitary on member qubits) on the members whose classical bits ``positive`` are all 1
+        and ``negative`` all 0; every other member is left bit-identical."""
+        matrix = getattr(gate, "matrix", None)
+        indices = [int(q) for q in getattr(gate, "indices", [])]
+        if matrix is None or matrix.shape[0] != matrix.shape[1] or len(indices) not in (1, 2) or matrix.shape[0] != 1 << len(indices):
+            raise ValueError("a conditional gate of an ensemble is a 1- or 2-qubit unitary")
+        all_of = none_of = 0
+        for b in positive:
+            if not 0 <= int(b) <= 63:
+                raise ValueError("a member has the classical bits 0 .. 63")
+            all_of |= 1 << int(b)
+        for b in negative:
+            if not 0 <= int(b) <= 63:
+                raise ValueError("a member has the classical bits 0 .. 63")
+            none_of |= 1 << int(b)
+        buf = np.ascontiguousarray(matrix, dtype=np.complex128).view(np.float64)
+        _lib.call("qsv_ensemble_apply_conditional", self.state._h, self.member_qubits, len(indices), _ints(indices),
+                  buf.ctypes.data_as(C.POINTER(C.c_double)), C.c_uint64(all_of), C.c_uint64(none_of))
+        return self
+
+    def bits(self) -> np.ndarray:
+        """The classical bits: one ``uint64`` per member."""
+        out = np.zeros(self.members, dtype=np.uint64)
+        _lib.call("qsv_ensemble_bits_read", self.state._h, self.member_qubits, out.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return out
+
+    def set_bits(self, words) -> "TrajectoryEnsemble":
+        """One ``uint64`` per member, or ``None``: all bits 0."""
+        if words is None:
+            _lib.call("qsv_ensemble_bits_write", self.state._h, self.member_qubits, None)
+            return self
+        buf = np.array(words, dtype=np.uint64).reshape(-1)          # a copy of our own
+        if buf.shape[0] != self.members:
+            raise ValueError("one word per member")
+        _lib.call("qsv_ensemble_bits_write", self.state._h, self.member_qubits, buf.ctypes.data_as(C.POINTER(C.c_uint64)))
+        self._bits_source = buf          # the copy is enqueued, not waited for: the words stay alive until the next write
+        return self
+
+    def outcomes(self, count: int) -> np.ndarray:
+        """``[members, count]`` int8: the classical bits ``0 .. count - 1`` of every member."""
+        count = int(count)
+        if not 0 <= count <= 64:
+            raise ValueError("a member has 64 classical bits")
+        words = self.bits()
+        return ((words[:, None] >> np.arange(count, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.int8)
 
     def channel_log(self) -> tuple[np.ndarray, np.ndarray]:
         """``(branches[steps, members], probs[steps, members])`` since the last read, in call order; clears the log."""

@@ -283,6 +283,103 @@ class Channel(Gate):
         raise ValueError("State has wrong dimensions.")
 
 
+def measure_branch(w0: float, w1: float, u: float, forced=None) -> tuple[int, float, float]:
+    """The branch rule of a non-removing measurement, as the device spells it (``k_ens_measure_select``):
+    ``(outcome, probability, scale)``.  ``forced`` if it is 0 or 1, else the first ``s`` with ``w_0 + .. + w_s > u total``,
+    the last positive one if rounding leaves none; an outcome of weight 0 has probability 0 and scale 0."""
+    weights = (float(w0), float(w1))
+    total = weights[0] + weights[1]
+    pick = -1 if forced is None or int(forced) < 0 else int(forced)
+    if pick < 0:
+        target, run, last = float(u) * total, 0.0, -1
+        for j in (0, 1):
+            run += weights[j]
+            if weights[j] > 0.0:
+                last = j
+            if pick < 0 and run > target and weights[j] > 0.0:
+                pick = j
+        if pick < 0:
+            pick = 0 if last < 0 else last
+    alive = weights[pick] > 0.0 and total > 0.0
+    return pick, (weights[pick] / total if alive else 0.0), (float(np.sqrt(total / weights[pick])) if alive else 0.0)
+
+
+class Measure(Gate):
+    """Projective measurement of qubit ``index`` along the Bloch direction ``(theta, phi)`` that LEAVES the qubit in the
+    register: in the eigenvector it was found in (``conj(e_s)``, the partner of the reference's unconjugated projector), or
+    in ``|0>`` with ``reset=True``.  Eigenvectors as ``M.eigenvectors()``.  ``apply`` returns ``(state, outcome)`` like
+    ``M``, so ``Simulator.run`` collects the outcome and ``ClassicalControl`` works with it.  ``result=`` forces the
+    outcome; otherwise one uniform number is drawn from ``rng`` (default: the global ``np.random.random()``) and the
+    outcome is the first ``s`` with ``w_0 + .. + w_s > u (w_0 + w_1)``.  ``bit``: the classical bit of an ensemble member
+    that receives the outcome (default: the k-th measurement of a circuit writes bit k)."""
+
+    result_dtype = np.complex128
+
+    def __init__(self, index: int, theta: float = 0.0, phi: float = 0.0, *, result=None, reset: bool = False, bit=None, rng=None):
+        super().__init__([int(index)], None)
+        if result is not None and result not in (0, 1):
+            raise ValueError(f"Measurement results must be from 0 or 1 but {result} was given.")
+        if bit is not None and not 0 <= int(bit) <= 63:
+            raise ValueError("a member has the classical bits 0 .. 63")
+        self.theta, self.phi = theta, phi
+        self.result = result
+        self.reset = bool(reset)
+        self.bit = None if bit is None else int(bit)
+        self.rng = rng
+
+    def __repr__(self):
+        return f"Measure_{self.indices[0]}({self.theta}, {self.phi})"
+
+    def eigenvectors(self) -> tuple[np.ndarray, np.ndarray]:
+        from .dv_simulator.gates import M
+        return M.eigenvectors(self)
+
+    def kraus(self, outcome: int, scale: float = 1.0) -> np.ndarray:
+        """``K_s[r][c] = v_s[r] e_s[c]`` times ``scale``."""
+        e = np.asarray(self.eigenvectors()[int(outcome)], dtype=np.complex128).reshape(2)
+        v = np.array([1.0, 0.0], dtype=np.complex128) if self.reset else e.conj()
+        return np.outer(v, e) * scale
+
+    def _measure(self, dev, rng=None) -> int:
+        eigs = self.eigenvectors()
+        w0, w1 = dev.measure_probs(self.indices[0], *eigs)
+        u = 0.0
+        if rng is not None:                 # run_trajectories: one draw per measurement, forced or not, as the batched stream has it
+            u = float(rng.random())
+        elif self.result is None:
+            u = float(self.rng.random()) if self.rng is not None else float(np.random.random())
+        s, _, scale = measure_branch(w0, w1, u, self.result)
+        dev.apply_matrix(self.kraus(s, scale), self.indices)
+        return s
+
+    def apply(self, state):
+        if isinstance(state, DensityState):
+            raise ValueError("a density register does not branch on outcomes: Measure acts on kets")
+        if is_device_register(state):
+            return state, self._measure(state)
+        state = np.asarray(state)
+        if state.ndim != 1:
+            raise ValueError("Measure acts on kets")
+        dev = _borrow_register(state)
+        n = DeviceState.num_qubits.fget(dev)
+        try:
+            s = self._measure(dev)
+            out = dev.to_numpy()
+        except BaseException:
+            dev.close()
+            raise
+        _return_register(dev, n)
+        return out, s
+
+
+def _control_masks(control, measured_bits) -> tuple[list[int], list[int]]:
+    """The classical bits a ``ClassicalControl`` reads: its indices are positions in the result list."""
+    try:
+        return [measured_bits[i] for i in control._pos], [measured_bits[i] for i in control._neg]
+    except IndexError:
+        raise ValueError("a ClassicalControl refers to a measurement that has not happened yet") from None
+
+
 class NoiseModel:
     """Rules ``(which gates, which channel)``; ``insert`` puts a :class:`Channel` after every matching gate."""
 
@@ -340,15 +437,21 @@ def _run_trajectories_batched(circuit, initial_state, shots: int, terms, seed, d
     shots, batch = int(shots), int(batch)
     if batch < 1 or batch & (batch - 1):
         raise ValueError("batch must be a power of two")
+    from .dv_simulator.simulator import ClassicalControl
     circuit = list(circuit)
     for gate in circuit:
-        if not isinstance(gate, Channel) and (getattr(gate, "matrix", None) is None or gate.matrix.shape[0] != gate.matrix.shape[1]):
+        if isinstance(gate, (Channel, Measure, ClassicalControl)):
+            continue
+        if getattr(gate, "matrix", None) is None or gate.matrix.shape[0] != gate.matrix.shape[1]:
             raise ValueError("run_trajectories does not take measurements")
-    n_channels = sum(isinstance(gate, Channel) for gate in circuit)
-    # entry [s, c] is the c-th scalar the serial loop draws in shot s: the same stream, number for number
-    draws = np.random.default_rng(seed).random((shots, n_channels))
+    n_draws = sum(isinstance(gate, (Channel, Measure)) for gate in circuit)
+    n_measurements = sum(isinstance(gate, Measure) for gate in circuit)
+    # entry [s, c] is the c-th scalar the serial loop draws in shot s -- channels and measurements in circuit order: the
+    # same stream, number for number
+    draws = np.random.default_rng(seed).random((shots, n_draws))
     values = np.zeros(shots, dtype=np.float64)
     branches = []
+    results = []
     terms = list(terms)
     ens = TrajectoryEnsemble.from_ket(np.asarray(initial_state), batch, device) if shots else None
     try:
@@ -357,23 +460,31 @@ def _run_trajectories_batched(circuit, initial_state, shots: int, terms, seed, d
             if first:
                 ens.reset(np.asarray(initial_state))
             c = 0
+            measured = []                                          # the log step of every measurement
             for gate in circuit:
-                if isinstance(gate, Channel):
+                if isinstance(gate, (Channel, Measure)):
                     u = np.zeros(batch, dtype=np.float64)          # surplus members of the last chunk: u = 0, discarded below
                     u[:count] = draws[first:first + count, c]
-                    ens.apply_channel(gate.channel, gate.indices, u=u)
+                    if isinstance(gate, Channel):
+                        ens.apply_channel(gate.channel, gate.indices, u=u)
+                    else:
+                        ens.apply(gate, u=u)
+                        measured.append(c)
                     c += 1
                 else:
                     ens.apply(gate)
             values[first:first + count] = ens.expect_pauli_sum(terms)[:count]
             logged = ens.channel_log()[0]
-            branches += [np.ascontiguousarray(logged[:, m]) for m in range(count)]
+            channels = np.array([step for step in range(c) if step not in measured], dtype=np.intp)     # "branches": the channels', as in the serial loop
+            measured = np.array(measured, dtype=np.intp)
+            branches += [np.ascontiguousarray(logged[channels, m]) for m in range(count)]
+            results += [np.ascontiguousarray(logged[measured, m]).astype(np.int8) for m in range(count)]
     finally:
         if ens is not None:
             ens.close()
     mean = float(values.mean()) if shots else 0.0
     stderr = float(values.std(ddof=1) / np.sqrt(shots)) if shots > 1 else 0.0
-    return {"mean": mean, "stderr": stderr, "values": values, "branches": branches}
+    return {"mean": mean, "stderr": stderr, "values": values, "branches": branches, "results": results}
 
 
 def run_trajectories(circuit, initial_state, shots: int, *, terms=None, observable=None, seed=None, device: int = 0,
@@ -381,7 +492,11 @@ def run_trajectories(circuit, initial_state, shots: int, *, terms=None, observab
     """``shots`` quantum trajectories of ``circuit`` from the ket ``initial_state``; the value of a shot is
     ``<psi|H|psi>`` for the Pauli sum ``terms``, or ``observable(register)``.  Every shot runs on a fresh copy of one
     uploaded register; all draws come from ``np.random.default_rng(seed)`` in call order.  Returns ``mean``, ``stderr``,
-    ``values`` and the ``branches`` each shot logged.
+    ``values``, the ``branches`` each shot logged and ``results``, the outcomes of its measurements in order (int8).
+
+    A circuit may contain :class:`Measure` (the qubit stays; one draw, in its place in circuit order) and
+    ``ClassicalControl`` gates whose indices are positions in the shot's result list, as in ``Simulator.run``.  The
+    reference's removing ``M`` is refused.
 
     ``batch=B`` (a power of two) runs the shots ``B`` at a time as the members of one register
     (:class:`~quantum_computations_amd.ensemble.TrajectoryEnsemble`): one pass per gate for all of them.  The draws are
@@ -400,23 +515,33 @@ def run_trajectories(circuit, initial_state, shots: int, *, terms=None, observab
     work = start.copy()
     values = np.zeros(int(shots), dtype=np.float64)
     branches = []
+    results = []
     terms = list(terms) if terms is not None else None
+    from .dv_simulator.simulator import ClassicalControl
     try:
         for s in range(int(shots)):
             start.copy_into(work)
             state = work
+            outcomes = []
             for gate in circuit:
+                if isinstance(gate, ClassicalControl):
+                    if not gate.eval(outcomes):
+                        continue
+                    gate = gate.gate
                 if isinstance(gate, Channel):
                     state = state.apply_channel(gate.channel, gate.indices, rng=rng)
+                elif isinstance(gate, Measure):
+                    outcomes.append(gate._measure(state, rng))
                 else:
                     state = gate.apply(state)
                     if isinstance(state, tuple):
                         raise ValueError("run_trajectories does not take measurements")
             values[s] = float(np.real(state.expect_pauli_sum(terms) if terms is not None else observable(state)))
             branches.append(state.channel_log()[0])
+            results.append(np.array(outcomes, dtype=np.int8))
     finally:
         start.close()
         work.close()
     mean = float(values.mean()) if shots else 0.0
     stderr = float(values.std(ddof=1) / np.sqrt(shots)) if shots > 1 else 0.0
-    return {"mean": mean, "stderr": stderr, "values": values, "branches": branches}
+    return {"mean": mean, "stderr": stderr, "values": values, "branches": branches, "results": results}

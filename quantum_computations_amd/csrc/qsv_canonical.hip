@@ -36,9 +36,11 @@
 // the (device, stream) context; the call ends with a synchronisation of its stream, as the pool's contract requires.
 #include <cmath>
 
+#include "qsv_jacobi.h"
 #include "qsv_linalg.h"
 
 using namespace qsvl;
+using namespace qsv_jacobi;
 
 namespace {
 
@@ -47,11 +49,6 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 constexpr int SITE_MAX_BOND = QSV_SITE_MAX_BOND;
 constexpr int GRAM_MAX_CHUNKS = 32;       // workgroups along N: 128 partial sums at most
 constexpr int JACOBI_THREADS = 1024;
-
-__device__ __forceinline__ amp_t cmul(amp_t a, amp_t b) { return amp_t{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-__device__ __forceinline__ amp_t cmul_conj(amp_t a, amp_t b) {      // conj(a) * b
-    return amp_t{a.x * b.x + a.y * b.y, a.x * b.y - a.y * b.x};
-}
 
 // element (long index n, bond index c) of the stored site
 template <int SIDE>
@@ -192,7 +189,7 @@ __global__ __launch_bounds__(256) void k_site_apply(const amp_t *__restrict__ Q,
 }
 
 // One-sided Jacobi on the columns of the column-major l x l matrix A (copied to the work matrix W), one workgroup:
-// A J = U diag(sigma).  Column pairs follow a round-robin tournament (as k_small_svd of qsv_decomp.hip, which holds its
+// A J = U diag(sigma).  Column pairs follow a round-robin tournament (as k_small_svd of qsv_panel.hip, which holds its
 // matrices in LDS and stops at 64 columns; here they stay in global memory, where 128 x 128 fits the L2).  Output: Js,
 // the accumulated rotations with their columns sorted by decreasing sigma.  For a Hermitian positive semi-definite A
 // the columns of Js are its eigenvectors.  The caller polishes Js and forms A Js itself (see `jacobi` below).
@@ -211,7 +208,6 @@ __global__ __launch_bounds__(JACOBI_THREADS) void k_site_jacobi(const amp_t *A, 
     int team = 1;                       // threads per pair: a power of two, pairs * team <= blockDim.x, team <= 64
     while (team * 2 * pairs <= NT && team < 64) team *= 2;
     const int pair = t / team, member = t % team;
-    const double eps = 2.220446049250313e-16;
     for (int sweep = 0; sweep < 60; ++sweep) {
         __syncthreads();
         if (t == 0) rotated = 0;
@@ -219,55 +215,29 @@ __global__ __launch_bounds__(JACOBI_THREADS) void k_site_jacobi(const amp_t *A, 
             __syncthreads();
             int p = -1, q = -1;
             if (pair < pairs) {
-                if (pair == 0) {
-                    p = lp - 1;
-                    q = step;
-                } else {
-                    p = (step + pair) % (lp - 1);
-                    q = (step - pair + (lp - 1)) % (lp - 1);
-                }
-                if (p > q) {
-                    const int tmp = p;
-                    p = q;
-                    q = tmp;
-                }
+                const ColumnPair cp = tournament_pair(lp, step, pair);
+                p = cp.p;
+                q = cp.q;
             }
             const bool live = pair < pairs && q < l;     // the padding column of an odd l sits out
             double alpha = 0.0, beta = 0.0;
             amp_t gamma = {0.0, 0.0};
-            if (live) {
+            if (live)
                 for (int r = member; r < l; r += team) {
                     const amp_t x = W[p * l + r], y = W[q * l + r];
-                    alpha += x.x * x.x + x.y * x.y;
-                    beta += y.x * y.x + y.y * y.y;
-                    const amp_t g = cmul_conj(x, y);
-                    gamma.x += g.x;
-                    gamma.y += g.y;
+                    QSV_JACOBI_ACCUMULATE(alpha, beta, gamma, x, y);
                 }
-            }
-            for (int o = team / 2; o > 0; o >>= 1) {     // teams are aligned sub-groups of a wave
-                alpha += __shfl_xor(alpha, o, 64);
-                beta += __shfl_xor(beta, o, 64);
-                gamma.x += __shfl_xor(gamma.x, o, 64);
-                gamma.y += __shfl_xor(gamma.y, o, 64);
-            }
+            QSV_JACOBI_TEAM_REDUCE(alpha, beta, gamma, team);    // teams are aligned sub-groups of a wave
             // a column 1e-20 times shorter than its partner is rounding of the partner's own arithmetic (the null columns of
             // a rank-deficient Gram matrix): rotating it would only chase that rounding down to the underflow range,
             // where the phase below loses its unit modulus
             const double g = hypot(gamma.x, gamma.y);
             const double shorter = alpha < beta ? alpha : beta, longer = alpha < beta ? beta : alpha;
-            if (live && shorter > 1e-40 * longer && g > eps * sqrt(alpha) * sqrt(beta)) {
-                const amp_t phase = {gamma.x / g, -gamma.y / g};          // conj(gamma / |gamma|)
-                const double zeta = (beta - alpha) / (2.0 * g);
-                const double tt = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                const double c = 1.0 / sqrt(1.0 + tt * tt), sn = c * tt;
+            if (live && shorter > 1e-40 * longer && g > EPS * sqrt(alpha) * sqrt(beta)) {
+                const Rotation rot = rotation_for(alpha, beta, gamma, g);
                 for (int r = member; r < l; r += team) {
-                    const amp_t x = W[p * l + r], y = cmul(W[q * l + r], phase);
-                    W[p * l + r] = amp_t{c * x.x - sn * y.x, c * x.y - sn * y.y};
-                    W[q * l + r] = amp_t{sn * x.x + c * y.x, sn * x.y + c * y.y};
-                    const amp_t vx = J[p * l + r], vy = cmul(J[q * l + r], phase);
-                    J[p * l + r] = amp_t{c * vx.x - sn * vy.x, c * vx.y - sn * vy.y};
-                    J[q * l + r] = amp_t{sn * vx.x + c * vy.x, sn * vx.y + c * vy.y};
+                    rotate(W[p * l + r], W[q * l + r], rot);
+                    rotate(J[p * l + r], J[q * l + r], rot);
                 }
                 if (member == 0) rotated = 1;
             }
@@ -284,8 +254,8 @@ __global__ __launch_bounds__(JACOBI_THREADS) void k_site_jacobi(const amp_t *A, 
     }
     __syncthreads();
     for (int c = t; c < l; c += NT) {
-        int rank = 0;
-        for (int o = 0; o < l; ++o) rank += sigma[o] > sigma[c] || (sigma[o] == sigma[c] && o < c);
+        int rank;
+        QSV_JACOBI_RANK(rank, sigma, l, c);
         order[rank] = c;
     }
     __syncthreads();
@@ -302,7 +272,7 @@ __global__ __launch_bounds__(256) void k_site_small_gram(const amp_t *__restrict
     const unsigned j = e / w, i = e % w;
     double re = 0.0, im = 0.0;
     for (unsigned r = 0; r < w; ++r) {
-        const amp_t p = cmul_conj(J[i * w + r], J[j * w + r]);
+        const amp_t p = conj_mul(J[i * w + r], J[j * w + r]);
         re += p.x;
         im += p.y;
     }
@@ -363,7 +333,7 @@ __global__ __launch_bounds__(256) void k_site_small_product(const amp_t *__restr
     const unsigned j = e / w, r = e % w;
     double re = 0.0, im = 0.0;
     for (unsigned i = 0; i < w; ++i) {
-        const amp_t p = cmul(A[i * w + r], B[j * w + i]);
+        const amp_t p = plain_mul(A[i * w + r], B[j * w + i]);
         re += p.x;
         im += p.y;
     }

@@ -1,19 +1,18 @@
-// Decompositions of matrix-product-state updates: tensor_svd (cv_simulator/mps.py:52-97) on the GPU.
+// The exact split of a matrix-product-state update: tensor_svd (cv_simulator/mps.py:52-97) on the GPU.
 //
-//   qsvg_svd_split   exact branch: verified low-rank route -> rocSOLVER zgesdd (guarded) -> rocSOLVER zgesvd
-//   qsvg_rsvd_split  randomized branch (mps.py:5-50): hand-written f64 MFMA tall-skinny products, CholeskyQR3 panels
-//                    (blocked beyond 64 columns), one-workgroup Jacobi SVD; rocBLAS / rocSOLVER as the fallback
-//   qsvg_skinny_gemm the tall-skinny product on its own
+//   qsvg_svd_split   verified low-rank route (qsv_rsvd.hip) -> rocSOLVER zgesdd (guarded) -> one-sided Jacobi sweeps over
+//                    the whole matrix, seeded by zgesdd (jacobi_full_split) -> rocSOLVER zgesvd
+// (The randomized branch is qsv_rsvd.hip; the host-side rules of both are in qsv_split_rules.h.)
+#include <algorithm>
 #include <cstdio>
-#include <cstdlib>
-#include <string>
-#include <memory>
-#include <mutex>
 #include <vector>
 
+#include "qsv_jacobi.h"
 #include "qsv_linalg.h"
 
 using namespace qsvl;
+using namespace qsv_jacobi;
+using namespace qsv_split_rules;
 
 namespace {
 
@@ -43,627 +42,11 @@ __global__ __launch_bounds__(QSV_BLOCK) void k_scale_rows(const amp_t *__restric
     }
 }
 
-int blocks_for(uint64_t items) {
-    const uint64_t b = (items + QSV_BLOCK - 1) / QSV_BLOCK;
-    return static_cast<int>(b < 1 ? 1 : (b > 65536 ? 65536 : b));
-}
-
-// out (column-major n x m, ld n) = in (row-major n x m): LDS-tiled transpose of the element order
-__global__ __launch_bounds__(256) void k_to_column_major(const amp_t *__restrict__ in, amp_t *__restrict__ out,
-                                                        uint64_t n, uint64_t m) {
-    __shared__ amp_t tile[16][17];
-    const uint64_t tiles_m = (m + 15) / 16, tiles = tiles_m * ((n + 15) / 16);
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
-        const uint64_t r0 = (t / tiles_m) * 16, c0 = (t % tiles_m) * 16;
-        __syncthreads();
-        if (r0 + ty < n && c0 + tx < m) tile[ty][tx] = in[(r0 + ty) * m + c0 + tx];
-        __syncthreads();
-        if (c0 + ty < m && r0 + tx < n) out[(c0 + ty) * n + r0 + tx] = tile[tx][ty];
-    }
-}
-
-// out[a, b] (row-major A x B) = sqrt(s[by_row ? a : b]) * in[a * sa + b * sb]
-__global__ __launch_bounds__(QSV_BLOCK) void k_scale_strided(const amp_t *__restrict__ in, amp_t *__restrict__ out,
-                                                            uint64_t A, uint64_t B, uint64_t sa, uint64_t sb,
-                                                            const double *__restrict__ s, int by_row) {
-    const uint64_t total = A * B;
-    for (uint64_t o = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x; o < total;
-         o += static_cast<uint64_t>(gridDim.x) * blockDim.x) {
-        const uint64_t a = o / B, b = o % B;
-        const double w = sqrt(s[by_row ? a : b]);
-        const amp_t v = in[a * sa + b * sb];
-        out[o] = amp_t{w * v.x, w * v.y};
-    }
-}
-
-// ----------------------------------------------------------------------------------------------------
-// Fused tall-skinny kernels for the randomized split.  rocSOLVER's zgeqrf / zungqr / zgesvd on an (n x l) panel with
-// l = k + 10 <= 64 columns are hundreds of microsecond-sized launches each (profiles/r01_mps_kernel_stats.csv: half of
-// the GPU time of a split), and the range finder re-orthonormalises 15 times.  Any orthonormal basis of the same
-// subspace gives the same U S Vh, so the panels are orthonormalised by shifted CholeskyQR3 (Fukaya et al., SIAM J.
-// Sci. Comput. 42, 2020): three rounds of  G = Y^H Y,  R = chol(G + shift I),  Y <- Y R^-1 (a triangular solve per row)  -- three launches per
-// round, every one a single pass over the panel; the shift of the first round makes the factorisation succeed for
-// condition numbers up to 1/u, directions that are numerically absent are detected by their pivot in the later
-// rounds and dropped (zero columns; Householder QR would invent arbitrary complements there).  The (l x m) projection
-// B is never decomposed directly either: B^H is orthonormalised the same way (B^H = Qb Rb) and the l x l triangle Rb
-// goes through a one-sided Jacobi SVD in a single workgroup (high relative accuracy, no bidiagonalisation).
-// ----------------------------------------------------------------------------------------------------
-constexpr int LMAX = 64;            // widest panel the fused kernels take
-constexpr int PANEL_ROWS = 64;      // rows per LDS tile
-constexpr int PANEL_PITCH = PANEL_ROWS + 1;
-constexpr int GRAM_BLOCKS = 64;     // partial Gram matrices per panel (summed by one workgroup: keep it short)
-
-__device__ __forceinline__ amp_t conj_mul(amp_t a, amp_t b) {   // conj(a) * b
-    return amp_t{a.x * b.x + a.y * b.y, a.x * b.y - a.y * b.x};
-}
-__device__ __forceinline__ amp_t plain_mul(amp_t a, amp_t b) {
-    return amp_t{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x};
-}
-
-// partials[block][i * l + j] = sum over the block's rows of conj(Y[r, i]) * Y[r, j]   (Y column-major, ld n)
-// BANDS > 1: blockIdx.y takes one of BANDS slices of the entries (a short panel has too few row tiles to fill the chip,
-// and one workgroup per tile spends 16 entries x 64 rows of dependent FMAs per thread)
-template <int BANDS>
-__global__ __launch_bounds__(256) void k_panel_gram(const amp_t *__restrict__ Y, uint64_t n, int l,
-                                                   amp_t *__restrict__ partials, const int *__restrict__ settled) {
-    if (settled && *settled) return;     // the previous round found the panel orthonormal already
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    amp_t *tile = reinterpret_cast<amp_t *>(smem_raw);   // [l][PANEL_PITCH]
-    constexpr int PER_THREAD = LMAX * LMAX / 256 / BANDS;
-    const int t = threadIdx.x + 256 * PER_THREAD * blockIdx.y, entries = l * l;
-    amp_t acc[PER_THREAD];
-#pragma unroll
-    for (int k = 0; k < PER_THREAD; ++k) acc[k] = amp_t{0.0, 0.0};
-    for (uint64_t r0 = static_cast<uint64_t>(blockIdx.x) * PANEL_ROWS; r0 < n;
-         r0 += static_cast<uint64_t>(gridDim.x) * PANEL_ROWS) {
-        __syncthreads();
-        for (int idx = threadIdx.x; idx < l * PANEL_ROWS; idx += 256) {
-            const int c = idx / PANEL_ROWS, r = idx % PANEL_ROWS;
-            tile[c * PANEL_PITCH + r] = r0 + r < n ? Y[static_cast<uint64_t>(c) * n + r0 + r] : amp_t{0.0, 0.0};
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < PER_THREAD; ++k) {
-            const int e = t + 256 * k;
-            if (e < entries) {
-                const amp_t *ci = tile + (e / l) * PANEL_PITCH, *cj = tile + (e % l) * PANEL_PITCH;
-                amp_t a = acc[k];
-                for (int r = 0; r < PANEL_ROWS; ++r) {
-                    const amp_t p = conj_mul(ci[r], cj[r]);
-                    a.x += p.x;
-                    a.y += p.y;
-                }
-                acc[k] = a;
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < PER_THREAD; ++k) {
-        const int e = t + 256 * k;
-        if (e < entries) partials[static_cast<size_t>(blockIdx.x) * entries + e] = acc[k];
-    }
-}
-
-// partials[0][e] = partials[0][e] + partials[1][e] + ... in block order, one entry per thread with every load in flight:
-// inside k_panel_factor (one workgroup, 128 registers per thread) that sum was a chain of load batches from another XCD's
-// L2 -- 26 of the kernel's 80 us.
-__global__ __launch_bounds__(256) void k_gram_reduce(amp_t *__restrict__ partials, int nblocks, int entries,
-                                                    const int *__restrict__ skip) {
-    if (skip && *skip) return;
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= entries) return;
-    amp_t v[GRAM_BLOCKS];
-#pragma unroll
-    for (int b = 0; b < GRAM_BLOCKS; ++b)
-        if (b < nblocks) v[b] = partials[static_cast<size_t>(b) * entries + e];
-    amp_t s = {0.0, 0.0};
-#pragma unroll
-    for (int b = 0; b < GRAM_BLOCKS; ++b)
-        if (b < nblocks) {
-            s.x += v[b].x;
-            s.y += v[b].y;
-        }
-    partials[e] = s;
-}
-
-// (1024 threads: the sum of the 64 partial Gram matrices is a chain of load batches per thread -- 16 entries x 2 batches
-// with 256 threads, 130 us per launch on average and 29 % of the GPU time of the GKP Grover experiment; four times the
-// threads quarter the chain, and the trailing updates of the factorisation shrink with it)
-constexpr int FACTOR_THREADS = 1024;
-
-// One workgroup: G = sum of the partials (+ shift), upper Cholesky factor R with G = R^H R, its inverse, and the running
-// product r_total = R * r_prev.  first_round != 0 applies the CholeskyQR3 shift; otherwise pivots at rounding level
-// mark absent directions: their column of R^-1 is zeroed (the panel column becomes zero).
-__global__ __launch_bounds__(FACTOR_THREADS) void k_panel_factor(const amp_t *__restrict__ partials, int nblocks, int l,
-                                                     uint64_t rows, int first_round,
-                                                     const amp_t *__restrict__ r_prev, amp_t *__restrict__ r_total,
-                                                     amp_t *__restrict__ r_out, const int *__restrict__ skip,
-                                                     int *__restrict__ settled) {
-    // `settled` (read by the NEXT round as its `skip`): set when this round's Gram matrix is the identity to 1e-7 -- after
-    // this round's own normalisation the panel is orthonormal to rounding, so every kernel of the next round returns at once
-    if (skip && *skip) {
-        if (settled && threadIdx.x == 0) *settled = 1;
-        return;
-    }
-    __shared__ amp_t G[LMAX * LMAX];
-    __shared__ double deviation[FACTOR_THREADS / 64];
-    __shared__ amp_t Stage[LMAX * LMAX];
-    __shared__ double pivot_floor, shift;
-    __shared__ int absent[LMAX];
-    const int t = threadIdx.x, entries = l * l;
-    for (int e = t; e < entries; e += FACTOR_THREADS) {
-        amp_t s = {0.0, 0.0};
-        int b = 0;
-        for (; b + 16 <= nblocks; b += 16) {        // 16 independent loads in flight, summed in block order
-            amp_t v[16];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) v[k] = partials[static_cast<size_t>(b + k) * entries + e];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                s.x += v[k].x;
-                s.y += v[k].y;
-            }
-        }
-        for (; b < nblocks; ++b) {
-            const amp_t v = partials[static_cast<size_t>(b) * entries + e];
-            s.x += v.x;
-            s.y += v.y;
-        }
-        G[e] = s;
-    }
-    __syncthreads();
-    if (t == 0) {
-        double trace = 0.0, top = 0.0;
-        for (int j = 0; j < l; ++j) {
-            trace += G[j * l + j].x;
-            top = fmax(top, G[j * l + j].x);
-        }
-        const double u = 1.1102230246251565e-16;
-        shift = first_round ? 11.0 * (static_cast<double>(rows) * l + static_cast<double>(l) * (l + 1)) * u * trace : 0.0;
-        pivot_floor = first_round ? 0.0 : static_cast<double>(l) * u * top;
-    }
-    if (settled) {
-        double dev = first_round ? 1.0 : 0.0;      // the shifted round never settles anything
-        for (int e = t; e < entries; e += FACTOR_THREADS) {
-            const int i = e / l, k = e % l;
-            if (k >= i) dev = fmax(dev, fmax(fabs(G[e].x - (i == k ? 1.0 : 0.0)), fabs(G[e].y)));
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) dev = fmax(dev, __shfl_xor(dev, o, 64));
-        if ((t & 63) == 0) deviation[t >> 6] = dev;
-    }
-    __syncthreads();
-    if (settled && t == 0) {
-        double worst = 0.0;
-        for (int w = 0; w < FACTOR_THREADS / 64; ++w) worst = fmax(worst, deviation[w]);
-        *settled = worst < 1e-7;
-    }
-    // Blocked right-looking Cholesky, G = R^H R with R upper, 8 columns per step: the 8 x 8 diagonal block is factored by
-    // the first wave alone (a wavefront executes its LDS instructions in order: no workgroup barriers inside), then all
-    // threads solve the block row and update the trailing matrix -- 3 barriers per 8 columns instead of 3 per column.
-    constexpr int NB = 8;
-    for (int jb = 0; jb < l; jb += NB) {
-        const int nb = l - jb < NB ? l - jb : NB;
-        __syncthreads();
-        if (t < 64) {
-            // lane (i, k) = (t / 8, t % 8) keeps entry (i, k) of the block in a register; the pivot and the two factors of
-            // every update come from the lanes of row p by wave shuffles -- the same operations on the same values as a
-            // walk through LDS (which cost three LDS round trips per pivot: 3.2 us per block, a third of this kernel)
-            const int i = t / NB, k = t % NB;
-            const bool inside = i < nb && k < nb;
-            amp_t g = inside ? G[(jb + i) * l + jb + k] : amp_t{0.0, 0.0};
-            for (int p = 0; p < nb; ++p) {
-                const double pivot = __shfl(g.x, p * NB + p, 64) + shift;
-                const bool gone = !(pivot > pivot_floor);
-                const double rjj = gone ? 1.0 : sqrt(pivot);
-                if (i == p && k == p) g = amp_t{rjj, 0.0};
-                else if (i == p && k > p && inside) g = gone ? amp_t{0.0, 0.0} : amp_t{g.x / rjj, g.y / rjj};   // the rest of row p
-                if (t == 0) absent[jb + p] = gone;
-                const amp_t ri = {__shfl(g.x, p * NB + i, 64), __shfl(g.y, p * NB + i, 64)};      // R[p][i]
-                const amp_t rk = {__shfl(g.x, p * NB + k, 64), __shfl(g.y, p * NB + k, 64)};      // R[p][k]
-                if (i > p && k >= i && inside) {     // the block's remaining entries (i, k), p < i <= k < nb
-                    const amp_t pr = conj_mul(ri, rk);
-                    g.x -= pr.x;
-                    g.y -= pr.y;
-                }
-            }
-            if (inside && k >= i) G[(jb + i) * l + jb + k] = g;
-        }
-        __syncthreads();
-        // block row: R[jb + p][k] for k beyond the block, by forward substitution with the block's R^H
-        for (int k = jb + nb + t; k < l; k += FACTOR_THREADS) {
-            amp_t x[NB];
-#pragma unroll
-            for (int p = 0; p < NB; ++p) {
-                if (p < nb) {
-                    amp_t acc = G[(jb + p) * l + k];
-#pragma unroll
-                    for (int q = 0; q < NB; ++q)
-                        if (q < p) {
-                            const amp_t pr = conj_mul(G[(jb + q) * l + jb + p], x[q]);
-                            acc.x -= pr.x;
-                            acc.y -= pr.y;
-                        }
-                    const double d = G[(jb + p) * l + jb + p].x;
-                    x[p] = absent[jb + p] ? amp_t{0.0, 0.0} : amp_t{acc.x / d, acc.y / d};
-                    G[(jb + p) * l + k] = x[p];
-                } else {
-                    x[p] = amp_t{0.0, 0.0};
-                }
-            }
-        }
-        __syncthreads();
-        // trailing update G[i][k] -= sum_p conj(R[jb + p][i]) * R[jb + p][k] for jb + nb <= i <= k
-        const int first = jb + nb, width = l - first;
-        for (int e = t; e < width * width; e += FACTOR_THREADS) {
-            const int i = first + e / width, k = first + e % width;
-            if (k >= i) {
-                amp_t acc = G[i * l + k];
-#pragma unroll
-                for (int p = 0; p < NB; ++p)
-                    if (p < nb) {
-                        const amp_t pr = conj_mul(G[(jb + p) * l + i], G[(jb + p) * l + k]);
-                        acc.x -= pr.x;
-                        acc.y -= pr.y;
-                    }
-                G[i * l + k] = acc;
-            }
-        }
-    }
-    __syncthreads();
-    for (int e = t; e < entries; e += FACTOR_THREADS) {
-        const int i = e / l, k = e % l;
-        // the factor handed to k_panel_solve: upper triangle, diagonal 0 marks an absent direction
-        r_out[e] = (k < i || absent[i]) ? amp_t{0.0, 0.0} : G[e];
-        if (r_total) {
-            amp_t sum = {0.0, 0.0};
-            if (absent[i]) {
-                // the panel column of an absent direction is zero: its row of the factor must not reach the SVD
-            } else if (r_prev) {
-                for (int q = i; q <= k; ++q) {   // both factors are upper triangular
-                    const amp_t p = plain_mul(G[i * l + q], r_prev[q * l + k]);
-                    sum.x += p.x;
-                    sum.y += p.y;
-                }
-            } else if (k >= i) {
-                sum = G[e];
-            }
-            Stage[e] = sum;   // staged: r_total may alias r_prev
-        }
-    }
-    __syncthreads();
-    if (r_total)
-        for (int e = t; e < entries; e += FACTOR_THREADS) r_total[e] = Stage[e];
-}
-
-// Y <- Y R^-1 in place for the upper triangular R of k_panel_factor (row-major [i * l + j]): forward substitution per row,
-// q_j = (y_j - sum_{i<j} q_i R[i][j]) / R[j][j], q_j = 0 for absent directions (R[j][j] == 0), in blocks of 8 columns.
-// A workgroup stages 64 rows through LDS (coalesced both ways) together with a transposed copy of R; for every block the
-// contribution of the columns solved so far is subtracted by all four waves (wave w takes two of the block's columns, so
-// R[i][j] is an LDS broadcast), then the first wave finishes the 8 x 8 triangle for its 64 rows.
-__global__ __launch_bounds__(256) void k_panel_solve(amp_t *__restrict__ Y, uint64_t n, int l,
-                                                    const amp_t *__restrict__ R, const int *__restrict__ skip) {
-    if (skip && *skip) return;
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    amp_t *tile = reinterpret_cast<amp_t *>(smem_raw);   // [l][PANEL_PITCH]
-    amp_t *Rs = tile + l * PANEL_PITCH;                  // [l][l], column-major copy: Rs[j * l + i] = R[i][j]
-    constexpr int NB = 8;
-    const int t = threadIdx.x, r = t & 63, wave = t >> 6;
-    for (int e = t; e < l * l; e += 256) Rs[(e % l) * l + e / l] = R[e];
-    for (uint64_t r0 = static_cast<uint64_t>(blockIdx.x) * PANEL_ROWS; r0 < n;
-         r0 += static_cast<uint64_t>(gridDim.x) * PANEL_ROWS) {
-        const bool inside = r0 + r < n;
-        __syncthreads();
-        for (int c = wave; c < l; c += 4)
-            tile[c * PANEL_PITCH + r] = inside ? Y[static_cast<uint64_t>(c) * n + r0 + r] : amp_t{0.0, 0.0};
-        for (int jb = 0; jb < l; jb += NB) {
-            const int nb = l - jb < NB ? l - jb : NB;
-            __syncthreads();
-            // subtract what the solved columns 0 .. jb-1 contribute to this block: wave w owns columns jb + 2w, jb + 2w + 1
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int p = 2 * wave + h;
-                if (p < nb && jb > 0) {
-                    const int j = jb + p;
-                    const amp_t *col = Rs + j * l;
-                    amp_t acc = tile[j * PANEL_PITCH + r];
-                    int i = 0;
-                    for (; i + 4 <= jb; i += 4) {
-                        const amp_t p0 = plain_mul(tile[(i + 0) * PANEL_PITCH + r], col[i + 0]);
-                        const amp_t p1 = plain_mul(tile[(i + 1) * PANEL_PITCH + r], col[i + 1]);
-                        const amp_t p2 = plain_mul(tile[(i + 2) * PANEL_PITCH + r], col[i + 2]);
-                        const amp_t p3 = plain_mul(tile[(i + 3) * PANEL_PITCH + r], col[i + 3]);
-                        acc.x -= (p0.x + p1.x) + (p2.x + p3.x);
-                        acc.y -= (p0.y + p1.y) + (p2.y + p3.y);
-                    }
-                    for (; i < jb; ++i) {
-                        const amp_t pr = plain_mul(tile[i * PANEL_PITCH + r], col[i]);
-                        acc.x -= pr.x;
-                        acc.y -= pr.y;
-                    }
-                    tile[j * PANEL_PITCH + r] = acc;
-                }
-            }
-            __syncthreads();
-            if (wave == 0) {            // the block's own triangle, row by row of the tile: 28 products per row
-                amp_t q[NB];
-#pragma unroll
-                for (int p = 0; p < NB; ++p) {
-                    if (p < nb) {
-                        const int j = jb + p;
-                        const amp_t *col = Rs + j * l;
-                        amp_t acc = tile[j * PANEL_PITCH + r];
-#pragma unroll
-                        for (int u = 0; u < NB; ++u)
-                            if (u < p) {
-                                const amp_t pr = plain_mul(q[u], col[jb + u]);
-                                acc.x -= pr.x;
-                                acc.y -= pr.y;
-                            }
-                        const double d = col[j].x;
-                        q[p] = d != 0.0 ? amp_t{acc.x / d, acc.y / d} : amp_t{0.0, 0.0};
-                        tile[j * PANEL_PITCH + r] = q[p];
-                        if (inside) Y[static_cast<uint64_t>(j) * n + r0 + r] = q[p];
-                    } else {
-                        q[p] = amp_t{0.0, 0.0};
-                    }
-                }
-            }
-        }
-    }
-}
-
-// SVD of the l x l matrix R (row-major) by one-sided Jacobi in one workgroup: R V = U S.  Column pairs follow a
-// round-robin tournament (l/2 disjoint pairs per step, a few threads per pair); outputs are sorted by decreasing
-// singular value: U, V column-major (l x l), S (l doubles).
-// (Measured on the GKP Grover run, 64 x 64 factors: 830 us per launch with 256 threads -- 8 per column pair --, 800 with
-// 512 and 1060 with 1024: the 63 workgroup barriers per sweep cost more with every wave added.  QSV_SVD_THREADS switches.)
-constexpr int SVD_THREADS = 1024;     // launch bound; the launch uses small_svd_threads()
-static int small_svd_threads() {
-    static const int v = [] {
-        const char *e = std::getenv("QSV_SVD_THREADS");
-        const int n = e ? atoi(e) : 256;
-        return n == 512 || n == 1024 ? n : 256;
-    }();
-    return v;
-}
-__global__ __launch_bounds__(SVD_THREADS) void k_small_svd(const amp_t *__restrict__ R, int l, amp_t *__restrict__ U,
-                                                  double *__restrict__ S, amp_t *__restrict__ V) {
-    __shared__ amp_t W[LMAX * LMAX];    // working columns, column-major
-    __shared__ amp_t Vw[LMAX * LMAX];
-    __shared__ double sigma[LMAX];
-    __shared__ int order[LMAX];
-    __shared__ int rotated;
-    const int t = threadIdx.x, NT = blockDim.x;
-    for (int e = t; e < l * l; e += NT) {
-        const int c = e / l, r = e % l;
-        // the working matrix is R^H: its columns are the conjugated rows of the upper triangle, which the one-sided sweeps
-        // orthogonalise in fewer passes than the columns of R itself (the triangle's rows are already nearly graded);
-        // R^H = V S U^H, so the caller receives the factors with their roles exchanged
-        const amp_t v = R[c * l + r];
-        W[c * l + r] = amp_t{v.x, -v.y};
-        Vw[c * l + r] = amp_t{r == c ? 1.0 : 0.0, 0.0};
-    }
-    const int lp = (l + 1) & ~1, pairs = lp / 2;
-    int team = 1;                       // threads per pair: a power of two, pairs * team <= blockDim.x, team <= 64
-    while (team * 2 * pairs <= NT && team < 64) team *= 2;
-    const int pair = t / team, member = t % team;
-    const double eps = 2.220446049250313e-16;
-    for (int sweep = 0; sweep < 40; ++sweep) {
-        __syncthreads();
-        if (t == 0) rotated = 0;
-        for (int step = 0; step < lp - 1; ++step) {
-            __syncthreads();
-            int p = -1, q = -1;
-            if (pair < pairs) {
-                if (pair == 0) {
-                    p = lp - 1;
-                    q = step;
-                } else {
-                    p = (step + pair) % (lp - 1);
-                    q = (step - pair + (lp - 1)) % (lp - 1);
-                }
-                if (p > q) {
-                    const int tmp = p;
-                    p = q;
-                    q = tmp;
-                }
-            }
-            const bool live = pair < pairs && q < l;     // the padding column of an odd l sits out
-            double alpha = 0.0, beta = 0.0;
-            amp_t gamma = {0.0, 0.0};
-            if (live) {
-                for (int r = member; r < l; r += team) {
-                    const amp_t x = W[p * l + r], y = W[q * l + r];
-                    alpha += x.x * x.x + x.y * x.y;
-                    beta += y.x * y.x + y.y * y.y;
-                    const amp_t g = conj_mul(x, y);
-                    gamma.x += g.x;
-                    gamma.y += g.y;
-                }
-            }
-            for (int o = team / 2; o > 0; o >>= 1) {     // teams are aligned sub-groups of a wave
-                alpha += __shfl_xor(alpha, o, 64);
-                beta += __shfl_xor(beta, o, 64);
-                gamma.x += __shfl_xor(gamma.x, o, 64);
-                gamma.y += __shfl_xor(gamma.y, o, 64);
-            }
-            const double g2 = gamma.x * gamma.x + gamma.y * gamma.y;
-            if (live && g2 > eps * eps * alpha * beta && g2 > 0.0) {
-                const double g = sqrt(g2);
-                const amp_t phase = {gamma.x / g, -gamma.y / g};          // conj(gamma / |gamma|)
-                const double zeta = (beta - alpha) / (2.0 * g);
-                const double tt = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                const double c = 1.0 / sqrt(1.0 + tt * tt), sn = c * tt;
-                for (int r = member; r < l; r += team) {
-                    const amp_t x = W[p * l + r], y = plain_mul(W[q * l + r], phase);
-                    W[p * l + r] = amp_t{c * x.x - sn * y.x, c * x.y - sn * y.y};
-                    W[q * l + r] = amp_t{sn * x.x + c * y.x, sn * x.y + c * y.y};
-                    const amp_t vx = Vw[p * l + r], vy = plain_mul(Vw[q * l + r], phase);
-                    Vw[p * l + r] = amp_t{c * vx.x - sn * vy.x, c * vx.y - sn * vy.y};
-                    Vw[q * l + r] = amp_t{sn * vx.x + c * vy.x, sn * vx.y + c * vy.y};
-                }
-                if (member == 0) rotated = 1;
-            }
-        }
-        __syncthreads();
-        if (!rotated) break;
-    }
-    __syncthreads();
-    for (int c = t; c < l; c += NT) {
-        double s = 0.0;
-        for (int r = 0; r < l; ++r) s += W[c * l + r].x * W[c * l + r].x + W[c * l + r].y * W[c * l + r].y;
-        sigma[c] = sqrt(s);
-    }
-    __syncthreads();
-    if (t == 0) {                       // ranks by decreasing singular value (l <= 64)
-        for (int c = 0; c < l; ++c) {
-            int rank = 0;
-            for (int o = 0; o < l; ++o) rank += sigma[o] > sigma[c] || (sigma[o] == sigma[c] && o < c);
-            order[rank] = c;
-        }
-    }
-    __syncthreads();
-    for (int e = t; e < l * l; e += NT) {
-        const int rank = e / l, r = e % l, c = order[rank];
-        const double s = sigma[c];
-        const amp_t w = W[c * l + r];
-        U[rank * l + r] = s > 0.0 ? amp_t{w.x / s, w.y / s} : amp_t{0.0, 0.0};
-        V[rank * l + r] = Vw[c * l + r];
-    }
-    for (int rank = t; rank < l; rank += NT) S[rank] = sigma[order[rank]];
-}
-
-// ---- the same one-sided Jacobi SVD for factors wider than 64 columns (up to WIDE_FACTOR): the working matrices live in
-// global memory (L2-resident) and every tournament step is one launch with a wave per column pair ------------------------
-constexpr int WIDE_FACTOR = 256;
-
-// W (column-major l x l) = R^H for the row-major upper triangular R; V = identity
-__global__ __launch_bounds__(256) void k_jacobi_init(const amp_t *__restrict__ R, int l, amp_t *__restrict__ W,
-                                                    amp_t *__restrict__ V) {
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < l * l; e += gridDim.x * 256) {
-        const int c = e / l, r = e % l;
-        const amp_t v = R[c * l + r];
-        W[e] = amp_t{v.x, -v.y};
-        V[e] = amp_t{r == c ? 1.0 : 0.0, 0.0};
-    }
-}
-
-// one step of the round-robin tournament: block b rotates its pair of columns of W (and of V) if they are not orthogonal
-__global__ __launch_bounds__(64) void k_jacobi_step(amp_t *__restrict__ W, amp_t *__restrict__ V, int l, int lp, int step,
-                                                   int *__restrict__ rotated) {
-    const int pair = blockIdx.x, lane = threadIdx.x;
-    int p, q;
-    if (pair == 0) {
-        p = lp - 1;
-        q = step;
-    } else {
-        p = (step + pair) % (lp - 1);
-        q = (step - pair + (lp - 1)) % (lp - 1);
-    }
-    if (p > q) {
-        const int tmp = p;
-        p = q;
-        q = tmp;
-    }
-    if (q >= l) return;       // the padding column of an odd l sits out
-    amp_t *wp = W + static_cast<size_t>(p) * l, *wq = W + static_cast<size_t>(q) * l;
-    double alpha = 0.0, beta = 0.0;
-    amp_t gamma = {0.0, 0.0};
-    for (int r = lane; r < l; r += 64) {
-        const amp_t x = wp[r], y = wq[r];
-        alpha += x.x * x.x + x.y * x.y;
-        beta += y.x * y.x + y.y * y.y;
-        const amp_t g = conj_mul(x, y);
-        gamma.x += g.x;
-        gamma.y += g.y;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        alpha += __shfl_xor(alpha, o, 64);
-        beta += __shfl_xor(beta, o, 64);
-        gamma.x += __shfl_xor(gamma.x, o, 64);
-        gamma.y += __shfl_xor(gamma.y, o, 64);
-    }
-    const double eps = 2.220446049250313e-16, g2 = gamma.x * gamma.x + gamma.y * gamma.y;
-    if (!(g2 > eps * eps * alpha * beta) || !(g2 > 0.0)) return;
-    const double g = sqrt(g2);
-    const amp_t phase = {gamma.x / g, -gamma.y / g};
-    const double zeta = (beta - alpha) / (2.0 * g);
-    const double tt = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-    const double c = 1.0 / sqrt(1.0 + tt * tt), sn = c * tt;
-    amp_t *vp = V + static_cast<size_t>(p) * l, *vq = V + static_cast<size_t>(q) * l;
-    for (int r = lane; r < l; r += 64) {
-        const amp_t x = wp[r], y = plain_mul(wq[r], phase);
-        wp[r] = amp_t{c * x.x - sn * y.x, c * x.y - sn * y.y};
-        wq[r] = amp_t{sn * x.x + c * y.x, sn * x.y + c * y.y};
-        const amp_t vx = vp[r], vy = plain_mul(vq[r], phase);
-        vp[r] = amp_t{c * vx.x - sn * vy.x, c * vx.y - sn * vy.y};
-        vq[r] = amp_t{sn * vx.x + c * vy.x, sn * vx.y + c * vy.y};
-    }
-    if (lane == 0) *rotated = 1;
-}
-
-// singular values = column norms of W, sorted decreasingly; left = W / sigma, right = V in that order (column-major)
-__global__ __launch_bounds__(256) void k_jacobi_finish(const amp_t *__restrict__ W, const amp_t *__restrict__ V, int l,
-                                                      amp_t *__restrict__ left, double *__restrict__ S,
-                                                      amp_t *__restrict__ right) {
-    __shared__ double sigma[WIDE_FACTOR];
-    __shared__ int order[WIDE_FACTOR];
-    const int t = threadIdx.x;
-    for (int c = t; c < l; c += 256) {
-        double s = 0.0;
-        for (int r = 0; r < l; ++r) {
-            const amp_t w = W[static_cast<size_t>(c) * l + r];
-            s += w.x * w.x + w.y * w.y;
-        }
-        sigma[c] = sqrt(s);
-    }
-    __syncthreads();
-    for (int c = t; c < l; c += 256) {
-        int rank = 0;
-        for (int o = 0; o < l; ++o) rank += sigma[o] > sigma[c] || (sigma[o] == sigma[c] && o < c);
-        order[rank] = c;
-    }
-    __syncthreads();
-    for (int e = t; e < l * l; e += 256) {
-        const int rank = e / l, r = e % l, c = order[rank];
-        const double s = sigma[c];
-        const amp_t w = W[static_cast<size_t>(c) * l + r];
-        left[e] = s > 0.0 ? amp_t{w.x / s, w.y / s} : amp_t{0.0, 0.0};
-        right[e] = V[static_cast<size_t>(c) * l + r];
-    }
-    for (int rank = t; rank < l; rank += 256) S[rank] = sigma[order[rank]];
-}
-
-// R = U_r S V_r^H for the row-major l x l triangle R, 64 < l <= WIDE_FACTOR.  W, V: 2 l^2 amplitudes of scratch; `flag`
-// one device int.  (The kernels decompose R^H = V_r S U_r^H, hence the exchanged output arguments.)
-int wide_factor_svd(hipStream_t stream, const amp_t *R, int l, amp_t *W, amp_t *V, amp_t *Ur, double *S, amp_t *Vr,
-                    int *flag) {
-    hipLaunchKernelGGL(k_jacobi_init, dim3(64), dim3(256), 0, stream, R, l, W, V);
-    const int lp = (l + 1) & ~1;
-    for (int sweep = 0; sweep < 40; ++sweep) {
-        QSV_HIP(hipMemsetAsync(flag, 0, sizeof(int), stream));
-        for (int step = 0; step < lp - 1; ++step)
-            hipLaunchKernelGGL(k_jacobi_step, dim3(lp / 2), dim3(64), 0, stream, W, V, l, lp, step, flag);
-        int rotated = 0;
-        QSV_HIP(hipMemcpyAsync(&rotated, flag, sizeof(int), hipMemcpyDeviceToHost, stream));
-        QSV_HIP(hipStreamSynchronize(stream));
-        if (!rotated) break;
-    }
-    hipLaunchKernelGGL(k_jacobi_finish, dim3(1), dim3(256), 0, stream, W, V, l, Vr, S, Ur);
-    QSV_HIP(hipGetLastError());
-    return QSV_OK;
-}
-
 // ---- one-sided Jacobi SVD of a whole matrix: the exact split of a theta that is NOT numerically low-rank ---------------
 // X (column-major L x k, k <= L, k <= JACOBI_MAX_COLUMNS) holds the k shorter vectors of theta; X J = Q S with J unitary
 // (k x k) and orthogonal columns Q S.  A workgroup per column pair and launch per tournament step, as the wide factor above,
 // but with 256 threads per pair (columns are thousands of entries long) -- rocSOLVER's zgesvd needs 1.35 s for a
 // 1200 x 1200 matrix of rank 700 and 5 s at 2000 x 2000 (bdsqr launch storms); these sweeps take a fifth of that.
-constexpr int JACOBI_MAX_COLUMNS = 2048;
-
 // squared norms of the k columns of an L x k matrix, element (r, c) at src[r * stride_row + c * stride_col]
 __global__ __launch_bounds__(256) void k_column_norms(const amp_t *__restrict__ src, uint64_t stride_row, uint64_t stride_col,
                                                      uint64_t L, double *__restrict__ norms) {
@@ -711,38 +94,17 @@ __global__ __launch_bounds__(256) void k_jacobi_pair(amp_t *__restrict__ W, amp_
                                                     int step, double floor2, int *__restrict__ rotated) {
     __shared__ double red[4][4];
     const int pair = blockIdx.x, t = threadIdx.x;
-    int p, q;
-    if (pair == 0) {
-        p = kp - 1;
-        q = step;
-    } else {
-        p = (step + pair) % (kp - 1);
-        q = (step - pair + (kp - 1)) % (kp - 1);
-    }
-    if (p > q) {
-        const int tmp = p;
-        p = q;
-        q = tmp;
-    }
+    const ColumnPair cp = tournament_pair(kp, step, pair);
+    const int p = cp.p, q = cp.q;
     if (q >= k) return;       // the padding column of an odd k sits out
     amp_t *wp = W + static_cast<uint64_t>(p) * L, *wq = W + static_cast<uint64_t>(q) * L;
     double alpha = 0.0, beta = 0.0;
     amp_t gamma = {0.0, 0.0};
     for (uint64_t r = t; r < L; r += 256) {
         const amp_t x = wp[r], y = wq[r];
-        alpha += x.x * x.x + x.y * x.y;
-        beta += y.x * y.x + y.y * y.y;
-        const amp_t g = conj_mul(x, y);
-        gamma.x += g.x;
-        gamma.y += g.y;
+        QSV_JACOBI_ACCUMULATE(alpha, beta, gamma, x, y);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        alpha += __shfl_xor(alpha, o, 64);
-        beta += __shfl_xor(beta, o, 64);
-        gamma.x += __shfl_xor(gamma.x, o, 64);
-        gamma.y += __shfl_xor(gamma.y, o, 64);
-    }
+    QSV_JACOBI_TEAM_REDUCE(alpha, beta, gamma, 64);
     if ((t & 63) == 0) {
         red[t >> 6][0] = alpha;
         red[t >> 6][1] = beta;
@@ -756,25 +118,13 @@ __global__ __launch_bounds__(256) void k_jacobi_pair(amp_t *__restrict__ W, amp_
     gamma.y = (red[0][3] + red[1][3]) + (red[2][3] + red[3][3]);
     // orthogonal to the rounding level of an L-term inner product, sqrt(L) eps (LAPACK's zgesvj uses the same tolerance):
     // below it the computed gamma is noise and the sweeps would never end
-    const double eps = 2.220446049250313e-16, g2 = gamma.x * gamma.x + gamma.y * gamma.y;
-    if (!(g2 > static_cast<double>(L) * eps * eps * alpha * beta) || !(g2 > 0.0)) return;      // every thread holds the same sums
+    const double g2 = gamma.x * gamma.x + gamma.y * gamma.y;
+    if (!(g2 > static_cast<double>(L) * EPS * EPS * alpha * beta) || !(g2 > 0.0)) return;      // every thread holds the same sums
     if (!(alpha > floor2) || !(beta > floor2)) return;
-    const double g = sqrt(g2);
-    const amp_t phase = {gamma.x / g, -gamma.y / g};
-    const double zeta = (beta - alpha) / (2.0 * g);
-    const double tt = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-    const double c = 1.0 / sqrt(1.0 + tt * tt), sn = c * tt;
-    for (uint64_t r = t; r < L; r += 256) {
-        const amp_t x = wp[r], y = plain_mul(wq[r], phase);
-        wp[r] = amp_t{c * x.x - sn * y.x, c * x.y - sn * y.y};
-        wq[r] = amp_t{sn * x.x + c * y.x, sn * x.y + c * y.y};
-    }
+    const Rotation rot = rotation_for(alpha, beta, gamma, sqrt(g2));
+    for (uint64_t r = t; r < L; r += 256) rotate(wp[r], wq[r], rot);
     amp_t *jp = J + static_cast<uint64_t>(p) * k, *jq = J + static_cast<uint64_t>(q) * k;
-    for (int r = t; r < k; r += 256) {
-        const amp_t x = jp[r], y = plain_mul(jq[r], phase);
-        jp[r] = amp_t{c * x.x - sn * y.x, c * x.y - sn * y.y};
-        jq[r] = amp_t{sn * x.x + c * y.x, sn * x.y + c * y.y};
-    }
+    for (int r = t; r < k; r += 256) rotate(jp[r], jq[r], rot);
     if (t == 0) *rotated = 1;
 }
 
@@ -804,55 +154,6 @@ __global__ __launch_bounds__(256) void k_jacobi_factors(const amp_t *__restrict_
         }
     }
 }
-
-// out[a, b] (row-major A x B) = sqrt(s[by_row ? a : b]) * (conj ? conj(in[...]) : in[a * sa + b * sb])
-__global__ __launch_bounds__(QSV_BLOCK) void k_scale_strided_conj(const amp_t *__restrict__ in, amp_t *__restrict__ out,
-                                                                 uint64_t A, uint64_t B, uint64_t sa, uint64_t sb,
-                                                                 const double *__restrict__ s, int by_row,
-                                                                 int conjugate) {
-    const uint64_t total = A * B;
-    for (uint64_t o = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x; o < total;
-         o += static_cast<uint64_t>(gridDim.x) * blockDim.x) {
-        const uint64_t a = o / B, b = o % B;
-        const double w = sqrt(s[by_row ? a : b]);
-        const amp_t v = in[a * sa + b * sb];
-        out[o] = amp_t{w * v.x, conjugate ? -w * v.y : w * v.y};
-    }
-}
-
-// The reference's truncation rule (mps.py:83-86) on singular values sorted in decreasing order.
-double allowed_error(const std::vector<double> &sv, double abs_err, double rel_err) {
-    double total = 0.0;
-    for (double v : sv) total += v;
-    double allowed = total * rel_err;
-    if (abs_err > allowed) allowed = abs_err;
-    return allowed < 0.0 ? 0.0 : allowed;
-}
-
-uint64_t kept_rank_for(const std::vector<double> &sv, int64_t max_bond_dim, double allowed) {
-    uint64_t r = 0;
-    double tail = 0.0;
-    for (size_t i = sv.size(); i-- > 0;) {
-        tail += sv[i];
-        if (tail > allowed) ++r;
-    }
-    if (max_bond_dim >= 0 && r > static_cast<uint64_t>(max_bond_dim)) r = static_cast<uint64_t>(max_bond_dim);
-    if (r > sv.size()) r = sv.size();
-    return r;
-}
-
-uint64_t kept_rank(const std::vector<double> &sv, int64_t max_bond_dim, double abs_err, double rel_err) {
-    return kept_rank_for(sv, max_bond_dim, allowed_error(sv, abs_err, rel_err));
-}
-
-}  // namespace
-
-constexpr int QSV_UNDECIDED = 2;
-bool fused_panels_enabled();
-int try_verified_low_rank(RocblasApi &a, rocblas_handle h, StreamContext &ctx, const amp_t *theta, uint64_t rows,
-                          uint64_t cols, int64_t max_bond_dim, double abs_err, double rel_err, amp_t *m1, amp_t *m2,
-                          uint64_t capacity, uint64_t *rank_out, std::vector<double> *values,
-                          double *frobenius_squared_out = nullptr);
 
 // The exact split by one-sided Jacobi sweeps over the whole matrix (k_jacobi_pair): theta is left untouched;
 // QSV_UNDECIDED when the matrix is outside what the sweeps take or they did not converge (the library SVD decides then).
@@ -894,20 +195,17 @@ int jacobi_full_split(RocblasApi &a, rocblas_handle h, hipStream_t stream, const
     const bool conj_work = seeded && !wide;
     int rc;
     if (seeded) {
-        const rocblas_double_complex one{1.0, 0.0}, zero{0.0, 0.0};
-        auto Z = [](const amp_t *p) { return reinterpret_cast<const rocblas_double_complex *>(p); };
         const rocblas_int Li = static_cast<rocblas_int>(L);
-        rocblas_status st;
+        const rocblas_operation N = rocblas_operation_none, Cc = rocblas_operation_conjugate_transpose;
+        bool ok;
         if (wide) {
             hipLaunchKernelGGL(k_jacobi_seed, dim3(1024), dim3(256), 0, stream, seed_vh, J, k);
-            st = a.zgemm(h, rocblas_operation_none, rocblas_operation_conjugate_transpose, Li, k, k, &one, Z(theta), Li, 0,
-                         Z(seed_vh), k, 0, &zero, reinterpret_cast<rocblas_double_complex *>(W), Li, 0, 1);
+            ok = zgemm(a, h, N, Cc, Li, k, k, theta, Li, seed_vh, k, W, Li);
         } else {
             QSV_HIP(hipMemcpyAsync(J, seed_u, sizeof(amp_t) * k64 * k64, hipMemcpyDeviceToDevice, stream));
-            st = a.zgemm(h, rocblas_operation_conjugate_transpose, rocblas_operation_none, Li, k, k, &one, Z(theta), k, 0,
-                         Z(seed_u), k, 0, &zero, reinterpret_cast<rocblas_double_complex *>(W), Li, 0, 1);
+            ok = zgemm(a, h, Cc, N, Li, k, k, theta, k, seed_u, k, W, Li);
         }
-        if (st != rocblas_status_success) return QSV_UNDECIDED;
+        if (!ok) return QSV_UNDECIDED;
         QSV_HIP(hipGetLastError());
     } else {
         // element (x, c) of X: wide theta -> theta[c, x] (buffer read column-major with ld cols); tall theta -> theta[x, c];
@@ -919,19 +217,17 @@ int jacobi_full_split(RocblasApi &a, rocblas_handle h, hipStream_t stream, const
         if (rc) return rc;
         hipLaunchKernelGGL(k_jacobi_gather, dim3(1024), dim3(256), 0, stream, theta, stride_row, stride_col, order, W, J, L, k);
     }
-    // Columns of norm below 4 sqrt(L) eps ||X||_F are rounding dust (the product X J itself is only that accurate): their
-    // singular values are numerically zero -- LAPACK returns noise of that size for them too -- and mutually orthogonal
-    // dust is not worth sweeps that never end (rotations among the large columns keep re-randomising it).  X = W J^H holds
-    // whether or not they are orthogonal, so the product of the two factors is unaffected.
+    // Columns below the dust floor (dust_floor2): their singular values are numerically zero -- LAPACK returns noise of that
+    // size for them too -- and mutually orthogonal dust is not worth sweeps that never end (rotations among the large columns
+    // keep re-randomising it).  X = W J^H holds whether or not they are orthogonal, so the product of the two factors is unaffected.
     hipLaunchKernelGGL(k_column_norms, dim3(k), dim3(256), 0, stream, W, static_cast<uint64_t>(1), L, L, norms);
     QSV_HIP(hipGetLastError());
     QSV_HIP(hipMemcpyAsync(host_norms.data(), norms, sizeof(double) * k, hipMemcpyDeviceToHost, stream));
     QSV_HIP(hipStreamSynchronize(stream));
     double frobenius2 = 0.0;
     for (double v : host_norms) frobenius2 += v;
-    const double floor2 = 16.0 * static_cast<double>(L) * 4.930380657631324e-32 * frobenius2;
+    const double floor2 = dust_floor2(L, frobenius2);
     bool converged = false;
-    static const bool trace = std::getenv("QSV_TRACE_SPLIT") != nullptr;
     const int max_sweeps = seeded ? 24 : 40;       // a seeded run that needs more is not being helped by its seed
     int sweeps = 0;
     for (; sweeps < max_sweeps && !converged; ++sweeps) {
@@ -944,7 +240,7 @@ int jacobi_full_split(RocblasApi &a, rocblas_handle h, hipStream_t stream, const
         QSV_HIP(hipStreamSynchronize(stream));
         converged = !rotated;
     }
-    if (trace)
+    if (split_options().trace)
         fprintf(stderr, "[qsv split] %llu x %llu: %sJacobi sweeps over the whole matrix: %d%s\n",
                 static_cast<unsigned long long>(rows), static_cast<unsigned long long>(cols), seeded ? "seeded " : "", sweeps,
                 converged ? "" : " (not converged)");
@@ -953,22 +249,14 @@ int jacobi_full_split(RocblasApi &a, rocblas_handle h, hipStream_t stream, const
     QSV_HIP(hipGetLastError());
     rc = sorted_by_norm();
     if (rc) return rc;
-    std::vector<double> sv(k);
-    for (int c = 0; c < k; ++c) sv[c] = sqrt(host_norms[host_order[c]]);
-    // The norm of a dust column is the rounding error of the product X J (hundreds of eps sigma_max), not a singular value;
-    // a backward-stable SVD reports eps sigma_max-sized values there, and a tail of 500 such columns must not reach a tight
-    // truncation threshold.  Dust is relabelled to at most eps sigma_max: if the rule keeps such a column anyway
-    // (rel_err = abs_err = 0) its outer product W[:, c] J[:, c]^H enters the factors unchanged -- sigma only decides how
-    // the two factors share it.
+    // (dust is relabelled -- values_from_norms --: if the rule keeps such a column anyway (rel_err = abs_err = 0) its outer
+    // product W[:, c] J[:, c]^H enters the factors unchanged -- sigma only decides how the two factors share it)
+    std::vector<double> sorted2(k);
+    for (int c = 0; c < k; ++c) sorted2[c] = host_norms[host_order[c]];
     bool relabelled = false;
-    for (int c = 0; c < k; ++c)
-        if (!(host_norms[host_order[c]] > floor2)) {
-            const double label = std::min(sv[c], 2.220446049250313e-16 * sv[0]);
-            sv[c] = label;
-            host_norms[host_order[c]] = label * label;
-            relabelled = true;
-        }
+    const std::vector<double> sv = values_from_norms(sorted2, floor2, &relabelled);
     if (relabelled) {
+        for (int c = 0; c < k; ++c) host_norms[host_order[c]] = sorted2[c];
         QSV_HIP(hipMemcpyAsync(norms, host_norms.data(), sizeof(double) * k, hipMemcpyHostToDevice, stream));
         QSV_HIP(hipStreamSynchronize(stream));
     }
@@ -990,6 +278,8 @@ int jacobi_full_split(RocblasApi &a, rocblas_handle h, hipStream_t stream, const
     return QSV_OK;
 }
 
+}  // namespace
+
 // tensor_svd (cv_simulator/mps.py:52-97) of a row-major (rows x cols) device matrix:
 //   theta = U S Vh,  r from the truncation rule,  m1 = U[:, :r] sqrt(S[:r]),  m2 = sqrt(S[:r]) Vh[:r, :].
 // rocSOLVER is column-major, so it factors theta^T = U' S V'^H (cols x rows); then U = (V'^H)^T and Vh = U'^T, i.e.
@@ -1007,20 +297,11 @@ int qsvg_svd_split(int device, hipStream_t stream, amp_t *theta, uint64_t rows, 
     if (!h) return rc;
     if (!a.zgesvd) return qsv_fail(QSV_EHIP, "rocSOLVER could not be loaded (librocsolver.so.0): no SVD available");
     const uint64_t k = rows < cols ? rows : cols;
-    static const bool shortcuts_enabled = [] {
-        const char *v = std::getenv("QSV_SVD");
-        return !(v && std::string(v) == "exact");
-    }();
+    const SplitOptions &opt = split_options();
     double frobenius_squared = -1.0;      // filled in by the verified route when it gets far enough to measure it
-    if (shortcuts_enabled && fused_panels_enabled()) {     // any tolerance: the route verifies itself (or declines)
-        std::vector<double> values;
+    if (opt.shortcuts && opt.fused_panels) {     // any tolerance: the route verifies itself (or declines)
         const int fast = try_verified_low_rank(a, h, *ctx, theta, rows, cols, max_bond_dim, abs_err, rel_err, m1, m2, capacity,
-                                               rank_out, s_host ? &values : nullptr, &frobenius_squared);
-        if (fast == QSV_OK) {
-            if (s_host)
-                for (uint64_t i = 0; i < k; ++i) s_host[i] = values[i];
-            return QSV_OK;
-        }
+                                               rank_out, s_host, k, &frobenius_squared);
         if (fast != QSV_UNDECIDED) return fast;
     }
     DeviceBuffers buf;
@@ -1035,57 +316,29 @@ int qsvg_svd_split(int device, hipStream_t stream, amp_t *theta, uint64_t rows, 
     std::vector<double> sv(k);
     rocblas_int info = 0;
     const rocblas_int ci = static_cast<rocblas_int>(cols), ri = static_cast<rocblas_int>(rows), ki = static_cast<rocblas_int>(k);
-    auto Zp = [](amp_t *p) { return reinterpret_cast<rocblas_double_complex *>(p); };
     auto fetch_values = [&]() -> int {
         QSV_HIP(hipMemcpyAsync(sv.data(), dS, sizeof(double) * k, hipMemcpyDeviceToHost, stream));
         QSV_HIP(hipMemcpyAsync(&info, dinfo, sizeof(info), hipMemcpyDeviceToHost, stream));
         QSV_HIP(hipStreamSynchronize(stream));
         return QSV_OK;
     };
-    // rocSOLVER's zgesvd needs seconds on the graded spectra of these matrices (5 s at 2000 x 2000); its zgesdd goes
-    // through the eigenvectors of A^H A and takes 0.17 s, but that route cannot resolve singular values below
-    // ~1e-8 sigma_max.  It is used when the truncation cannot notice: the allowed error must exceed the possible
-    // garbage in the tail sum by a wide margin, the kept rank must be the same at both ends of that margin, and every
-    // kept value must be well above the floor; otherwise theta is restored and zgesvd decides.
+    // rocSOLVER's zgesvd needs seconds on the graded spectra of these matrices (5 s at 2000 x 2000); its zgesdd takes 0.17 s
+    // and is used when the truncation cannot notice its floor (gram_values_decide); otherwise theta is restored, and
+    // zgesdd's factors seed the Jacobi sweeps where those fit (exact_route)
     bool decided = false;
-    static const bool gram_route_enabled = [] {
-        const char *v = std::getenv("QSV_SVD");
-        return !(v && std::string(v) == "exact");
-    }();
-    bool hopeless = false;                // an absolute tolerance far below the scale of theta: zgesdd cannot pass its test
-    if (frobenius_squared > 0.0) {
-        const double norm = sqrt(frobenius_squared);
-        hopeless = (abs_err > rel_err * norm ? abs_err : rel_err * norm) < 1e-5 * norm;
-    }
-    static const bool jacobi_enabled = [] {
-        const char *v = std::getenv("QSV_SVD");
-        return !(v && (std::string(v) == "exact" || std::string(v) == "library"));
-    }();
-    // zgesdd's answer is tried as it is only when the tolerance cannot tell the difference; under a tight one its factors
-    // still seed the Jacobi sweeps over the whole matrix (jacobi_full_split), which then need a handful of sweeps
-    const bool loose = !hopeless && (rel_err >= 1e-6 || abs_err > 0.0);
-    // (sweeps move the whole working matrix once per tournament step: beyond 2^26 amplitudes the library is no slower)
-    const bool jacobi_fits = jacobi_enabled && k >= 2 && k <= static_cast<uint64_t>(JACOBI_MAX_COLUMNS) &&
-                             rows * cols <= (1ull << 26);
+    const ExactRoute route = exact_route(rows, cols, abs_err, rel_err, frobenius_squared, opt);
+    const bool loose = route.loose, jacobi_fits = route.jacobi_fits;
     bool have_seed = false;
-    if (a.zgesdd && gram_route_enabled && (loose || jacobi_fits)) {
+    if (a.zgesdd && opt.shortcuts && (loose || jacobi_fits)) {
         amp_t *backup = nullptr;
         if (buf.alloc(&backup, sizeof(amp_t) * rows * cols)) {
             QSV_HIP(hipMemcpyAsync(backup, theta, sizeof(amp_t) * rows * cols, hipMemcpyDeviceToDevice, stream));
-            if (a.zgesdd(h, rocblas_svect_singular, rocblas_svect_singular, ci, ri, Zp(theta), ci, dS, Zp(dU), ci, Zp(dV), ki,
+            if (a.zgesdd(h, rocblas_svect_singular, rocblas_svect_singular, ci, ri, Z(theta), ci, dS, Z(dU), ci, Z(dV), ki,
                          dinfo) == rocblas_status_success) {
                 const int rc_fetch = fetch_values();
                 if (rc_fetch) return rc_fetch;
                 have_seed = info == 0;
-                if (info == 0 && k > 0 && loose) {
-                    const double floor_value = 2e-8 * sv[0], margin = floor_value * static_cast<double>(k);
-                    const double allowed = allowed_error(sv, abs_err, rel_err);
-                    if (allowed > 100.0 * margin) {
-                        const uint64_t r_lo = kept_rank_for(sv, max_bond_dim, allowed + margin);
-                        const uint64_t r_hi = kept_rank_for(sv, max_bond_dim, allowed - margin);
-                        decided = r_lo == r_hi && (r_lo == 0 || sv[r_lo - 1] > 1e3 * floor_value);
-                    }
-                }
+                decided = info == 0 && loose && gram_values_decide(sv, max_bond_dim, abs_err, rel_err);
             }
             if (!decided) QSV_HIP(hipMemcpyAsync(theta, backup, sizeof(amp_t) * rows * cols, hipMemcpyDeviceToDevice, stream));
         }
@@ -1096,8 +349,8 @@ int qsvg_svd_split(int device, hipStream_t stream, amp_t *theta, uint64_t rows, 
         if (own != QSV_UNDECIDED) return own;
     }
     if (!decided) {
-        const rocblas_status s = a.zgesvd(h, rocblas_svect_singular, rocblas_svect_singular, ci, ri, Zp(theta), ci, dS, Zp(dU),
-                                          ci, Zp(dV), ki, dE, rocblas_outofplace, dinfo);
+        const rocblas_status s = a.zgesvd(h, rocblas_svect_singular, rocblas_svect_singular, ci, ri, Z(theta), ci, dS, Z(dU),
+                                          ci, Z(dV), ki, dE, rocblas_outofplace, dinfo);
         if (s != rocblas_status_success) return qsv_fail(QSV_EHIP, "rocsolver_zgesvd failed");
         const int rc_fetch = fetch_values();
         if (rc_fetch) return rc_fetch;
@@ -1115,1093 +368,5 @@ int qsvg_svd_split(int device, hipStream_t stream, amp_t *theta, uint64_t rows, 
     if (s_host)
         for (uint64_t i = 0; i < k; ++i) s_host[i] = sv[i];
     *rank_out = r;
-    return QSV_OK;
-}
-
-// ----------------------------------------------------------------------------------------------------
-// Tall-skinny products of the range finder on the f64 matrix cores.
-//
-//   k_skinny_nn :  Y (n x l) = A (n x m) . Q (m x l)          k_skinny_cn :  Y (m x l) = A^H (m x n) . Q (n x l)
-//
-// A is the big operand (column-major, ld n: gigabytes), Q / Y are panels of l <= 64 columns.  rocBLAS pads such panels
-// to a 64-wide macro tile and streams A at 2.2 TB/s whatever l is; these kernels tile l in steps of 16
-// (v_mfma_f64_16x16x4_f64: A[i = lane & 15][k = lane >> 4], B[k = lane >> 4][j = lane & 15], D col = lane & 15,
-// row = (lane >> 4) + 4 reg), stage the Q slab through LDS once per workgroup and keep A as one 16-byte load per lane
-// per k-step.  A complex product is four real MFMAs; one wave owns 16 rows (nn) or 16 columns (cn) of A.
-// The sum over k may be taken in any order as long as both operands use the same one: the cn kernel lets a lane
-// fetch two consecutive rows (32 contiguous bytes) and spends them on two successive MFMA steps, so that the four lane
-// groups cover whole 128-byte lines of every column.
-// ----------------------------------------------------------------------------------------------------
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-constexpr int SK_SLAB = 32;           // k values per LDS slab of Q
-
-template <int T>                      // T = number of 16-column tiles of the panel (l <= 16 T)
-__global__ __launch_bounds__(256) void k_skinny_nn(const amp_t *__restrict__ A, const amp_t *__restrict__ Q,
-                                                  amp_t *__restrict__ Y, uint64_t n, uint64_t m, int l,
-                                                  double im_sign, amp_t *__restrict__ shares) {
-    __shared__ amp_t slab[2][SK_SLAB][16 * T + 1];   // +1: the column-wise slab stores would otherwise hit one bank
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int li = lane & 15, lk = lane >> 4;
-    const uint64_t row = static_cast<uint64_t>(blockIdx.x) * 64 + wave * 16 + li;
-    const bool row_ok = row < n;
-    f64x4 cre[T], cim[T];
-#pragma unroll
-    for (int j = 0; j < T; ++j) cre[j] = cim[j] = f64x4{0.0, 0.0, 0.0, 0.0};
-    const uint64_t all_slabs = (m + SK_SLAB - 1) / SK_SLAB;
-    // split-K: blockIdx.y takes a contiguous share of the slabs; with two shares the two partial sums meet in a
-    // zero-initialised Y through atomic adds, and a + b does not depend on which arrives first
-    const uint64_t s_begin = all_slabs * blockIdx.y / gridDim.y, slabs = all_slabs * (blockIdx.y + 1) / gridDim.y;
-    constexpr int QREGS = SK_SLAB * 16 * T / 256;     // slab entries per thread
-    amp_t q_next[QREGS];
-    auto load_q = [&](uint64_t s) {              // Q[k0 + k][j] of slab s -> registers, zero padded
-        const uint64_t k0 = s * SK_SLAB;
-#pragma unroll
-        for (int u = 0; u < QREGS; ++u) {
-            const int e = t + 256 * u, k = e % SK_SLAB, j = e / SK_SLAB;
-            q_next[u] = (k0 + k < m && j < l) ? Q[static_cast<uint64_t>(j) * m + k0 + k] : amp_t{0.0, 0.0};
-        }
-    };
-    auto store_q = [&](int buf) {
-#pragma unroll
-        for (int u = 0; u < QREGS; ++u) {
-            const int e = t + 256 * u;
-            slab[buf][e % SK_SLAB][e / SK_SLAB] = q_next[u];
-        }
-    };
-    amp_t a_now[SK_SLAB / 4], a_next[SK_SLAB / 4];
-    auto fetch = [&](amp_t *dst, uint64_t s) {
-        const uint64_t k0 = s * SK_SLAB;
-#pragma unroll
-        for (int q = 0; q < SK_SLAB / 4; ++q) {
-            const uint64_t k = k0 + 4 * q + lk;
-            dst[q] = (row_ok && k < m) ? __builtin_nontemporal_load(A + k * n + row) : amp_t{0.0, 0.0};
-        }
-    };
-    load_q(s_begin);
-    store_q(s_begin & 1);
-    fetch(a_now, s_begin);
-    for (uint64_t s = s_begin; s < slabs; ++s) {
-        const int buf = s & 1;
-        __syncthreads();                               // slab[buf] is complete, slab[buf ^ 1] is free
-        const bool more = s + 1 < slabs;
-        if (more) {                                    // loads for the next slab fly while this one is multiplied
-            load_q(s + 1);
-            fetch(a_next, s + 1);
-        }
-#pragma unroll
-        for (int q = 0; q < SK_SLAB / 4; ++q) {
-            const double are = a_now[q].x, aim = im_sign * a_now[q].y;   // im_sign = -1: conj(A) Q
-            amp_t b[T];
-#pragma unroll
-            for (int j = 0; j < T; ++j) b[j] = slab[buf][4 * q + lk][16 * j + li];
-#pragma unroll
-            for (int j = 0; j < T; ++j) {        // dependent updates of one accumulator stay 2 T instructions apart
-                cre[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(are, b[j].x, cre[j], 0, 0, 0);
-                cim[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(are, b[j].y, cim[j], 0, 0, 0);
-            }
-#pragma unroll
-            for (int j = 0; j < T; ++j) {
-                cre[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(-aim, b[j].y, cre[j], 0, 0, 0);
-                cim[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(aim, b[j].x, cim[j], 0, 0, 0);
-            }
-        }
-        if (more) {
-            store_q(buf ^ 1);
-#pragma unroll
-            for (int q = 0; q < SK_SLAB / 4; ++q) a_now[q] = a_next[q];
-        }
-    }
-    // D: col = lane & 15, row = (lane >> 4) + 4 reg
-    const uint64_t row_base = static_cast<uint64_t>(blockIdx.x) * 64 + wave * 16;
-#pragma unroll
-    for (int j = 0; j < T; ++j) {
-        const int col = 16 * j + li;
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            const uint64_t r = row_base + lk + 4 * reg;
-            if (r < n && col < l) {
-                amp_t *dst = Y + static_cast<uint64_t>(col) * n + r;
-                if (gridDim.y == 1) {
-                    *dst = amp_t{cre[j][reg], cim[j][reg]};
-                } else if (shares) {        // k_sum_shares adds the shares in order
-                    shares[(static_cast<uint64_t>(blockIdx.y) * l + col) * n + r] = amp_t{cre[j][reg], cim[j][reg]};
-                } else {
-                    atomicAdd(reinterpret_cast<double *>(dst), cre[j][reg]);
-                    atomicAdd(reinterpret_cast<double *>(dst) + 1, cim[j][reg]);
-                }
-            }
-        }
-    }
-}
-
-template <int T>
-__global__ __launch_bounds__(256) void k_skinny_cn(const amp_t *__restrict__ A, const amp_t *__restrict__ Q,
-                                                  amp_t *__restrict__ Y, uint64_t n, uint64_t m, int l,
-                                                  double im_sign, amp_t *__restrict__ shares) {
-    __shared__ amp_t slab[2][SK_SLAB][16 * T + 1];   // +1: the column-wise slab stores would otherwise hit one bank
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int li = lane & 15, lk = lane >> 4;
-    const uint64_t col = static_cast<uint64_t>(blockIdx.x) * 64 + wave * 16 + li;   // column of A = output row
-    const bool col_ok = col < m;
-    f64x4 cre[T], cim[T];
-#pragma unroll
-    for (int j = 0; j < T; ++j) cre[j] = cim[j] = f64x4{0.0, 0.0, 0.0, 0.0};
-    const uint64_t all_slabs = (n + SK_SLAB - 1) / SK_SLAB;
-    const uint64_t s_begin = all_slabs * blockIdx.y / gridDim.y, slabs = all_slabs * (blockIdx.y + 1) / gridDim.y;
-    constexpr int QREGS = SK_SLAB * 16 * T / 256;
-    amp_t q_next[QREGS];
-    auto load_q = [&](uint64_t s) {              // Q[r0 + k][j] of slab s -> registers
-        const uint64_t r0 = s * SK_SLAB;
-#pragma unroll
-        for (int u = 0; u < QREGS; ++u) {
-            const int e = t + 256 * u, k = e % SK_SLAB, j = e / SK_SLAB;
-            q_next[u] = (r0 + k < n && j < l) ? Q[static_cast<uint64_t>(j) * n + r0 + k] : amp_t{0.0, 0.0};
-        }
-    };
-    auto store_q = [&](int buf) {
-#pragma unroll
-        for (int u = 0; u < QREGS; ++u) {
-            const int e = t + 256 * u;
-            slab[buf][e % SK_SLAB][e / SK_SLAB] = q_next[u];
-        }
-    };
-    // rows of a slab in blocks of 8: lane group lk owns rows 8 b + 2 lk and 8 b + 2 lk + 1 (32 contiguous bytes)
-    amp_t a_now[SK_SLAB / 4], a_next[SK_SLAB / 4];
-    auto fetch = [&](amp_t *dst, uint64_t s) {
-        const uint64_t r0 = s * SK_SLAB;
-#pragma unroll
-        for (int b = 0; b < SK_SLAB / 8; ++b)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const uint64_t r = r0 + 8 * b + 2 * lk + h;
-                dst[2 * b + h] = (col_ok && r < n) ? __builtin_nontemporal_load(A + col * n + r) : amp_t{0.0, 0.0};
-            }
-    };
-    load_q(s_begin);
-    store_q(s_begin & 1);
-    fetch(a_now, s_begin);
-    for (uint64_t s = s_begin; s < slabs; ++s) {
-        const int buf = s & 1;
-        __syncthreads();
-        const bool more = s + 1 < slabs;
-        if (more) {
-            load_q(s + 1);
-            fetch(a_next, s + 1);
-        }
-#pragma unroll
-        for (int b = 0; b < SK_SLAB / 8; ++b)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                // the MFMAs below take conj(A): (are, -aim); im_sign = -1 turns that into the plain transpose
-                const double are = a_now[2 * b + h].x, aim = im_sign * a_now[2 * b + h].y;
-                amp_t q[T];
-#pragma unroll
-                for (int j = 0; j < T; ++j) q[j] = slab[buf][8 * b + 2 * lk + h][16 * j + li];
-#pragma unroll
-                for (int j = 0; j < T; ++j) {
-                    cre[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(are, q[j].x, cre[j], 0, 0, 0);
-                    cim[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(are, q[j].y, cim[j], 0, 0, 0);
-                }
-#pragma unroll
-                for (int j = 0; j < T; ++j) {
-                    cre[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(aim, q[j].y, cre[j], 0, 0, 0);
-                    cim[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(-aim, q[j].x, cim[j], 0, 0, 0);
-                }
-            }
-        if (more) {
-            store_q(buf ^ 1);
-#pragma unroll
-            for (int q = 0; q < SK_SLAB / 4; ++q) a_now[q] = a_next[q];
-        }
-    }
-    const uint64_t out_base = static_cast<uint64_t>(blockIdx.x) * 64 + wave * 16;
-#pragma unroll
-    for (int j = 0; j < T; ++j) {
-        const int pc = 16 * j + li;
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            const uint64_t r = out_base + lk + 4 * reg;
-            if (r < m && pc < l) {
-                amp_t *dst = Y + static_cast<uint64_t>(pc) * m + r;
-                if (gridDim.y == 1) {
-                    *dst = amp_t{cre[j][reg], cim[j][reg]};
-                } else if (shares) {
-                    shares[(static_cast<uint64_t>(blockIdx.y) * l + pc) * m + r] = amp_t{cre[j][reg], cim[j][reg]};
-                } else {
-                    atomicAdd(reinterpret_cast<double *>(dst), cre[j][reg]);
-                    atomicAdd(reinterpret_cast<double *>(dst) + 1, cim[j][reg]);
-                }
-            }
-        }
-    }
-}
-
-// Y = op(A) Q with A (n x m), everything column-major with tight leading dimensions:
-//   transpose == false: Y (n x l) = A Q or conj(A) Q   (Q is m x l);   transpose == true: Y (m x l) = A^T Q or A^H Q   (Q is n x l).
-// Returns false when the shape is outside what the kernels take (l > 64) so that the caller can use the library instead.
-constexpr int WIDE_MAX = 256;        // widest panel the blocked (64-column) forms take
-
-constexpr unsigned SKINNY_MAX_SHARES = 16;
-
-// Y[i] = shares[0][i] + shares[1][i] + ... in that order (the k ranges of a split-K skinny product)
-__global__ __launch_bounds__(256) void k_sum_shares(const amp_t *__restrict__ shares, amp_t *__restrict__ Y, uint64_t count,
-                                                   int n_shares) {
-    const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
-    if (i >= count) return;
-    amp_t v[SKINNY_MAX_SHARES];
-#pragma unroll
-    for (int s = 0; s < static_cast<int>(SKINNY_MAX_SHARES); ++s)
-        if (s < n_shares) v[s] = shares[static_cast<uint64_t>(s) * count + i];
-    amp_t sum = v[0];
-#pragma unroll
-    for (int s = 1; s < static_cast<int>(SKINNY_MAX_SHARES); ++s)
-        if (s < n_shares) {
-            sum.x += v[s].x;
-            sum.y += v[s].y;
-        }
-    Y[i] = sum;
-}
-
-// `shares` (optional, room for `share_amps` amplitudes): workspace that lets a product with few output rows cut its k
-// range into up to 16 shares (one workgroup each, summed in order by k_sum_shares) instead of two
-bool skinny_gemm(hipStream_t stream, bool transpose, bool conjugate, const amp_t *A, const amp_t *Q, amp_t *Y,
-                 uint64_t n, uint64_t m, int l, amp_t *shares = nullptr, uint64_t share_amps = 0) {
-    if (l < 1 || l > WIDE_MAX) return false;
-    const uint64_t out_rows = transpose ? m : n;
-    if (l > 64) {        // panels wider than the kernels' 64 columns: one pass over A per 64-column slice
-        const uint64_t q_rows = transpose ? n : m;
-        for (int c0 = 0; c0 < l; c0 += 64)
-            if (!skinny_gemm(stream, transpose, conjugate, A, Q + static_cast<uint64_t>(c0) * q_rows,
-                             Y + static_cast<uint64_t>(c0) * out_rows, n, m, l - c0 < 64 ? l - c0 : 64, shares, share_amps))
-                return false;
-        return true;
-    }
-    const int tiles = (l + 15) / 16;
-    const unsigned row_blocks = static_cast<unsigned>((out_rows + 63) / 64);
-    const uint64_t depth = transpose ? n : m;        // the summed dimension
-    // one wave per SIMD cannot hide its own load latency: below two workgroups per CU the k range is cut in two (the two
-    // partial sums meet in a zero-initialised Y through atomic adds: a + b does not depend on which arrives first) -- or,
-    // with a workspace, into as many shares as give every CU two workgroups, each at least four slabs deep
-    unsigned split = row_blocks < 512 && depth >= 4 * SK_SLAB ? 2 : 1;
-    bool shared_out = false;
-    if (split > 1 && shares && row_blocks < 256) {
-        unsigned want = (512 + row_blocks - 1) / row_blocks;
-        const uint64_t deepest = depth / (4 * SK_SLAB);
-        if (want > SKINNY_MAX_SHARES) want = SKINNY_MAX_SHARES;
-        if (want > deepest) want = static_cast<unsigned>(deepest);
-        while (want > 2 && static_cast<uint64_t>(want) * out_rows * l > share_amps) --want;
-        if (want > 2 && static_cast<uint64_t>(want) * out_rows * l <= share_amps) {
-            split = want;
-            shared_out = true;
-        }
-    }
-    if (split > 1 && !shared_out && hipMemsetAsync(Y, 0, sizeof(amp_t) * out_rows * l, stream) != hipSuccess) return false;
-    const dim3 grid(row_blocks, split), block(256);
-    amp_t *share_arg = shared_out ? shares : nullptr;
-    // k_skinny_nn multiplies by (re, im_sign * im); k_skinny_cn by the conjugate of that
-    const double im_sign = transpose ? (conjugate ? 1.0 : -1.0) : (conjugate ? -1.0 : 1.0);
-#define QSV_SKINNY(T)                                                                                                    \
-    if (transpose) hipLaunchKernelGGL(k_skinny_cn<T>, grid, block, 0, stream, A, Q, Y, n, m, l, im_sign, share_arg);     \
-    else hipLaunchKernelGGL(k_skinny_nn<T>, grid, block, 0, stream, A, Q, Y, n, m, l, im_sign, share_arg)
-    switch (tiles) {
-        case 1: QSV_SKINNY(1); break;
-        case 2: QSV_SKINNY(2); break;
-        case 3: QSV_SKINNY(3); break;
-        default: QSV_SKINNY(4); break;
-    }
-#undef QSV_SKINNY
-    if (shared_out) {
-        const uint64_t count = out_rows * l;
-        hipLaunchKernelGGL(k_sum_shares, dim3(static_cast<unsigned>((count + 255) / 256)), dim3(256), 0, stream, shares, Y,
-                           count, static_cast<int>(split));
-    }
-    return hipGetLastError() == hipSuccess;
-}
-
-// Shifted CholeskyQR3 of the column-major (n x l) panel Y, in place.  `r_total` (l x l, row-major, may be null) receives
-// the triangular factor with  Y_in = Y_out * r_total.
-// `rounds` = 2 for the intermediate panels of the power iteration: only their SPAN enters the next product, and after the
-// shifted round and one plain round the basis is conditioned like O(1) (absent directions dropped) -- the third round,
-// which takes the Gram matrix from ~1e-8 of the identity to rounding level, matters for the final Q and for Qb alone.
-int panel_orthonormalise(hipStream_t stream, amp_t *Y, uint64_t n, int l, amp_t *partials, amp_t *r_factor,
-                         amp_t *r_total, int *flags = nullptr, int rounds = 3) {
-    const size_t lds = sizeof(amp_t) * l * PANEL_PITCH;
-    static std::once_flag raised, raised_solve;     // attributes are process-wide: set once, whichever thread comes first
-    static hipError_t raised_status = hipSuccess, raised_solve_status = hipSuccess;
-    if (lds > 64 * 1024) {
-        std::call_once(raised, [] {
-            const int bytes = static_cast<int>(LMAX * PANEL_PITCH * sizeof(amp_t));
-            raised_status = hipFuncSetAttribute(reinterpret_cast<const void *>(k_panel_gram<1>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            if (raised_status == hipSuccess)
-                raised_status = hipFuncSetAttribute(reinterpret_cast<const void *>(k_panel_gram<4>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        });
-        QSV_HIP(raised_status);
-    }
-    if (lds + sizeof(amp_t) * l * l > 64 * 1024) {
-        std::call_once(raised_solve, [] {
-            raised_solve_status = hipFuncSetAttribute(reinterpret_cast<const void *>(k_panel_solve),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                      static_cast<int>((LMAX * PANEL_PITCH + LMAX * LMAX) * sizeof(amp_t)));
-        });
-        QSV_HIP(raised_solve_status);
-    }
-    const uint64_t tiles = (n + PANEL_ROWS - 1) / PANEL_ROWS;
-    const int gram_blocks = static_cast<int>(tiles < GRAM_BLOCKS ? tiles : GRAM_BLOCKS);
-    const unsigned apply_blocks = static_cast<unsigned>(tiles < 4096 ? tiles : 4096);
-    for (int round = 0; round < rounds; ++round) {
-        // flags[round] tells this round's kernels to return at once; the factor kernel of a round writes flags[round + 1]
-        const int *skip = flags && round > 0 ? flags + round : nullptr;
-        int *next = flags && round < 2 ? flags + round + 1 : nullptr;
-        if (tiles <= 256) hipLaunchKernelGGL(k_panel_gram<4>, dim3(gram_blocks, 4), dim3(256), lds, stream, Y, n, l, partials, skip);
-        else hipLaunchKernelGGL(k_panel_gram<1>, dim3(gram_blocks), dim3(256), lds, stream, Y, n, l, partials, skip);
-        if (gram_blocks > 1)
-            hipLaunchKernelGGL(k_gram_reduce, dim3((l * l + 255) / 256), dim3(256), 0, stream, partials, gram_blocks, l * l, skip);
-        hipLaunchKernelGGL(k_panel_factor, dim3(1), dim3(FACTOR_THREADS), 0, stream, partials, 1, l, n, round == 0,
-                           round == 0 ? nullptr : r_total, r_total, r_factor, skip, next);
-        hipLaunchKernelGGL(k_panel_solve, dim3(apply_blocks), dim3(256), lds + sizeof(amp_t) * l * l, stream, Y, n, l,
-                           r_factor, skip);
-    }
-    QSV_HIP(hipGetLastError());
-    return QSV_OK;
-}
-
-// ---- panels wider than 64 columns: block Gram-Schmidt over 64-column blocks -------------------------------------------
-// partials[block][i * lb + j] = sum over the block's rows of conj(Ya[r, i]) * Yb[r, j]  (two panels of la, lb <= 64 columns)
-__global__ __launch_bounds__(256) void k_panel_cross(const amp_t *__restrict__ Ya, const amp_t *__restrict__ Yb,
-                                                    uint64_t n, int la, int lb, amp_t *__restrict__ partials) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    amp_t *ta = reinterpret_cast<amp_t *>(smem_raw);     // [la][PANEL_PITCH]
-    amp_t *tb = ta + la * PANEL_PITCH;                   // [lb][PANEL_PITCH]
-    const int t = threadIdx.x, entries = la * lb;
-    amp_t acc[LMAX * LMAX / 256];
-#pragma unroll
-    for (int k = 0; k < LMAX * LMAX / 256; ++k) acc[k] = amp_t{0.0, 0.0};
-    for (uint64_t r0 = static_cast<uint64_t>(blockIdx.x) * PANEL_ROWS; r0 < n;
-         r0 += static_cast<uint64_t>(gridDim.x) * PANEL_ROWS) {
-        __syncthreads();
-        for (int idx = t; idx < (la + lb) * PANEL_ROWS; idx += 256) {
-            const int c = idx / PANEL_ROWS, r = idx % PANEL_ROWS;
-            const amp_t *src = c < la ? Ya + static_cast<uint64_t>(c) * n : Yb + static_cast<uint64_t>(c - la) * n;
-            ta[c * PANEL_PITCH + r] = r0 + r < n ? src[r0 + r] : amp_t{0.0, 0.0};
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < LMAX * LMAX / 256; ++k) {
-            const int e = t + 256 * k;
-            if (e < entries) {
-                const amp_t *ci = ta + (e / lb) * PANEL_PITCH, *cj = tb + (e % lb) * PANEL_PITCH;
-                amp_t a = acc[k];
-                for (int r = 0; r < PANEL_ROWS; ++r) {
-                    const amp_t p = conj_mul(ci[r], cj[r]);
-                    a.x += p.x;
-                    a.y += p.y;
-                }
-                acc[k] = a;
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < LMAX * LMAX / 256; ++k) {
-        const int e = t + 256 * k;
-        if (e < entries) partials[static_cast<size_t>(blockIdx.x) * entries + e] = acc[k];
-    }
-}
-
-// C (la x lb, row-major) = sum of the partials; optionally R[row0 + i][col0 + j] (+)= C[i][j] in the l x l factor
-__global__ __launch_bounds__(256) void k_cross_reduce(const amp_t *__restrict__ partials, int nblocks, int la, int lb,
-                                                     amp_t *__restrict__ C, amp_t *__restrict__ R, int l, int row0,
-                                                     int col0, int accumulate) {
-    const int entries = la * lb;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < entries; e += gridDim.x * 256) {
-        amp_t s = {0.0, 0.0};
-        for (int b = 0; b < nblocks; ++b) {
-            const amp_t v = partials[static_cast<size_t>(b) * entries + e];
-            s.x += v.x;
-            s.y += v.y;
-        }
-        C[e] = s;
-        if (R) {
-            amp_t *dst = R + static_cast<size_t>(row0 + e / lb) * l + col0 + e % lb;
-            *dst = accumulate ? amp_t{dst->x + s.x, dst->y + s.y} : s;
-        }
-    }
-}
-
-// Yb[r, j] -= sum_i Qa[r, i] * C[i][j]   (Qa: la columns, Yb: lb columns, C row-major la x lb)
-__global__ __launch_bounds__(256) void k_panel_update(amp_t *__restrict__ Yb, const amp_t *__restrict__ Qa, uint64_t n,
-                                                     int la, int lb, const amp_t *__restrict__ C) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    amp_t *tile = reinterpret_cast<amp_t *>(smem_raw);   // [la][PANEL_PITCH]
-    amp_t *Cs = tile + la * PANEL_PITCH;                 // [la][lb]
-    const int t = threadIdx.x, r = t % PANEL_ROWS, group = t / PANEL_ROWS;
-    for (int e = t; e < la * lb; e += 256) Cs[e] = C[e];
-    for (uint64_t r0 = static_cast<uint64_t>(blockIdx.x) * PANEL_ROWS; r0 < n;
-         r0 += static_cast<uint64_t>(gridDim.x) * PANEL_ROWS) {
-        __syncthreads();
-        for (int idx = t; idx < la * PANEL_ROWS; idx += 256) {
-            const int c = idx / PANEL_ROWS, rr = idx % PANEL_ROWS;
-            tile[c * PANEL_PITCH + rr] = r0 + rr < n ? Qa[static_cast<uint64_t>(c) * n + r0 + rr] : amp_t{0.0, 0.0};
-        }
-        __syncthreads();
-        if (r0 + r < n)
-            for (int j = group; j < lb; j += 256 / PANEL_ROWS) {
-                amp_t acc = Yb[static_cast<uint64_t>(j) * n + r0 + r];
-                for (int i = 0; i < la; ++i) {
-                    const amp_t p = plain_mul(tile[i * PANEL_PITCH + r], Cs[i * lb + j]);
-                    acc.x -= p.x;
-                    acc.y -= p.y;
-                }
-                Yb[static_cast<uint64_t>(j) * n + r0 + r] = acc;
-            }
-    }
-}
-
-// out[row0 + i][col0 + j] = src[i][j] for an (h x w) row-major block `src` inside the l x l row-major `out`
-__global__ __launch_bounds__(256) void k_place_block(amp_t *__restrict__ out, int l, int row0, int col0,
-                                                    const amp_t *__restrict__ src, int h, int w) {
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < h * w; e += gridDim.x * 256)
-        out[static_cast<size_t>(row0 + e / w) * l + col0 + e % w] = src[e];
-}
-
-// Orthonormalise a column-major (n x l) panel of any width up to WIDE_MAX: shifted CholeskyQR3 on 64-column blocks, each
-// first projected twice against the blocks before it (block classical Gram-Schmidt with re-orthogonalisation).
-// `r_total` (l x l row-major, may be null) receives the block upper triangular factor with Y_in = Y_out * r_total;
-// `scratch` holds 2 * 64 * 64 amplitudes.
-int wide_panel_orthonormalise(hipStream_t stream, amp_t *Y, uint64_t n, int l, amp_t *partials, amp_t *scratch,
-                              amp_t *r_total, int *flags, int rounds = 3) {
-    if (l <= LMAX) return panel_orthonormalise(stream, Y, n, l, partials, scratch, r_total, flags, rounds);
-    static std::once_flag raised;
-    static hipError_t raised_status = hipSuccess;
-    std::call_once(raised, [] {
-        const int big = static_cast<int>((2 * LMAX * PANEL_PITCH) * sizeof(amp_t));
-        raised_status = hipFuncSetAttribute(reinterpret_cast<const void *>(k_panel_cross),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, big);
-        if (raised_status == hipSuccess)
-            raised_status = hipFuncSetAttribute(reinterpret_cast<const void *>(k_panel_update),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                static_cast<int>((LMAX * PANEL_PITCH + LMAX * LMAX) * sizeof(amp_t)));
-    });
-    QSV_HIP(raised_status);
-    amp_t *block_factor = scratch, *cross = scratch + LMAX * LMAX;
-    const uint64_t tiles = (n + PANEL_ROWS - 1) / PANEL_ROWS;
-    const int red_blocks = static_cast<int>(tiles < GRAM_BLOCKS ? tiles : GRAM_BLOCKS);
-    const unsigned row_blocks = static_cast<unsigned>(tiles < 4096 ? tiles : 4096);
-    if (r_total) QSV_HIP(hipMemsetAsync(r_total, 0, sizeof(amp_t) * l * l, stream));
-    for (int c0 = 0; c0 < l; c0 += LMAX) {
-        const int w = l - c0 < LMAX ? l - c0 : LMAX;
-        amp_t *Yj = Y + static_cast<uint64_t>(c0) * n;
-        for (int pass = 0; pass < 2 && c0 > 0; ++pass)
-            for (int p0 = 0; p0 < c0; p0 += LMAX) {
-                const amp_t *Qi = Y + static_cast<uint64_t>(p0) * n;        // earlier blocks are full 64-column blocks
-                hipLaunchKernelGGL(k_panel_cross, dim3(red_blocks), dim3(256), sizeof(amp_t) * (LMAX + w) * PANEL_PITCH,
-                                   stream, Qi, Yj, n, LMAX, w, partials);
-                hipLaunchKernelGGL(k_cross_reduce, dim3(4), dim3(256), 0, stream, partials, red_blocks, LMAX, w, cross,
-                                   r_total, l, p0, c0, 1);
-                hipLaunchKernelGGL(k_panel_update, dim3(row_blocks), dim3(256),
-                                   sizeof(amp_t) * (LMAX * PANEL_PITCH + LMAX * w), stream, Yj, Qi, n, LMAX, w, cross);
-            }
-        // the block itself; its triangular factor goes on the diagonal of r_total
-        amp_t *diag = r_total ? cross : nullptr;       // w x w, row-major, reuses the cross buffer
-        const int rc = panel_orthonormalise(stream, Yj, n, w, partials, block_factor, diag, flags, rounds);
-        if (rc) return rc;
-        if (r_total) hipLaunchKernelGGL(k_place_block, dim3(4), dim3(256), 0, stream, r_total, l, c0, c0, diag, w, w);
-    }
-    QSV_HIP(hipGetLastError());
-    return QSV_OK;
-}
-
-bool fused_panels_enabled() {
-    static const bool on = [] {
-        const char *v = std::getenv("QSV_RSVD");
-        return !(v && std::string(v) == "rocsolver");
-    }();
-    return on;
-}
-
-// out (column-major l x l) = transpose of in (column-major l x l);  conjugate != 0: out = conj(in) elementwise instead
-__global__ __launch_bounds__(256) void k_small_reorder(const amp_t *__restrict__ in, amp_t *__restrict__ out, int l,
-                                                      int conjugate) {
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < l * l; e += gridDim.x * 256) {
-        const int i = e % l, k = e / l;
-        const amp_t v = conjugate ? in[e] : in[static_cast<size_t>(i) * l + k];
-        out[e] = conjugate ? amp_t{v.x, -v.y} : v;
-    }
-}
-
-// T (n x l, column-major) = Q (n x l, column-major) * R^H with R (l x l) row-major: the projection coefficients
-// Q^H A = R^H Qb^H of the range finder, folded into the left panel.
-__global__ __launch_bounds__(256) void k_panel_times_rh(const amp_t *__restrict__ Q, const amp_t *__restrict__ R,
-                                                        amp_t *__restrict__ T, uint64_t n, int l) {
-    const uint64_t total = n * static_cast<uint64_t>(l);
-    for (uint64_t o = blockIdx.x * 256ull + threadIdx.x; o < total; o += gridDim.x * 256ull) {
-        const uint64_t i = o % n;
-        const int k = static_cast<int>(o / n);
-        double re = 0.0, im = 0.0;
-        for (int p = 0; p < l; ++p) {
-            const amp_t q = Q[i + static_cast<uint64_t>(p) * n], r = R[static_cast<size_t>(k) * l + p];
-            re += q.x * r.x + q.y * r.y;     // q * conj(r)
-            im += q.y * r.x - q.x * r.y;
-        }
-        T[o] = amp_t{re, im};
-    }
-}
-
-// partials[block] = sum over a 16 x 16 tile of |A(i, j) - sum_k T(i, k) conj(Qb(j, k))|^2: the squared Frobenius norm
-// of what the projection misses, entry by entry -- no subtraction of two nearly equal norms, so the result is good
-// down to rounding level (~1e-15 ||A||) instead of ~1e-8 ||A||.  A(i, j) = theta[i * si + j * sj].
-__global__ __launch_bounds__(256) void k_residual_partials(const amp_t *__restrict__ theta, uint64_t si, uint64_t sj,
-                                                           const amp_t *__restrict__ T, const amp_t *__restrict__ Qb,
-                                                           uint64_t n, uint64_t m, int l, double *__restrict__ partials) {
-    __shared__ amp_t ts[16][17], qs[16][17];
-    __shared__ double red[4];
-    const int ti = threadIdx.x & 15, tj = threadIdx.x >> 4;
-    const uint64_t tiles_i = (n + 15) / 16, tiles_j = (m + 15) / 16;
-    double sum = 0.0;
-    for (uint64_t tile = blockIdx.x; tile < tiles_i * tiles_j; tile += gridDim.x) {
-        const uint64_t i0 = (tile % tiles_i) * 16, j0 = (tile / tiles_i) * 16;
-        const uint64_t i = i0 + ti, j = j0 + tj;
-        double re = 0.0, im = 0.0;
-        for (int k0 = 0; k0 < l; k0 += 16) {
-            __syncthreads();
-            // thread (ti, tj) stages T(i0 + ti, k0 + tj) and Qb(j0 + ti, k0 + tj)
-            const int kk = k0 + tj;
-            ts[tj][ti] = (i0 + ti < n && kk < l) ? T[i0 + ti + static_cast<uint64_t>(kk) * n] : amp_t{0.0, 0.0};
-            qs[tj][ti] = (j0 + ti < m && kk < l) ? Qb[j0 + ti + static_cast<uint64_t>(kk) * m] : amp_t{0.0, 0.0};
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                const amp_t t = ts[k][ti], q = qs[k][tj];
-                re += t.x * q.x + t.y * q.y;     // t * conj(q)
-                im += t.y * q.x - t.x * q.y;
-            }
-        }
-        if (i < n && j < m) {
-            const amp_t a = theta[i * si + j * sj];
-            const double dr = a.x - re, di = a.y - im;
-            sum += dr * dr + di * di;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-// The randomized split with the fused panel kernels: same algorithm and random stream as below, but every
-// re-orthonormalisation is 9 launches and the l x m projection is decomposed through B^H = Qb Rb and a Jacobi SVD of Rb.
-// `verify` != null switches to the *verified low-rank* mode used by the exact split (see qsvg_svd_split): all l computed
-// values are examined, the Frobenius norm of what the l-dimensional projection misses is known exactly
-// (||A||_F^2 - sum sigma~_i^2), and the split is accepted only if the truncation rule provably gives the same rank as it
-// would on the full spectrum; the function returns QSV_UNDECIDED otherwise and theta is untouched.
-struct LowRankCheck {
-    double frobenius_squared;   // ||theta||_F^2
-    int64_t max_bond_dim;       // the caller's cap (k_keep only bounds what the projection may return)
-    uint64_t full_rank;         // min(rows, cols)
-    std::vector<double> *values;   // out: the kept spectrum padded with zeros to full_rank
-};
-
-int rsvd_split_fused(RocblasApi &a, rocblas_handle h, StreamContext &ctx, const amp_t *theta, uint64_t rows, uint64_t cols,
-                     int64_t k_keep, int l, int q, const amp_t *omega, double abs_err, double rel_err, amp_t *m1, amp_t *m2,
-                     uint64_t capacity, uint64_t *rank_out, double *s_host, const LowRankCheck *verify = nullptr) {
-    hipStream_t stream = ctx.stream;
-    const bool wide = rows < cols;
-    const uint64_t n = wide ? cols : rows, m = wide ? rows : cols;
-    const uint64_t L = static_cast<uint64_t>(l);
-    DeviceBuffers buf;
-    const uint64_t block = L < LMAX ? L : LMAX, scratch_amps = 2 * LMAX * LMAX;
-    // the k-range shares of the skinny products: only matrices with few 64-row blocks use them (see skinny_gemm)
-    const uint64_t share_amps = n < 256 * 64 ? SKINNY_MAX_SHARES * n * (L < 64 ? L : 64) : 0;
-    buf.reserve(ctx, sizeof(amp_t) * ((n + m) * (L + static_cast<uint64_t>(k_keep)) + (verify ? n * L : 0) + share_amps +
-                                         GRAM_BLOCKS * block * block + scratch_amps + 5 * L * L) + 32 * L + 16384 + 8 * 1024);
-    amp_t *Qn = nullptr, *Qm = nullptr, *partials = nullptr, *small = nullptr, *UA = nullptr, *VA = nullptr, *shares = nullptr;
-    double *dS = nullptr;
-    // small: block scratch (2 x 64 x 64) | r_total | U_r | V_r | library scratch, each L x L
-    if (!buf.alloc(&Qn, sizeof(amp_t) * n * L) || !buf.alloc(&Qm, sizeof(amp_t) * m * L) ||
-        !buf.alloc(&partials, sizeof(amp_t) * GRAM_BLOCKS * block * block) ||
-        !buf.alloc(&small, sizeof(amp_t) * (scratch_amps + 5 * L * L)) || !buf.alloc(&dS, sizeof(double) * (2 * L + 6)) ||
-        (share_amps && !buf.alloc(&shares, sizeof(amp_t) * share_amps)))
-        return qsv_fail(QSV_ENOMEM, "device allocation of the randomized-SVD workspace failed");
-    amp_t *r_factor = small, *r_total = small + scratch_amps, *Ur = r_total + L * L, *Vr = Ur + L * L, *lib = Vr + L * L;
-    int *flags = reinterpret_cast<int *>(dS + 2 * L + 2);     // round-skipping flags of the panel kernels (4 ints)
-    // theta is row-major (rows x cols); read column-major it is M = theta^T (cols x rows, ld cols).  The reference works on
-    // the tall orientation A: wide theta -> A = theta^T = M itself; tall theta -> A = theta = M^T, reached through the
-    // transposed / conjugated forms of the panel kernels, so no re-ordered copy of theta is ever made.
-    const amp_t *M = theta;
-    const rocblas_double_complex one{1.0, 0.0}, zero{0.0, 0.0};
-    auto Z = [](const amp_t *p) { return reinterpret_cast<const rocblas_double_complex *>(p); };
-    auto W = [](amp_t *p) { return reinterpret_cast<rocblas_double_complex *>(p); };
-    const rocblas_int ni = static_cast<rocblas_int>(n), mi = static_cast<rocblas_int>(m), li = static_cast<rocblas_int>(L);
-    auto gemm = [&](rocblas_operation ta, rocblas_operation tb, rocblas_int M_, rocblas_int N_, rocblas_int K_,
-                    const amp_t *pa, rocblas_int lda, const amp_t *pb, rocblas_int ldb, amp_t *pc, rocblas_int ldc) {
-        return a.zgemm(h, ta, tb, M_, N_, K_, &one, Z(pa), lda, 0, Z(pb), ldb, 0, &zero, W(pc), ldc, 0, 1) ==
-               rocblas_status_success;
-    };
-    const rocblas_operation N = rocblas_operation_none, Cc = rocblas_operation_conjugate_transpose;
-    // the passes over A: the MFMA panel kernels (l tiled by 16); rocBLAS if they decline the shape
-    const rocblas_operation T_ = rocblas_operation_transpose;
-    const rocblas_int ld = static_cast<rocblas_int>(cols);       // leading dimension of M
-    auto times_a = [&](const amp_t *panel, amp_t *out) {          // out (n x l) = A panel (m x l)
-        if (wide)   // A = M (n x m)
-            return skinny_gemm(stream, false, false, M, panel, out, n, m, l, shares, share_amps) ||
-                   gemm(N, N, ni, li, mi, M, ld, panel, mi, out, ni);
-        // A = M^T with M (m x n)
-        return skinny_gemm(stream, true, false, M, panel, out, m, n, l, shares, share_amps) || gemm(T_, N, ni, li, mi, M, ld, panel, mi, out, ni);
-    };
-    auto times_ah = [&](const amp_t *panel, amp_t *out) {         // out (m x l) = A^H panel (n x l)
-        if (wide) return skinny_gemm(stream, true, true, M, panel, out, n, m, l, shares, share_amps) ||
-                         gemm(Cc, N, mi, li, ni, M, ld, panel, ni, out, mi);
-        // A^H = conj(M): no library form for a plain conjugate, the kernels take every l <= 64 this path is entered with
-        return skinny_gemm(stream, false, true, M, panel, out, m, n, l, shares, share_amps);
-    };
-    static const int between = [] {        // rounds of the panels in between (QSV_PANEL_ROUNDS=3: as the final ones)
-        const char *e = std::getenv("QSV_PANEL_ROUNDS");
-        return e && atoi(e) == 3 ? 3 : 2;
-    }();
-    bool ok = times_a(omega, Qn);                                                                 // Y = A O
-    int rc = ok ? wide_panel_orthonormalise(stream, Qn, n, l, partials, r_factor, nullptr, flags, q > 0 ? between : 3) : QSV_OK;
-    for (int it = 0; ok && !rc && it < q; ++it) {
-        ok = times_ah(Qn, Qm);                                                                    // Y = A^H Q
-        if (ok) rc = wide_panel_orthonormalise(stream, Qm, m, l, partials, r_factor, nullptr, flags, between);
-        ok = ok && !rc && times_a(Qm, Qn);                                                        // Y = A Q
-        if (ok) rc = wide_panel_orthonormalise(stream, Qn, n, l, partials, r_factor, nullptr, flags, it + 1 < q ? between : 3);
-    }
-    // B^H = A^H Q = Qb Rb  (m x l);  Rb = Ur S Vr^H;  A ~ (Q Vr) S (Qb Ur)^H
-    ok = ok && !rc && times_ah(Qn, Qm);
-    if (ok) rc = wide_panel_orthonormalise(stream, Qm, m, l, partials, r_factor, r_total, flags);
-    if (!ok) return qsv_fail(QSV_EHIP, "rocBLAS call failed in the randomized range finder");
-    if (rc) return rc;
-    if (L <= LMAX) {
-        hipLaunchKernelGGL(k_small_svd, dim3(1), dim3(small_svd_threads()), 0, stream, r_total, l, Vr, dS, Ur);   // decomposes R^H: roles swap
-        QSV_HIP(hipGetLastError());
-    } else {
-        // wider than the one-workgroup Jacobi kernel: the same sweeps with the working matrices in global memory, one
-        // launch per tournament step (rocSOLVER's zgesvd spends ~25 ms in bdsqr launch storms on a 110 x 110 factor)
-        const int rc_svd = wide_factor_svd(stream, r_total, l, lib, lib + L * L, Ur, dS, Vr, flags + 3);
-        if (rc_svd) return rc_svd;
-    }
-    const uint64_t k = verify ? L : static_cast<uint64_t>(k_keep);
-    std::vector<double> sv(k);
-    QSV_HIP(hipMemcpyAsync(sv.data(), dS, sizeof(double) * k, hipMemcpyDeviceToHost, stream));
-    QSV_HIP(hipStreamSynchronize(stream));
-    uint64_t r;
-    if (verify) {
-        // What the projection misses: rho^2 = ||A||_F^2 - sum sigma~_i^2 = ||(I - Q Q^H) A||_F^2 exactly.  With
-        // d_i = sigma_i^2 - sigma~_i^2 >= 0 (i <= l; singular values of a compression never exceed the true ones) and
-        // d_i = sigma_i^2 (i > l) one has sum d_i = rho^2 and sigma_i - sigma~_i <= sqrt(d_i), so every true tail sum lies
-        // in [T~_j, T~_j + sqrt(full) rho] (Cauchy-Schwarz).  rho itself is resolved down to ~1e-8 ||A||.
-        double captured = 0.0;
-        for (double v : sv) captured += v * v;
-        const double f2 = verify->frobenius_squared;
-        double rho2 = f2 - captured;
-        double resolution = 4e-16 * static_cast<double>(L) * f2;
-        static const bool trace = std::getenv("QSV_TRACE_SPLIT") != nullptr;
-        uint64_t r_decided = 0;
-        // the acceptance test for a given bound on the missed mass: true = the rank is settled (in r_decided)
-        auto settled_with = [&](double rho2_bound) {
-            const double rho = sqrt(rho2_bound), margin = sqrt(static_cast<double>(verify->full_rank)) * rho;
-            const double allowed = allowed_error(sv, abs_err, rel_err);
-            if (trace)
-                fprintf(stderr, "[qsv split] %llu x %llu: probes %d, ||A||_F %.3e, rho %.3e, allowed %.3e, margin %.3e, s0 %.3e\n",
-                        static_cast<unsigned long long>(rows), static_cast<unsigned long long>(cols), l, sqrt(f2), rho, allowed,
-                        margin, sv[0]);
-            if (!(allowed > margin)) return false;
-            // true tail sums are the computed ones plus something in [0, margin]; the true allowance is the computed one
-            // plus at most rel_err * margin: the rank is settled if no computed tail sum falls between these two thresholds
-            const uint64_t r_lo = kept_rank_for(sv, verify->max_bond_dim, allowed + rel_err * margin);
-            const uint64_t r_hi = kept_rank_for(sv, verify->max_bond_dim, allowed - margin);
-            if (trace)
-                fprintf(stderr, "[qsv split]   r in [%llu, %llu], s[r-1] %.3e\n", static_cast<unsigned long long>(r_lo),
-                        static_cast<unsigned long long>(r_hi), r_lo > 0 ? sv[r_lo - 1] : 0.0);
-            // the kept triplets must sit well inside the captured block and far above what was missed (their subspace
-            // error after q power iterations is of order (rho / sigma_r)^(2q+1))
-            if (r_lo != r_hi || r_lo > static_cast<uint64_t>(k_keep) || (r_lo > 0 && !(sv[r_lo - 1] > 1e2 * rho))) return false;
-            r_decided = r_lo;
-            return true;
-        };
-        bool settled = false;
-        if (rho2 < 1e-6 * f2) {
-            // The difference of the two norms is blind below ~1e-8 ||A||.  Under a loose tolerance that is still far more
-            // than the test needs: try it with the blind spot itself as the bound -- a wider margin can only leave the
-            // rank undecided, never change it (both thresholds move outwards) -- and only if that fails ...
-            settled = settled_with(rho2 > resolution ? rho2 : resolution);
-        }
-        if (!settled && rho2 < 1e-6 * f2) {
-            // ... (a tight tolerance: the reference's default rel_err = 1e-12) evaluate the residual itself:
-            // (I - Q Q^H) A = A - (Q Rb^H) Qb^H entry by entry (A^H Q = Qb Rb was formed above), one l-term dot product
-            // per entry, rounding level ~l eps ||A||.
-            amp_t *Tp = nullptr;
-            double *res_partials = nullptr;
-            if (buf.alloc(&Tp, sizeof(amp_t) * n * L) && buf.alloc(&res_partials, sizeof(double) * 1024)) {
-                hipLaunchKernelGGL(k_panel_times_rh, dim3(blocks_for(n * L)), dim3(256), 0, stream, Qn, r_total, Tp, n, l);
-                // A(i, j): wide theta -> A = theta^T: theta[j * cols + i]; tall theta -> A = theta: theta[i * cols + j]
-                hipLaunchKernelGGL(k_residual_partials, dim3(1024), dim3(256), 0, stream, theta, wide ? 1ull : cols,
-                                   wide ? cols : 1ull, Tp, Qm, n, m, l, res_partials);
-                QSV_HIP(hipGetLastError());
-                std::vector<double> parts(1024);
-                QSV_HIP(hipMemcpyAsync(parts.data(), res_partials, sizeof(double) * 1024, hipMemcpyDeviceToHost, stream));
-                QSV_HIP(hipStreamSynchronize(stream));
-                double explicit_rho2 = 0.0;
-                for (double v : parts) explicit_rho2 += v;
-                rho2 = explicit_rho2;
-                // rounding floor of the entry-wise evaluation: each entry carries ~sqrt(l) eps |A_ij| (random signs)
-                resolution = 1e-30 * static_cast<double>(L) * f2;
-            }
-        }
-        if (!settled) settled = settled_with(rho2 > resolution ? rho2 : resolution);
-        if (!settled) return QSV_UNDECIDED;
-        const uint64_t r_lo = r_decided;
-        r = r_lo;
-        if (verify->values) {
-            verify->values->assign(verify->full_rank, 0.0);
-            for (uint64_t i = 0; i < L && i < verify->full_rank; ++i) (*verify->values)[i] = sv[i];
-        }
-    } else {
-        r = kept_rank(sv, k_keep, abs_err, rel_err);
-    }
-    if (r > capacity) return qsv_fail(QSV_EINVAL, "output buffers are smaller than the kept bond dimension");
-    if (r > 0) {
-        const rocblas_int ri = static_cast<rocblas_int>(r);
-        if (!buf.alloc(&UA, sizeof(amp_t) * n * r) || !buf.alloc(&VA, sizeof(amp_t) * m * r))
-            return qsv_fail(QSV_ENOMEM, "device allocation of the randomized-SVD workspace failed");
-        if (!gemm(N, N, ni, ri, li, Qn, ni, Vr, li, UA, ni) || !gemm(N, N, mi, ri, li, Qm, mi, Ur, li, VA, mi))
-            return qsv_fail(QSV_EHIP, "rocblas_zgemm failed");
-        // A = UA S VA^H.  Tall theta = A:  m1 = UA sqrt(S),  m2 = sqrt(S) VA^H.
-        // Wide theta = A^T = conj(VA) S UA^T:  m1 = conj(VA) sqrt(S),  m2 = sqrt(S) UA^T.
-        const amp_t *u_src = wide ? VA : UA, *v_src = wide ? UA : VA;
-        const uint64_t u_ld = wide ? m : n, v_ld = wide ? n : m;
-        hipLaunchKernelGGL(k_scale_strided_conj, dim3(blocks_for(rows * r)), dim3(QSV_BLOCK), 0, stream, u_src, m1, rows,
-                           r, static_cast<uint64_t>(1), u_ld, dS, 0, wide ? 1 : 0);
-        hipLaunchKernelGGL(k_scale_strided_conj, dim3(blocks_for(r * cols)), dim3(QSV_BLOCK), 0, stream, v_src, m2, r,
-                           cols, v_ld, static_cast<uint64_t>(1), dS, 1, wide ? 0 : 1);
-        QSV_HIP(hipGetLastError());
-    }
-    QSV_HIP(hipStreamSynchronize(stream));   // the workspace is freed on return
-    if (s_host && !verify)
-        for (uint64_t i = 0; i < k; ++i) s_host[i] = sv[i];
-    *rank_out = r;
-    return QSV_OK;
-}
-
-// sum of |x|^2 over `count` amplitudes into per-block partials
-__global__ __launch_bounds__(256) void k_sum_squares(const amp_t *__restrict__ x, uint64_t count, double *__restrict__ partials) {
-    __shared__ double red[4];
-    double s = 0.0;
-    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < count; i += gridDim.x * 256ull) s += x[i].x * x[i].x + x[i].y * x[i].y;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-// The probe matrices of the verified low-rank route, per device, width and matrix size: they depend only on those (a
-// fixed random stream), so every stream shares them.  (Several sizes per width: the thetas of one MPS alternate between a
-// few shapes -- 1000, 2000, 4000 on the short side in the GKP runs -- and with ONE entry per width every change of shape
-// cost a Box-Muller pass over 10^5 deviates on the host, an allocation and an upload.)  Entries are handed out
-// reference-counted, and an evicted entry is kept in `retired` until qsv_tensor_release_workspace: a split on another
-// stream may still read it, and hipFree would wait for the whole device.
-struct ProbeMatrix {
-    amp_t *omega = nullptr;
-    uint64_t count = 0;
-    ~ProbeMatrix() {
-        if (omega) (void)hipFree(omega);
-    }
-};
-
-struct ProbeCache {
-    static constexpr int SIZES = 8;
-    struct Slot {
-        std::shared_ptr<ProbeMatrix> probes;
-        uint64_t last_use = 0;
-    };
-    std::mutex lock;          // held for lookup and insertion only
-    Slot slots[16][3][SIZES];
-    std::vector<std::shared_ptr<ProbeMatrix>> retired[16];
-    uint64_t use_clock = 0;
-};
-
-ProbeCache &probe_cache() {
-    static ProbeCache *c = new ProbeCache;     // never destroyed: no hipFree after the runtime has gone at exit
-    return *c;
-}
-
-// The (full x l) probe matrix of width index `w` on the context's device, generated and uploaded on the context's stream
-// when no stream has it yet; null when the device memory is not there.
-std::shared_ptr<ProbeMatrix> probes_for(StreamContext &ctx, int w, uint64_t full, int l) {
-    ProbeCache &cache = probe_cache();
-    ProbeCache::Slot *row = cache.slots[ctx.device][w];
-    const uint64_t count = full * static_cast<uint64_t>(l);
-    {
-        std::lock_guard<std::mutex> guard(cache.lock);
-        for (int i = 0; i < ProbeCache::SIZES; ++i)
-            if (row[i].probes && row[i].probes->count == count) {
-                row[i].last_use = ++cache.use_clock;
-                return row[i].probes;
-            }
-    }
-    auto fresh = std::make_shared<ProbeMatrix>();
-    if (hipMalloc(reinterpret_cast<void **>(&fresh->omega), sizeof(amp_t) * count) != hipSuccess) {
-        fresh->omega = nullptr;
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    std::vector<double> host(2 * count, 0.0);
-    uint64_t state = 0x9e3779b97f4a7c15ull + static_cast<uint64_t>(w);   // splitmix64 + Box-Muller: fixed probe matrices
-    auto next = [&]() {
-        state += 0x9e3779b97f4a7c15ull;
-        uint64_t z = state;
-        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-        return ((z ^ (z >> 31)) >> 11) * (1.0 / 9007199254740992.0);
-    };
-    for (uint64_t i = 0; i < count; ++i) {
-        const double u1 = next() + 1e-300, u2 = next();
-        host[2 * i] = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
-    }
-    // complete before it is published (a synchronous copy): other streams may use the entry as soon as it is in the cache
-    if (hipMemcpy(fresh->omega, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    fresh->count = count;
-    std::lock_guard<std::mutex> guard(cache.lock);
-    ProbeCache::Slot *slot = nullptr;
-    for (int i = 0; i < ProbeCache::SIZES; ++i)
-        if (row[i].probes && row[i].probes->count == count) slot = &row[i];      // another stream was quicker: use its copy
-    if (slot) {
-        slot->last_use = ++cache.use_clock;
-        cache.retired[ctx.device].push_back(std::move(fresh));    // never published; freed with the other retired ones
-        return slot->probes;
-    }
-    slot = &row[0];                          // a free entry, or the one that was used longest ago
-    for (int i = 0; i < ProbeCache::SIZES; ++i)
-        if (!row[i].probes) {
-            slot = &row[i];
-            break;
-        } else if (row[i].last_use < slot->last_use) {
-            slot = &row[i];
-        }
-    if (slot->probes) cache.retired[ctx.device].push_back(std::move(slot->probes));
-    slot->probes = fresh;
-    slot->last_use = ++cache.use_clock;
-    return fresh;
-}
-
-// Free the probe matrices evicted on `device` (qsv_tensor_release_workspace, after it has waited for the device).
-int release_retired_probes(int device) {
-    std::vector<std::shared_ptr<ProbeMatrix>> gone;
-    {
-        ProbeCache &cache = probe_cache();
-        std::lock_guard<std::mutex> guard(cache.lock);
-        gone.swap(cache.retired[device]);
-    }
-    gone.clear();
-    return QSV_OK;
-}
-
-// The exact split's shortcut for numerically low-rank theta under a loose tolerance (the regime of the reference's own
-// GKP runs: rel_err = 1e-2, bonds of 1-2 on d = 1000 grids, where LAPACK-style SVDs of 1000..2000-sized matrices are all
-// the time there is): a 64-probe range finder with its own fixed random stream -- the reference's exact branch draws no
-// random numbers, so the caller's generator must not be touched -- verified a posteriori by LowRankCheck.
-int try_verified_low_rank(RocblasApi &a, rocblas_handle h, StreamContext &ctx, const amp_t *theta, uint64_t rows,
-                          uint64_t cols, int64_t max_bond_dim, double abs_err, double rel_err, amp_t *m1, amp_t *m2,
-                          uint64_t capacity, uint64_t *rank_out, std::vector<double> *values,
-                          double *frobenius_squared_out) {
-    const uint64_t full = rows < cols ? rows : cols;
-    if (full < 4 * static_cast<uint64_t>(LMAX)) return QSV_UNDECIDED;    // small matrices: the library SVD is cheap
-    // the norm partials live outside the pool (which rsvd_split_fused carves for itself), in the stream's context; the
-    // probe matrices in the cache shared by every stream of the device (probes_for)
-    hipStream_t stream = ctx.stream;
-    if (!ctx.norm_partials &&
-        hipMalloc(reinterpret_cast<void **>(&ctx.norm_partials), sizeof(double) * 256) != hipSuccess) {
-        ctx.norm_partials = nullptr;
-        (void)hipGetLastError();
-        return QSV_UNDECIDED;
-    }
-    double *partials = ctx.norm_partials;
-    hipLaunchKernelGGL(k_sum_squares, dim3(256), dim3(256), 0, stream, theta, rows * cols, partials);
-    QSV_HIP(hipGetLastError());
-    double sums[256];
-    QSV_HIP(hipMemcpyAsync(sums, partials, sizeof(sums), hipMemcpyDeviceToHost, stream));
-    QSV_HIP(hipStreamSynchronize(stream));
-    std::vector<double> spectrum;       // the computed values of the attempt that decided (padded with zeros to `full`)
-    LowRankCheck check{0.0, max_bond_dim, full, &spectrum};
-    for (double v : sums) check.frobenius_squared += v;
-    if (frobenius_squared_out) *frobenius_squared_out = check.frobenius_squared;
-    if (!(check.frobenius_squared > 0.0)) return QSV_UNDECIDED;
-    // One 64-column block of probes keeps everything in the fused kernels; when the numerical rank does not fit (the kept
-    // triplets must leave ten probes of oversampling and stand well above what was missed) the panel is widened to 128 and
-    // 256 probes (64-column blocks, Jacobi sweeps in global memory) before the library SVD gets the matrix: even the
-    // widest attempt costs tens of milliseconds where zgesvd takes seconds on these graded spectra.
-    // (Starting at the width that decided the last split of the same shape was measured on the 15 dB GKP Grover run: 3.5 s
-    // against 3.3 -- a 128-probe attempt costs three to four 64-probe ones, and most splits still pass at 64.)
-    const int widths[3] = {LMAX, 2 * LMAX, WIDE_MAX};
-    for (int w = 0; w < 3; ++w) {
-        const int l = widths[w], keep = l - 10;
-        if (full < 4 * static_cast<uint64_t>(l)) break;
-        const std::shared_ptr<ProbeMatrix> probes = probes_for(ctx, w, full, l);
-        if (!probes) return QSV_UNDECIDED;
-        // two power iterations: the route is accepted only when the kept values stand 10^2 rho above everything that was
-        // missed, and the error of their subspace after q iterations is of order (missed / kept)^(2q+1)
-        const int rc = rsvd_split_fused(a, h, ctx, theta, rows, cols, keep, l, 2, probes->omega, abs_err, rel_err, m1, m2,
-                                        capacity, rank_out, nullptr, &check);
-        if (rc == QSV_OK && values) *values = spectrum;
-        if (rc != QSV_UNDECIDED) return rc;
-    }
-    return QSV_UNDECIDED;
-}
-
-// tensor_svd on its randomized branch (mps.py:5-50,78-79; Halko, Martinsson & Tropp 2010): range finder with
-// l = k + 10 Gaussian probes (drawn by the caller so that the reference's random stream is reproduced) and q power
-// iterations re-orthonormalised by Householder QR, SVD of the small l x m' projection, first k triplets kept, then the
-// same truncation rule.  Everything is column-major here; A is the tall orientation of theta (the reference
-// transposes a wide matrix first) and `omega` is (m' x l) column-major, m' = min(rows, cols).
-int qsvg_rsvd_split(int device, hipStream_t stream, const amp_t *theta, uint64_t rows, uint64_t cols, int64_t k_keep,
-                    int l, int q, const amp_t *omega, double abs_err, double rel_err, amp_t *m1, amp_t *m2,
-                    uint64_t capacity, uint64_t *rank_out, double *s_host) {
-    const uint64_t lim = 0x7fffffffull;
-    if (rows > lim || cols > lim) return qsv_fail(QSV_EINVAL, "matrix dimension exceeds 2^31 - 1");
-    RocblasApi &a = api();
-    int rc;
-    StreamContext *ctx = context_for(device, stream, &rc);
-    if (!ctx) return rc;
-    rocblas_handle h = handle_of(*ctx, &rc);
-    if (!h) return rc;
-    if (!a.zgesvd || !a.zgeqrf || !a.zungqr)
-        return qsv_fail(QSV_EHIP, "rocSOLVER could not be loaded (librocsolver.so.0): no SVD available");
-    const bool wide = rows < cols;                      // the reference works on theta^T then
-    const uint64_t n = wide ? cols : rows, m = wide ? rows : cols;   // A is n x m, n >= m
-    const uint64_t L = static_cast<uint64_t>(l), kk = L < m ? L : m;
-    if (k_keep < 1 || L < static_cast<uint64_t>(k_keep) || L > m)
-        return qsv_fail(QSV_EINVAL, "need 1 <= k <= l <= min(rows, cols)");
-    if (omega && L <= LMAX && fused_panels_enabled())
-        return rsvd_split_fused(a, h, *ctx, theta, rows, cols, k_keep, l, q, omega, abs_err, rel_err, m1, m2, capacity,
-                                rank_out, s_host);
-    // More probes than the fused kernels take (max_bond_dim > 54, e.g. the 100 of the reference's GKP runs).  Under a
-    // loose tolerance the kept rank is far below that anyway: the verified low-rank route decides it with 64 probes of
-    // its own; the caller has already drawn -- and thereby consumed from its generator -- the test matrix the reference
-    // would use, so the random stream of a seeded simulation is unaffected.
-    static const bool shortcuts_enabled = [] {
-        const char *v = std::getenv("QSV_SVD");
-        return !(v && std::string(v) == "exact");
-    }();
-    // A caller that came without its test matrix, was asked for it and is back with it (same theta, untouched in between)
-    // has had its verified attempts already: do not repeat them.  (The memo is the stream's: the second call comes on
-    // the stream of the first.)
-    const bool back_with_omega = omega && ctx->asked_theta == theta && ctx->asked_rows == rows && ctx->asked_cols == cols;
-    ctx->asked_theta = nullptr;
-    if (!back_with_omega && L > LMAX && shortcuts_enabled && fused_panels_enabled() && (rel_err >= 1e-4 || abs_err > 0.0)) {
-        std::vector<double> values;
-        const int fast = try_verified_low_rank(a, h, *ctx, theta, rows, cols, k_keep, abs_err, rel_err, m1, m2, capacity,
-                                               rank_out, s_host ? &values : nullptr);
-        if (fast == QSV_OK) {
-            if (s_host)
-                for (int64_t i = 0; i < k_keep; ++i) s_host[i] = values[static_cast<size_t>(i)];
-            return QSV_OK;
-        }
-        if (fast != QSV_UNDECIDED) return fast;
-    }
-    if (!omega) {      // the caller has not drawn the test matrix yet (it costs more than the route above): ask for it
-        ctx->asked_theta = theta;
-        ctx->asked_rows = rows;
-        ctx->asked_cols = cols;
-        *rank_out = QSV_RANK_NEEDS_OMEGA;
-        return QSV_OK;
-    }
-    if (L <= WIDE_MAX && fused_panels_enabled())      // 64-column blocks of probes, library SVD of the projected factor
-        return rsvd_split_fused(a, h, *ctx, theta, rows, cols, k_keep, l, q, omega, abs_err, rel_err, m1, m2, capacity,
-                                rank_out, s_host);
-    DeviceBuffers buf;
-    buf.reserve(*ctx, sizeof(amp_t) * ((n + m) * L + L + L * m + L * kk + kk * m + n * static_cast<uint64_t>(k_keep) +
-                                         (wide ? 0 : n * m)) + 16 * kk + 8192);
-    amp_t *A = nullptr, *Qn = nullptr, *Qm = nullptr, *tau = nullptr, *B = nullptr, *UB = nullptr, *VB = nullptr;
-    double *dS = nullptr, *dE = nullptr;
-    rocblas_int *dinfo = nullptr;
-    if (!buf.alloc(&Qn, sizeof(amp_t) * n * L) || !buf.alloc(&Qm, sizeof(amp_t) * m * L) ||
-        !buf.alloc(&tau, sizeof(amp_t) * L) || !buf.alloc(&B, sizeof(amp_t) * L * m) ||
-        !buf.alloc(&UB, sizeof(amp_t) * L * kk) || !buf.alloc(&VB, sizeof(amp_t) * kk * m) ||
-        !buf.alloc(&dS, sizeof(double) * (2 * kk + 2)))
-        return qsv_fail(QSV_ENOMEM, "device allocation of the randomized-SVD workspace failed");
-    dE = dS + kk;
-    dinfo = reinterpret_cast<rocblas_int *>(dS + 2 * kk);
-    if (wide) {
-        // theta row-major (rows x cols) read column-major is theta^T (cols x rows) = A already
-        A = const_cast<amp_t *>(theta);
-    } else {
-        if (!buf.alloc(&A, sizeof(amp_t) * n * m))
-            return qsv_fail(QSV_ENOMEM, "device allocation of the randomized-SVD workspace failed");
-        const uint64_t tiles = ((n + 15) / 16) * ((m + 15) / 16);
-        hipLaunchKernelGGL(k_to_column_major, dim3(static_cast<unsigned>(tiles < 65536 ? tiles : 65536)), dim3(256), 0,
-                           stream, theta, A, n, m);
-        QSV_HIP(hipGetLastError());
-    }
-    const rocblas_double_complex one{1.0, 0.0}, zero{0.0, 0.0};
-    auto Z = [](const amp_t *p) { return reinterpret_cast<const rocblas_double_complex *>(p); };
-    auto W = [](amp_t *p) { return reinterpret_cast<rocblas_double_complex *>(p); };
-    const rocblas_int ni = static_cast<rocblas_int>(n), mi = static_cast<rocblas_int>(m), li = static_cast<rocblas_int>(L);
-    auto gemm = [&](rocblas_operation ta, rocblas_operation tb, rocblas_int M_, rocblas_int N_, rocblas_int K_,
-                    const amp_t *pa, rocblas_int lda, const amp_t *pb, rocblas_int ldb, amp_t *pc, rocblas_int ldc) {
-        return a.zgemm(h, ta, tb, M_, N_, K_, &one, Z(pa), lda, 0, Z(pb), ldb, 0, &zero, W(pc), ldc, 0, 1) ==
-               rocblas_status_success;
-    };
-    auto orthonormalise = [&](amp_t *Y, rocblas_int rows_) {      // Y <- Q of its reduced QR
-        return a.zgeqrf(h, rows_, li, W(Y), rows_, W(tau)) == rocblas_status_success &&
-               a.zungqr(h, rows_, li, li, W(Y), rows_, W(tau)) == rocblas_status_success;
-    };
-    const rocblas_operation N = rocblas_operation_none, Cc = rocblas_operation_conjugate_transpose;
-    bool ok = gemm(N, N, ni, li, mi, A, ni, omega, mi, Qn, ni) && orthonormalise(Qn, ni);       // Y = A O
-    for (int it = 0; ok && it < q; ++it) {
-        ok = gemm(Cc, N, mi, li, ni, A, ni, Qn, ni, Qm, mi) && orthonormalise(Qm, mi) &&         // Y = A^H Q
-             gemm(N, N, ni, li, mi, A, ni, Qm, mi, Qn, ni) && orthonormalise(Qn, ni);            // Y = A Q
-    }
-    ok = ok && gemm(Cc, N, li, mi, ni, Qn, ni, A, ni, B, li);                                    // B = Q^H A  (l x m)
-    if (!ok) return qsv_fail(QSV_EHIP, "rocBLAS / rocSOLVER call failed in the randomized range finder");
-    if (a.zgesvd(h, rocblas_svect_singular, rocblas_svect_singular, li, mi, W(B), li, dS, W(UB), li, W(VB),
-                 static_cast<rocblas_int>(kk), dE, rocblas_outofplace, dinfo) != rocblas_status_success)
-        return qsv_fail(QSV_EHIP, "rocsolver_zgesvd failed");
-    const uint64_t k = static_cast<uint64_t>(k_keep);
-    std::vector<double> sv(k);
-    rocblas_int info = 0;
-    QSV_HIP(hipMemcpyAsync(sv.data(), dS, sizeof(double) * k, hipMemcpyDeviceToHost, stream));
-    QSV_HIP(hipMemcpyAsync(&info, dinfo, sizeof(info), hipMemcpyDeviceToHost, stream));
-    QSV_HIP(hipStreamSynchronize(stream));
-    if (info != 0) return qsv_fail(QSV_EHIP, "rocsolver_zgesvd did not converge");
-    const uint64_t r = kept_rank(sv, k_keep, abs_err, rel_err);
-    if (r > capacity) return qsv_fail(QSV_EINVAL, "output buffers are smaller than the kept bond dimension");
-    if (r > 0) {
-        // U_A = Q U_B[:, :r]  (n x r, column-major)
-        amp_t *UA = nullptr;
-        if (!buf.alloc(&UA, sizeof(amp_t) * n * r))
-            return qsv_fail(QSV_ENOMEM, "device allocation of the randomized-SVD workspace failed");
-        if (!gemm(N, N, ni, static_cast<rocblas_int>(r), li, Qn, ni, UB, li, UA, ni))
-            return qsv_fail(QSV_EHIP, "rocblas_zgemm failed");
-        // A = U_A S Vh_B.  Tall theta: theta = A; wide theta: theta = A^T = Vh_B^T S U_A^T.
-        const amp_t *u_src = wide ? VB : UA, *v_src = wide ? UA : VB;
-        // m1[row, i] = sqrt(s_i) u[row, i];  m2[i, c] = sqrt(s_i) vh[i, c]
-        const uint64_t u_sa = wide ? kk : 1, u_sb = wide ? 1 : n;          // wide: u[row, i] = VB[i + row * kk]
-        const uint64_t v_sa = wide ? n : 1, v_sb = wide ? 1 : kk;          // wide: vh[i, c] = UA[c + i * n]
-        hipLaunchKernelGGL(k_scale_strided, dim3(blocks_for(rows * r)), dim3(QSV_BLOCK), 0, stream, u_src, m1, rows, r,
-                           u_sa, u_sb, dS, 0);
-        hipLaunchKernelGGL(k_scale_strided, dim3(blocks_for(r * cols)), dim3(QSV_BLOCK), 0, stream, v_src, m2, r, cols,
-                           v_sa, v_sb, dS, 1);
-        QSV_HIP(hipGetLastError());
-    }
-    QSV_HIP(hipStreamSynchronize(stream));   // the workspace is freed on return
-    if (s_host)
-        for (uint64_t i = 0; i < k; ++i) s_host[i] = sv[i];
-    *rank_out = r;
-    return QSV_OK;
-}
-
-// Column-major tall-skinny product on the f64 matrix cores (see k_skinny_nn / k_skinny_cn).
-int qsvg_skinny_gemm(int device, hipStream_t stream, int op, uint64_t n, uint64_t m, int l, const amp_t *A,
-                     const amp_t *Q, amp_t *Y) {
-    QSV_HIP(hipSetDevice(device));
-    // op: 0 = A, 1 = A^H, 2 = A^T, 3 = conj(A)
-    if (!skinny_gemm(stream, op == 1 || op == 2, op == 1 || op == 3, A, Q, Y, n, m, l))
-        return qsv_fail(QSV_EINVAL, "panel width must be 1..256 columns");
     return QSV_OK;
 }

@@ -9,7 +9,9 @@ instructions, the .amdhsa_ descriptor block, and the kernel's entry in the metad
 and LDS use).  Before the comparison
   * symbols are demangled and namespace qualifiers dropped -- "(anonymous namespace)::k(qsv_layout::BigArgs)" and
     "k(BigArgs)" are the same kernel, so a type or a helper may move into a header's namespace;
-  * comments go, and the function number inside local labels (.LBB12_3 -> .LBB_3, .Lfunc_end12, .LJTI12_0, .Ltmp7).
+  * comments go, and the function number inside local labels (.LBB12_3 -> .LBB_3, .Lfunc_end12, .LJTI12_0, .Ltmp7);
+  * section switches go (.section, .text): after its descriptor a kernel with external linkage returns to .text, one in an
+    anonymous namespace to a section of its own, so a kernel may move into an anonymous namespace.
 Static LDS arrays need no rule: the compiler addresses them by number, and their demangled names do not reach the text.
 Prints the kernel counts, the kernels that exist on one side only and those that differ; exit status 1 if there are any.
 """
@@ -71,7 +73,7 @@ def kernels_of(path: Path, names: dict[str, str], text: str) -> dict[str, dict[s
                 where = "body"
             elif where == "desc":
                 desc.append(normalise(s, names))
-            elif s and not s.startswith((".section", ".p2align")):
+            elif s and s != ".text" and not s.startswith((".section", ".p2align")):
                 n = normalise(l, names).strip()
                 if n:
                     body.append(n)

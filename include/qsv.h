@@ -198,6 +198,22 @@ int qsv_apply_pauli_rotation(qsv_state *st, int k, const int *qubits, const char
  * with no host synchronisation. */
 int qsv_apply_pauli_rotations(qsv_state *st, int n_terms, const int *term_offsets, const int *qubits,
                               const char *paulis, const double *thetas, uint64_t *passes);
+/* The quantum Fourier transform on the ordered qubits qubits[0 .. m-1] (qubits[0] the most significant leg), every other
+ * qubit left alone: psi <- F psi with F[y, x] = 2^(-m/2) exp(+2 pi i x y / 2^m), x = sum_r x_r 2^(m-1-r) -- what
+ * qsv_apply_kq would do with that matrix, for any m <= 64, and numpy.fft.ifft(norm="ortho") along the flattened legs.
+ * flags, combinable: QSV_QFT_INVERSE = the adjoint F^dagger; QSV_QFT_NO_SWAPS = without the final reversal of the m qubits
+ * (with INVERSE: without the initial one); QSV_QFT_CONJUGATE = conj(F) (conj(F^dagger) with INVERSE), which the column side
+ * of a density matrix takes and which differs from the adjoint once the reversal is left out.
+ * Every stage (a Hadamard and its controlled phases) whose qubit lies in one 4096-amplitude tile runs in the same pass over
+ * the register (k_qft_tile; csrc/qsv_qft_plan.h): a full 28-qubit transform is 4 passes and one qubit permutation.
+ * passes (may be NULL) = kernel launches made: tile passes plus the permutation.  The arguments are checked before the
+ * deferred queue is flushed or anything is launched: QSV_EINVAL (null pointer, repeated or out-of-range qubit, unknown flag
+ * bit) leaves the register and the queue as they were; QSV_ESTATE on a mode register; m = 0 does nothing.  The transform
+ * never joins the deferred queue; it works on views. */
+#define QSV_QFT_INVERSE 1
+#define QSV_QFT_NO_SWAPS 2
+#define QSV_QFT_CONJUGATE 4
+int qsv_apply_qft(qsv_state *st, int m, const int *qubits, int flags, uint64_t *passes);
 /* Qubit-axis permutation of the ket: permute_tensor_product (numpy_quantum.py:227-240); the qubit
  * at position j moves to position new_ordering[j]. */
 int qsv_permute(qsv_state *st, const int *new_ordering);

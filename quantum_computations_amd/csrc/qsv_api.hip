@@ -1008,6 +1008,26 @@ int qsv_apply_pauli_rotation(qsv_state *st, int k, const int *qubits, const char
     return qsv_apply_pauli_rotations(st, 1, offsets, qubits, paulis, &theta, nullptr);
 }
 
+int qsv_apply_qft(qsv_state *st, int m, const int *qubits, int flags, uint64_t *passes) {
+    if (!valid(st) || (m > 0 && !qubits)) return qsv_fail(QSV_EINVAL, "null pointer");
+    if (st->kind != 0) return qsv_fail(QSV_ESTATE, "this call needs a qubit register");
+    if (m < 0 || m > 64) return qsv_fail(QSV_EINVAL, "bad number of qubits for the Fourier transform");
+    int rc = check_qubits(st, m, qubits);
+    if (rc) return rc;
+    if (flags & ~(QSV_QFT_INVERSE | QSV_QFT_NO_SWAPS | QSV_QFT_CONJUGATE)) return qsv_fail(QSV_EINVAL, "unknown flag for the Fourier transform");
+    if (passes) *passes = 0;
+    if (m == 0) return QSV_OK;
+    QSV_FLUSH(st);
+    QSV_HIP(hipSetDevice(st->device));
+    std::vector<int> bits(m);
+    for (int r = 0; r < m; ++r) bits[r] = bit_of(st, qubits[r]);
+    uint64_t launches = 0;
+    rc = qsvk_qft(st, m, bits.data(), flags, &launches);
+    if (rc) return rc;
+    if (passes) *passes = launches;
+    return QSV_OK;
+}
+
 // Two registers that one launch reads and writes: qubit registers on one device.  check_disjoint: their first amps_a and
 // amps_b amplitudes (which must lie inside their allocations) do not meet.
 static int check_register_pair(const qsv_state *a, const qsv_state *b) {

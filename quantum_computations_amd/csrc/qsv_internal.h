@@ -189,6 +189,9 @@ int qsvk_pauli_transition_groups(qsv_state *bra, const amp_t *ket, const std::ve
 // the backward walk over a qsv_apply_pauli_rotations plan: values[2 index, 2 index + 1] = <lambda|P|psi>, both registers rewound
 int qsvk_pauli_adjoint_passes(qsv_state *psi, amp_t *lambda, const std::vector<qsv_pauli_rotation_plan::Pass> &passes,
                               const double *cs, const double *sn, double *values);
+// qsv_qft.hip: the Fourier transform on index bits bits[0 .. m-1] (flags: QSV_QFT_*), in place and with no synchronisation;
+// *launches = tile passes plus the permutation
+int qsvk_qft(qsv_state *st, int m, const int *bits, int flags, uint64_t *launches);
 int qsvk_reduced_density(qsv_state *st, int k, const int *bits, double *rho_out);
 int qsvk_expect_density(qsv_state *ket, qsv_state *rho, double *re, double *im);
 int qsvk_sample(qsv_state *st, int shots, const double *u, uint64_t *out);

@@ -414,6 +414,25 @@ class DeviceState:
                   tbuf.ctypes.data_as(C.POINTER(C.c_double)), C.byref(passes))
         return passes.value
 
+    # ---- quantum Fourier transform ---------------------------------------------------------------
+    def apply_qft(self, qubits=None, *, inverse: bool = False, swaps: bool = True) -> "DeviceState":
+        """In-place quantum Fourier transform on the ordered ``qubits`` (``None``: all of them, in order; the first is the
+        most significant leg): ``apply_matrix(npq.qft_matrix(m, inverse, swaps), qubits)`` for any ``m``, in a few tile
+        passes over the register (``qsv_apply_qft``) instead of ``m (m + 1) / 2`` gates.  ``swaps=False`` leaves the
+        reversal of the qubits out.  ``ShardedState`` has no such method: out of scope there."""
+        self._apply_qft(range(self.num_qubits) if qubits is None else qubits, inverse=inverse, swaps=swaps)
+        return self
+
+    def _apply_qft(self, qubits, *, inverse: bool = False, swaps: bool = True, qubit_offset: int = 0,
+                   conjugate: bool = False) -> int:
+        """Launch; returns the number of passes (tile passes plus the permutation).  ``conjugate``: ``conj(F)`` on qubits
+        moved by ``qubit_offset`` (the column side of a density matrix)."""
+        qubits = [int(q) + qubit_offset for q in qubits]
+        flags = (_lib.QFT_INVERSE if inverse else 0) | (0 if swaps else _lib.QFT_NO_SWAPS) | (_lib.QFT_CONJUGATE if conjugate else 0)
+        passes = C.c_uint64()
+        _lib.call("qsv_apply_qft", self._h, len(qubits), _ints(qubits), flags, C.byref(passes))
+        return passes.value
+
     def evolve(self, terms, t: float, steps: int = 1, order: int = 1) -> "DeviceState":
         """Trotterised ``exp(-i t H) ket`` for ``H = sum_t c_t P_t``, ``terms`` as for ``expect_pauli_sum`` (real
         coefficients): ``npq.trotter_rotations`` turned into shared passes by ``apply_pauli_rotations``."""
@@ -771,6 +790,17 @@ class DensityState(DeviceState):
             raise ValueError(f"qubit index out of range for a {n}-qubit register")
         self._pauli_rotations(rotations)
         self._pauli_rotations(rotations, qubit_offset=n, conjugate=True)
+        return self
+
+    def apply_qft(self, qubits=None, *, inverse: bool = False, swaps: bool = True) -> "DensityState":
+        """``F rho F^dagger``: the transform on the row qubits, its complex conjugate on the column qubits ``n + q``
+        (with and without the reversal: ``conj(F)``, not the adjoint)."""
+        n = self.num_qubits
+        qubits = list(range(n)) if qubits is None else [int(q) for q in qubits]
+        if any(not 0 <= q < n for q in qubits):
+            raise ValueError(f"qubit index out of range for a {n}-qubit register")
+        self._apply_qft(qubits, inverse=inverse, swaps=swaps)
+        self._apply_qft(qubits, inverse=inverse, swaps=swaps, qubit_offset=n, conjugate=True)
         return self
 
     def apply_pauli_sum(self, terms, out=None, accumulate: bool = False):

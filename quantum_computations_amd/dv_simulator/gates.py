@@ -250,6 +250,54 @@ class PauliRotation(Gate):
         return out
 
 
+class QFT(Gate):
+    """The quantum Fourier transform on the ordered qubits ``indices`` (the first is the most significant leg):
+    ``npq.qft_matrix(len(indices), inverse, swaps)``.  On a ``DeviceState`` / ``DensityState`` (and on host arrays, which
+    borrow one) it is a few tile passes over the register whatever its width (``apply_qft``).  ``matrix`` is the dense
+    operator for at most six qubits, so that fusion and registers without that method (``distributed.ShardedState``: out
+    of scope) keep working through the matrix path, and ``None`` above: no dense route exists there.
+    ``TrajectoryEnsemble.apply`` needs the matrix, so an ensemble takes a ``QFT`` of at most six qubits."""
+
+    MAX_DENSE = 6                    # qsv_apply_kq takes matrices on at most six qubits (include/qsv.h)
+    result_dtype = np.complex128     # what the gate contributes to NumPy's promotion when it has no matrix
+
+    def __init__(self, indices: list[int], inverse: bool = False, swaps: bool = True):
+        indices = list(indices)
+        matrix = npq.qft_matrix(len(indices), inverse, swaps) if 1 <= len(indices) <= self.MAX_DENSE else None
+        super().__init__(indices, matrix)
+        self.inverse = bool(inverse)
+        self.swaps = bool(swaps)
+
+    def __repr__(self):
+        return super().__repr__() + ("^dagger" if self.inverse else "") + ("" if self.swaps else "[no swaps]")
+
+    def apply(self, state):
+        if is_device_register(state):
+            if hasattr(state, "apply_qft"):
+                return state.apply_qft(self.indices, inverse=self.inverse, swaps=self.swaps)
+            if self.matrix is None:
+                raise ValueError(f"{type(state).__name__} has no apply_qft and {self} has no dense matrix.")
+            return super().apply(state)
+        state = np.asarray(state)
+        if state.ndim not in (1, 2):
+            raise ValueError("State has wrong dimensions.")
+        flat = np.ascontiguousarray(state).reshape(-1)
+        dev = _borrow_register(flat)
+        size = DeviceState.num_qubits.fget(dev)
+        try:
+            if state.ndim == 2 and any(not 0 <= q < size // 2 for q in self.indices):
+                raise ValueError(f"qubit index out of range for a {size // 2}-qubit register")
+            dev._apply_qft(self.indices, inverse=self.inverse, swaps=self.swaps)
+            if state.ndim == 2:      # F rho F^dagger: conj(F) on the column qubits, as DensityState does
+                dev._apply_qft(self.indices, inverse=self.inverse, swaps=self.swaps, qubit_offset=size // 2, conjugate=True)
+            out = dev.to_numpy().reshape(state.shape)
+        except BaseException:
+            dev.close()
+            raise
+        _return_register(dev, size)
+        return out
+
+
 def _fixed_2q(name: str, matrix_of, doc: str, **extra):
     def __init__(self, first, second):
         TwoQubitGate.__init__(self, first, second, matrix_of())

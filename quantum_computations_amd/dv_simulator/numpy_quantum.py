@@ -599,6 +599,20 @@ def expand_gate(gate: np.ndarray, N: int, targets) -> np.ndarray:
     return permute_tensor_product(padded, targets + spectators)
 
 
+def qft_matrix(m: int, inverse: bool = False, swaps: bool = True) -> np.ndarray:
+    """Dense quantum Fourier transform on ``m`` qubits (leg 0 most significant): ``F[y, x] = 2^(-m/2) exp(+2 pi i x y /
+    2^m)``, ``numpy.fft.ifft(norm="ortho")`` as a matrix.  ``swaps=False`` leaves the final reversal of the qubits out
+    (the rows come out bit-reversed); ``inverse`` is the adjoint of either."""
+    dim = 1 << m
+    index = np.arange(dim, dtype=np.int64)
+    turns = np.multiply.outer(index, index) % dim          # x y mod 2^m, exact
+    matrix = np.exp(2j * np.pi * turns / dim) / np.sqrt(dim)
+    if not swaps:
+        reverse = np.array([int(format(y, f"0{m}b")[::-1], 2) if m else 0 for y in range(dim)])
+        matrix = matrix[reverse, :]
+    return matrix.conj().T if inverse else matrix
+
+
 def add_control(gate: np.ndarray) -> np.ndarray:
     """``|0><0| x I + |1><1| x gate``."""
     dim = gate.shape[0]

@@ -44,6 +44,8 @@ def to_gates(ops: list[dict]) -> list:
             gate = G.M(idx[0], o["theta"], o["phi"], result=o.get("result"))
         elif name == "Insert":
             gate = G.Insert(idx[0], State[o["state"]])
+        elif name == "MCPhase":
+            gate = MCPhase(idx, o["phase"])
         else:
             gate = G.Gate(list(idx), np.asarray(o["matrix"]))
         ctl = o.get("control")
@@ -139,6 +141,28 @@ class MCPhase:
         out = dev.to_numpy()
         dev.close()
         return out
+
+
+def qft_ops(qubits, inverse: bool = False, swaps: bool = True, conjugate: bool = False) -> list[dict]:
+    """The quantum Fourier transform on the ordered ``qubits`` spelled gate by gate, as an op list: for each qubit a
+    Hadamard followed by the phases ``exp(2 pi i / 2^(s - r + 1))`` controlled by every later qubit (two-qubit
+    ``MCPhase`` ops, which carry their 4 x 4 diagonal for the oracle), then ``m // 2`` SWAPs: ``m (m + 1) / 2 + m // 2``
+    gates, what ``apply_qft`` does in a few passes.  ``inverse``: the same list backwards with the phases conjugated;
+    ``conjugate``: the phases conjugated (``conj(F)``)."""
+    qubits = [int(q) for q in qubits]
+    m = len(qubits)
+    ops = []
+    for r in range(m):
+        ops.append(op("H", qubits[r]))
+        for s in range(r + 1, m):
+            # 2^(m-1-s) / 2^(m-r) of a turn, conjugated for the adjoint and for conj(F); the eighth roots come out of
+            # np.exp as they are (no exact table needed at the tolerances the spelling is compared at)
+            turn = 1.0 / (1 << (s - r + 1))
+            phase = complex(np.exp(2j * np.pi * (-turn if inverse != conjugate else turn)))
+            ops.append({"name": "MCPhase", "indices": [qubits[s], qubits[r]], "matrix": np.diag([1.0, 1.0, 1.0, phase]),
+                        "phase": phase})
+    tail = [op("SWAP", qubits[r], qubits[m - 1 - r]) for r in range(m // 2)] if swaps else []
+    return (tail + ops[::-1]) if inverse else (ops + tail)
 
 
 def grover_circuit(n: int, marked: int, iterations: int) -> list:

@@ -1,6 +1,7 @@
 // C ABI of libqsv.so (include/qsv.h): argument validation, qubit -> bit mapping, kernel selection.
-// The device work lives in qsv_kernels.hip (qubit gates), qsv_readout.hip (measurement, reshaping, reductions),
-// qsv_pauli.hip (Pauli sums and rotations) and qsv_qudit.hip (d-level modes).
+// The device work lives in qsv_gate12.hip, qsv_gatek.hip, qsv_sequence.hip and qsv_pass.hip (qubit gates), qsv_state.hip
+// (staging ring, spare buffer, copy), qsv_readout.hip (measurement, reshaping, reductions), qsv_pauli.hip (Pauli sums and
+// rotations) and qsv_qudit.hip (d-level modes).
 
 #include "qsv_internal.h"
 #include "qsv_plan.h"

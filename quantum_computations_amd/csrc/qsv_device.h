@@ -1,6 +1,7 @@
-// Device and host helpers shared by the qubit-register translation units of libqsv.so (qsv_kernels.hip: gates,
-// qsv_readout.hip: measurement / reshaping / reductions, qsv_pauli.hip: Pauli sums and rotations).  Everything here is
-// static: each translation unit compiles its own copy.
+// Device and host helpers shared by the qubit-register translation units of libqsv.so (the gate families qsv_gate12.hip,
+// qsv_gatek.hip, qsv_sequence.hip and qsv_pass.hip, qsv_state.hip: staging ring / spare buffer / copy, qsv_readout.hip:
+// measurement / reshaping / reductions, qsv_pauli.hip: Pauli sums and rotations).  Everything here is static: each
+// translation unit compiles its own copy.  No __global__ function lives here: a kernel is defined in exactly one .hip file.
 #pragma once
 
 #include "qsv_internal.h"
@@ -97,6 +98,11 @@ static __device__ __forceinline__ uint64_t deposit(uint64_t w, const Args &g) {
     return w | g.or_mask;
 }
 
+// The LDS rows of k_dense_lds and k_seq_lds are private to a wave (a wave exchanges data with itself only), and the LDS
+// executes one wave's instructions in order: no workgroup barrier is needed, only the compiler must keep the program order
+// of the accesses (it does: they may alias) -- wave_sync() marks the spots.
+static __device__ __forceinline__ void wave_sync() { __builtin_amdgcn_wave_barrier(); }
+
 static __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -127,20 +133,28 @@ static __device__ __forceinline__ void block_sum2(double &x, double &y) {
 // ----------------------------------------------------------------------------------------------------
 // host-side helpers
 // ----------------------------------------------------------------------------------------------------
-static int grid_for(uint64_t items, int per_block, int cap) {
-    uint64_t blocks = (items + per_block - 1) / per_block;
-    if (blocks < 1) blocks = 1;
-    if (cap > 0 && blocks > static_cast<uint64_t>(cap)) blocks = cap;
-    // an AQL dispatch counts work-ITEMS in 32 bits: at most 2^32 / 256 workgroups of 256 threads per launch
-    // (a 33-qubit register would need 2^25); every kernel launched through here loops over the remainder
-    if (blocks > 0x00ffffffull) blocks = 0x00ffffffull;
-    return static_cast<int>(blocks);
-}
+using qsv_layout::grid_for;   // workgroups of a grid-stride launch: with the launch rules it feeds, in qsv_layout.h
 
 static int check_launch() {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return qsv_fail(QSV_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return QSV_OK;
+}
+
+// The dispatches of one launch of g.W work items, at most `limit` each: launch(count) with g.w0 set to the range's start.
+template <class Args, class Launch>
+static int launch_ranges(Args &g, uint64_t limit, Launch &&launch) {
+    for (const qsv_layout::Range &r : qsv_layout::dispatch_ranges(g.W, limit)) {
+        g.w0 = r.w0;
+        launch(r.count);
+        const int rc = check_launch();
+        if (rc) return rc;
+    }
+    return QSV_OK;
+}
+
+static uint32_t regions_or(const qsv_state *st, uint32_t by_default) {   // QSV_OPT_REMAP overrides a form's tile order
+    return st->remap >= 0 ? static_cast<uint32_t>(st->remap) : by_default;
 }
 
 // Sum the first `blocks` pairs of partials on the host, in index order (deterministic).

@@ -135,7 +135,7 @@ constexpr int QSV_REDUCE_BLOCKS = 1024;
 constexpr int QSV_STAGE_SLOTS = 8;
 constexpr size_t QSV_STAGE_BYTES = 512u << 10;
 
-// A gate's matrix / tables on their way to the device without a host-side wait (see qsvk_stage in qsv_kernels.hip).
+// A gate's matrix / tables on their way to the device without a host-side wait (see qsvk_stage in qsv_state.hip).
 struct StageRef {
     char *dev = nullptr;   // device address of part A; part B follows at pad16(bytes of A)
     int slot = -1;         // ring slot, or -1: the data went through st->dev_matrix with a synchronous copy
@@ -153,8 +153,8 @@ int qsv_fail(int code, const std::string &msg);
             return qsv_fail(QSV_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e));               \
     } while (0)
 
-// launchers (qsv_kernels.hip: gates and state plumbing, qsv_readout.hip, qsv_pauli.hip, qsv_qudit.hip); all enqueue on
-// st->stream
+// launchers (qsv_gate12.hip, qsv_gatek.hip, qsv_sequence.hip, qsv_pass.hip: gates; qsv_state.hip: state plumbing;
+// qsv_readout.hip, qsv_pauli.hip, qsv_qudit.hip); all enqueue on st->stream
 int qsvk_copy(amp_t *dst, const amp_t *src, uint64_t amps, hipStream_t stream);   // nontemporal copy kernel
 int qsvk_dense(qsv_state *st, int k, const int *bits, int nctrl, const int *cbits, const double *m_user);
 int qsvk_pair_exchange(qsv_state *st, int bit_a, int bit_b);  // SWAP on two high bits (moves 1/2 of the state)

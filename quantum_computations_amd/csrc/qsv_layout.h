@@ -1,5 +1,6 @@
-// Host-side layouts of the dense-gate launchers (qsv_kernels.hip): plain C++, no HIP, so that the host tests can compile
-// it alone (tests/test_layout_host.py).  The read-out and Pauli launchers have qsv_readout_layout.h.
+// Host-side layouts and launch rules of the gate launchers (qsv_gate12.hip, qsv_gatek.hip, qsv_sequence.hip,
+// qsv_pass.hip): plain C++, no HIP, so that the host tests can compile it alone (tests/test_layout_host.py).  The read-out
+// and Pauli launchers have qsv_readout_layout.h.
 //
 // A launcher chooses a kernel form, asks this header for the tables of that form, stages them, fills the kernel's argument
 // struct and launches over the dispatch ranges.  Everything here is integer and index arithmetic on three index spaces:
@@ -463,6 +464,95 @@ inline std::vector<Range> dispatch_ranges(uint64_t W, uint64_t limit) {
     std::vector<Range> out;
     for (uint64_t w0 = 0; w0 < W; w0 += limit) out.push_back(Range{w0, std::min(limit, W - w0)});
     return out;
+}
+
+// Workgroups of a grid-stride launch over `items` work items, `per_block` each, at most `cap` (0: no cap).
+inline int grid_for(uint64_t items, int per_block, int cap) {
+    uint64_t blocks = (items + per_block - 1) / per_block;
+    if (blocks < 1) blocks = 1;
+    if (cap > 0 && blocks > static_cast<uint64_t>(cap)) blocks = cap;
+    // an AQL dispatch counts work-ITEMS in 32 bits: at most 2^32 / 256 workgroups of 256 threads per launch
+    // (a 33-qubit register would need 2^25); every kernel launched through here loops over the remainder
+    if (blocks > 0x00ffffffull) blocks = 0x00ffffffull;
+    return static_cast<int>(blocks);
+}
+
+// ---- launch rules of the register forms of 1- and 2-qubit gates (k_dense, k_dense_ctrl, k_diag) -------------------------
+// What launch_dense and launch_diag (qsv_gate12.hip) put around their launch: the items a thread keeps in flight, the
+// distance between them, the tile order and the grid.  All figures are MI355X at n = 28, from the sweeps under profiles/.
+struct LaunchOptions {          // the register's options; the defaults are qsv_state's
+    int unroll = 0;             // QSV_OPT_UNROLL: items per thread, 0 = the rule's choice
+    int remap = -1;             // QSV_OPT_TILE_REGIONS: tile order, -1 = the rule's choice
+    int ubit = 8;               // QSV_OPT_ITEM_STRIDE_BIT
+    int grid_cap = 0;           // QSV_OPT_GRID_CAP
+};
+struct Launch12 {
+    int U = 1;                  // items per thread, after the default choice and the halving for small W
+    int ubit = 8;               // GateArgs::ubit after the clamp (k_diag's items are always back to back: left as given)
+    int remap = 0;              // GateArgs::remap / DiagArgs::remap: tile-order regions
+    int grid = 1;               // workgroups
+};
+
+// The pair strides of a dense launch: hbit[i] = address bit of high target i (the top set bit of GateArgs::hoff[1 << i]).
+struct PairStrides {
+    bool far = false;           // some stride is 16 MiB .. 512 MiB (bits 20..25)
+    int top = 0;                // the highest target bit
+};
+inline PairStrides pair_strides(int KH, const int *hbit) {
+    PairStrides s;
+    for (int i = 0; i < KH; ++i) {
+        s.far = s.far || (hbit[i] >= 20 && hbit[i] <= 25);
+        s.top = std::max(s.top, hbit[i]);
+    }
+    return s;
+}
+
+// Work items in flight per thread: with nontemporal accesses one item per thread streams best (6.0-6.4 TB/s) until the
+// pair stride reaches 16 MiB (bit 20), where four items per thread hold 5.8 TB/s and one item drops to 5.4.
+inline int dense_default_unroll(int KH, int KL, const PairStrides &s) {
+    if (KH == 0) return KL == 2 ? 2 : 1;
+    if (KH == 1 && KL == 1) return 1;   // round 2 re-sweep: one item per thread at every stride (1.35-1.44 against 1.50-1.53 ms on bits 20..25)
+    // single far pair stride: only 16 MiB (bit 20) wants four items per thread (profiles/r01_sweep_far_bits.txt)
+    if (KH == 1 && KL == 0) return s.top == 20 ? 4 : 1;
+    return s.far ? 4 : 1;
+}
+
+// Tile order (profiles/r01_sweep_tile_order.txt): natural-order kernels like 32 regions, pair kernels 8 (one per XCD),
+// except at pair strides of 16..512 MiB where the plain order is best.  `sub`: a controlled or pair-exchange launch.
+inline int dense_default_regions(int KH, int KL, bool sub, const PairStrides &s) {
+    if (sub) return 0;                                  // controlled / pair-exchange launches: plain order
+    if (KH == 0) return KL == 2 ? 0 : 32;               // round 2 re-sweep (tools/probe_low_pairs.py): 1.35 against 1.41 ms
+    if (KH == 1 && KL == 0) return s.top == 20 ? 0 : s.top == 24 ? 2 : 8;   // per-stride winners of the sweeps
+    if (KH == 1) return (s.top == 20 || s.top == 24) ? 32 : 8;              // KL = 1; round 2 re-sweep (tools/probe_retune.py)
+    return s.top < 20 ? 8 : 0;
+}
+
+inline int halved_for(int U, uint64_t W) {   // never more unrolling than there is work for one tile
+    while (U > 1 && W < static_cast<uint64_t>(BLOCK) * U) U >>= 1;
+    return U;
+}
+
+// k_dense<KH, KL> / k_dense_ctrl<KH, KL> over W work items.
+inline Launch12 dense_launch(int KH, int KL, const int *hbit, bool sub, uint64_t W, const LaunchOptions &o) {
+    const PairStrides s = pair_strides(KH, hbit);
+    Launch12 l;
+    l.U = halved_for(o.unroll > 0 ? o.unroll : dense_default_unroll(KH, KL, s), W);
+    l.remap = o.remap >= 0 ? o.remap : dense_default_regions(KH, KL, sub, s);
+    l.ubit = o.ubit;
+    while (l.ubit > 8 && (W >> l.ubit) < static_cast<uint64_t>(l.U)) --l.ubit;   // small registers
+    l.grid = grid_for(W, BLOCK * l.U, o.grid_cap);
+    return l;
+}
+
+// k_diag over W work items.  Full traffic: one item per thread, 32 regions; sub-space launches (Z, CZ, multi-controlled
+// phases): four items per thread, one region per XCD (profiles/r01_sweep_sub_kernels.txt).
+inline Launch12 diag_launch(bool sub, uint64_t W, const LaunchOptions &o) {
+    Launch12 l;
+    l.U = halved_for(o.unroll > 0 ? o.unroll : (sub ? 4 : 1), W);
+    l.remap = o.remap >= 0 ? o.remap : (sub ? 8 : 32);
+    l.ubit = o.ubit;
+    l.grid = grid_for(W, BLOCK * l.U, o.grid_cap);
+    return l;
 }
 
 // ---- form of a dense k-qubit gate (qsvk_generic) -----------------------------------------------------------------------

@@ -1,5 +1,5 @@
 // The quantum Fourier transform on a qubit register (qsv_apply_qft): every stage whose qubit lies in an LDS-resident tile
-// runs in the same pass over HBM (k_qft_tile, modelled on k_pass_tile of qsv_kernels.hip); the planning arithmetic and the
+// runs in the same pass over HBM (k_qft_tile, modelled on k_pass_tile of qsv_pass.hip); the planning arithmetic and the
 // statement of the twiddle angles are qsv_qft_plan.h.  The reversal of the qubits goes through qsvk_permute.
 //
 // Twiddles.  Stage r multiplies by t = exp(2 pi i T / 2^L) with T = X mod 2^(L-1), X the integer the transform's qubits

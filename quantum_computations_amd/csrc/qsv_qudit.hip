@@ -513,7 +513,7 @@ int launch_axis(int device, hipStream_t stream, const amp_t *in, amp_t *out, uin
     return check_launch();
 }
 
-// The spare buffer (`fresh`) now holds the register: swap it in (qsv_kernels.hip::qsvk_adopt).
+// The spare buffer (`fresh`) now holds the register: swap it in (qsv_state.hip::qsvk_adopt).
 int adopt(qsv_state *st, amp_t *fresh) {
     (void)fresh;
     return qsvk_adopt(st, st->amps);

@@ -14,6 +14,7 @@
 //   tilecut n k ngates bits.. {arity leg0 leg1 m..}..  -> status | tile_bits.. | passes {first count q0..q3}.. | {code m[0..32)}..
 //   limits                                   -> DISPATCH_TILES DISPATCH_ITEMS TILE_SEQ_MAX_PASSES
 //   ranges W limit                           -> {w0 count}..
+//   launch12 KH KL sub W unroll remap ubit cap hbit0 hbit1  -> U ubit remap grid   (KH < 0: the diagonal launch, k_diag)
 //   form n k real variant complex_product mtile bits..  -> form transposed realm m3
 //   pass n tile_high count {kind k b0 b1 nctrl cbits.. m[0..32)}..
 //                                            -> status | tile_bits.. | groups {first count q0..q3 gates}.. | {form code rc tc tz0 tz1 omask m[0..32)}..
@@ -181,6 +182,15 @@ int main() {
             in >> W >> limit;
             for (const Range &r : dispatch_ranges(W, limit))
                 std::printf(" %llu %llu", static_cast<unsigned long long>(r.w0), static_cast<unsigned long long>(r.count));
+        } else if (what == "launch12") {
+            int KH, KL, sub, hbit[2];
+            LaunchOptions o;
+            in >> KH >> KL >> sub;
+            const unsigned long long W = u64(in);
+            in >> o.unroll >> o.remap >> o.ubit >> o.grid_cap >> hbit[0] >> hbit[1];
+            if (KH > 2) return 3;
+            const Launch12 l = KH < 0 ? diag_launch(sub != 0, W, o) : dense_launch(KH, KL, hbit, sub != 0, W, o);
+            std::printf("%d %d %d %d", l.U, l.ubit, l.remap, l.grid);
         } else if (what == "form") {
             int n, k, real, variant, cp, mtile;
             in >> n >> k >> real >> variant >> cp >> mtile;

@@ -8,9 +8,9 @@ applies the same operations to both.
    the cache hint of loads and stores, never the arithmetic of an amplitude.  Exceptions, found by reading the launchers:
 
    * An explicit QSV_OPT_UNROLL takes 1-qubit gates (plain or controlled) off the workgroup-tile form and onto the register
-     form (qsvk_dense, qsv_kernels.hip:2061).  With the target on bits 3..5 that is k_dense_tile12<1>, which sums the two
-     matrix columns in index order (tile12_body, :1355), against k_dense<0, 1, U> / k_dense_ctrl<0, 1, U>, whose lanes add
-     their OWN amplitude first and the partner's second (dense_body, :101-106): the lanes with the target bit set sum in
+     form (qsvk_dense in qsv_gate12.hip).  With the target on bits 3..5 that is k_dense_tile12<1>, which sums the two
+     matrix columns in index order (tile12_body), against k_dense<0, 1, U> / k_dense_ctrl<0, 1, U>, whose lanes add
+     their OWN amplitude first and the partner's second (dense_body): the lanes with the target bit set sum in
      the other order.  Those gates are held to the oracle alone, and the register under test is then overwritten with the
      default one so that the next gate starts from equal bits.  On every other placement the two forms sum alike and are
      compared bit for bit.
@@ -108,8 +108,8 @@ def tf(flag):
 
 # ---- per-gate kernels -----------------------------------------------------------------------------------------------------------
 def launch_model(W_items, unroll, regions, ubit, cap):
-    """launch_dense (qsv_kernels.hip:830-857) for W work items: (U after halving, stride bit after the clamp, tiles,
-    whether the tile order is a real permutation, trips of the grid-stride loop)."""
+    """launch_dense (qsv_gate12.hip; its rules are qsv_layout::dense_launch) for W work items: (U after halving, stride
+    bit after the clamp, tiles, whether the tile order is a real permutation, trips of the grid-stride loop)."""
     U = max(unroll, 1)
     while U > 1 and W_items < BLOCK * U:
         U >>= 1
@@ -392,7 +392,7 @@ def test_per_gate_default_register_of_each_pass_circuit_agrees_with_the_oracle(n
     assert err < GATE_TOL * scale_of(want)
 
 
-# the tile order is a real permutation when tiles % R == 0 and tiles > R (k_pass_tile, qsv_kernels.hip:1822); -1 is the
+# the tile order is a real permutation when tiles % R == 0 and tiles > R (tile_id in k_pass_tile, qsv_pass.hip); -1 is the
 # built-in 8 regions: engaged at n = 16 (16 tiles) and n = 18 (64), the identity on the 8 tiles of n = 15, where R = 2 is
 # engaged; R = 16 is engaged at n = 18 only (the identity on 16 tiles, not a divisor of 8)
 @pytest.mark.parametrize("nt", [0, 1])

@@ -5,7 +5,9 @@ answers come back as text.  Every check compares the header with a NumPy model w
 bits, offset tables and the five matrix layouts end to end (gather, multiply, scatter on a 10-qubit state against the
 oracle), the low-bit fields of the line-granular forms, SeqGate records, the pass cutter of k_seq_tile, the dispatch
 ranges of split launches, the gate records of a k_pass_tile pass (executed by the model of test_defer_groups_host.py, bit
-for bit against the gates applied one by one) and the choice of kernel form.
+for bit against the gates applied one by one), the choice of kernel form, and the launch rules of the 1- and 2-qubit
+register forms (items per thread, stride bit, tile order, grid) against a model of the launchers they were lifted from and
+against the figures tests/test_gpu_options.py holds last_kernel() to.
 """
 from __future__ import annotations
 
@@ -472,3 +474,139 @@ def test_form_selection(ask):
         assert (got[0], bool(got[1]), bool(got[2]), bool(got[3])) == want, (n, k, variant, real, bits, got, want)
         seen.add(got[0])
     assert seen == set(range(6))
+
+
+# ---- launch rules of the 1- and 2-qubit register forms ----------------------------------------------------------------------
+# The model is the parent commit's launch_dense / default_unroll / launch_diag (then inline in the gate-kernel file), kept
+# in their shape: the far-stride scan once in default_unroll and once more in launch_dense, the single-stride special case,
+# the halving loop, the tile-order table, the stride-bit clamp, grid_for.
+BLOCK = 256
+
+
+def parent_grid_for(items, per_block, cap):
+    blocks = max((items + per_block - 1) // per_block, 1)
+    if cap > 0:
+        blocks = min(blocks, cap)
+    return min(blocks, 0x00FFFFFF)
+
+
+def parent_default_unroll(KH, KL, hbit):
+    if KH == 0:
+        return 2 if KL == 2 else 1
+    far = False
+    for b in hbit[:KH]:
+        far = far or 20 <= b <= 25
+    if KH == 1 and KL == 1:
+        return 1
+    if KH == 1 and KL == 0 and far:
+        return 4 if hbit[0] == 20 else 1
+    return 4 if far else 1
+
+
+def parent_launch_dense(KH, KL, hbit, sub, W, unroll, remap, ubit, cap):
+    U = unroll if unroll > 0 else parent_default_unroll(KH, KL, hbit)
+    while U > 1 and W < BLOCK * U:
+        U >>= 1
+    if remap >= 0:
+        regions = remap
+    else:
+        top = 0
+        for b in hbit[:KH]:
+            top = max(top, b)
+        if sub:
+            regions = 0
+        elif KH == 0:
+            regions = 0 if KL == 2 else 32
+        elif KH == 1 and KL == 0:
+            regions = 0 if top == 20 else 2 if top == 24 else 8
+        elif KH == 1:
+            regions = 32 if top in (20, 24) else 8
+        else:
+            regions = 8 if top < 20 else 0
+    while ubit > 8 and (W >> ubit) < U:
+        ubit -= 1
+    return U, ubit, regions, parent_grid_for(W, BLOCK * U, cap)
+
+
+def parent_launch_diag(sub, W, unroll, remap, ubit, cap):
+    regions = remap if remap >= 0 else (8 if sub else 32)
+    U = unroll if unroll > 0 else (4 if sub else 1)
+    while U > 1 and W < BLOCK * U:
+        U >>= 1
+    return U, ubit, regions, parent_grid_for(W, BLOCK * U, cap)      # k_diag has no stride bit: passed through
+
+
+def launch12_line(KH, KL, hbit, sub, W, unroll, remap, ubit, cap):
+    return f"launch12 {KH} {KL} {int(sub)} {W} {unroll} {remap} {ubit} {cap} {hbit[0]} {hbit[1]}"
+
+
+def launch12_cases():
+    """(KH, KL, hbit, sub, W, unroll, remap, ubit, cap); KH = -1 is the diagonal launch."""
+    unset = (0, -1, 8, 0)
+    one_at_a_time = [unset] + [(u, -1, 8, 0) for u in (1, 2, 4, 8)] + [(0, r, 8, 0) for r in (0, 2, 8, 32)] \
+        + [(0, -1, b, 0) for b in (8, 10, 12)] + [(0, -1, 8, c) for c in (0, 3, 7)]
+    product = list(itertools.product((0, 1, 2, 4, 8), (-1, 0, 2, 8, 32), (8, 10, 12), (0, 3, 7)))
+    placements = []
+    for b in range(6, 28):                                     # every high-target position, alone and as one of a pair
+        placements += [(1, 0, (b, 0)), (1, 1, (b, 0))]
+        placements += [(2, 0, pair) for other in (6, 20, 23, 27) if other != b for pair in ((b, other), (other, b))]
+    placements += [(0, 1, (0, 0)), (0, 2, (0, 0)), (-1, 0, (0, 0))]
+    for KH, KL, hbit in placements:
+        # the full product of the options on a sample of placements (a near, a 16 MiB and a 256 MiB stride), one option
+        # at a time on the others
+        combined = KH <= 0 or (KH == 1 and hbit[0] in (6, 20, 24)) or hbit in ((7, 6), (20, 23), (6, 24))
+        for options in (product if combined else one_at_a_time):
+            for sub in (False, True):
+                for logw in range(7, 28):
+                    yield (KH, KL, hbit, sub, 1 << logw, *options)
+
+
+def test_launch_rules_of_the_register_forms(ask):
+    cases = list(launch12_cases())
+    answers = ask([launch12_line(*c) for c in cases])
+    tops, halved, clamped = set(), set(), set()
+    for case, (ans,) in zip(cases, answers):
+        KH, KL, hbit, sub, W, unroll, remap, ubit, cap = case
+        want = parent_launch_diag(sub, W, unroll, remap, ubit, cap) if KH < 0 else parent_launch_dense(*case)
+        assert tuple(nums(ans)) == want, (case, nums(ans), want)
+        if KH > 0 and remap < 0 and not unroll:
+            top = max(hbit[:KH])
+            tops.add("<20" if top < 20 else "21..23" if 21 <= top <= 23 else ">25" if top > 25 else str(top))
+        start = unroll or ((4 if sub else 1) if KH < 0 else parent_default_unroll(KH, KL, hbit))     # U before the halving
+        if start > 1:
+            halved.add(want[0] < start)
+        if KH >= 0 and ubit > 8:
+            clamped.add(want[1] < ubit)
+    assert {(c[0], c[1]) for c in cases} == {(1, 0), (0, 1), (2, 0), (1, 1), (0, 2), (-1, 0)}
+    assert tops == {"<20", "20", "21..23", "24", "25", ">25"}, tops
+    assert halved == {False, True} and clamped == {False, True}, "the U halving and the stride-bit clamp both fire and both do not"
+
+
+def gpu_option_settings():
+    """SETTINGS of tests/test_gpu_options.py, read from its source (importing the module would load the GPU library)."""
+    import ast
+    tree = ast.parse((hostcheck.HERE / "test_gpu_options.py").read_text())
+    for node in tree.body:
+        if isinstance(node, ast.Assign) and [getattr(t, "id", None) for t in node.targets] == ["SETTINGS"]:
+            return ast.literal_eval(node.value)
+    raise AssertionError("SETTINGS not found in tests/test_gpu_options.py")
+
+
+def test_launch_rules_give_what_the_gpu_option_settings_record(ask):
+    """Rows A..N of SETTINGS: the (U, stride bit, tiles) that test_gpu_options.py holds last_kernel() to, asked of the header."""
+    rows = [s for s in gpu_option_settings() if s[7] is not None]
+    assert [s[0] for s in rows] == list("ABCDEFGHIJMN")
+    requests, wants = [], []
+    for name, n, nt, unroll, regions, ubit, cap, high, low in rows:
+        for kind, W, want in (((1, 0), 1 << (n - 1), high), ((0, 1), 1 << n, low), ((-1, 0), 1 << n, low)):
+            requests.append(launch12_line(kind[0], kind[1], (n - 1, 0), False, W, unroll, regions, ubit, cap))
+            wants.append((name, kind, W, cap, want))
+    for (name, kind, W, cap, want), (ans,) in zip(wants, ask(requests)):
+        U, stride_bit, remap, grid = nums(ans)
+        tiles = -(-W // (BLOCK * U))
+        assert grid == (min(tiles, cap) if cap else tiles), (name, kind)
+        trips = -(-tiles // grid)
+        if kind[0] < 0:                                        # k_diag has no stride bit
+            assert (U, tiles, trips) == (want[0], want[2], want[4]), (name, kind)
+        else:
+            assert (U, stride_bit, tiles, trips) == (want[0], want[1], want[2], want[4]), (name, kind)

@@ -2,7 +2,9 @@
 """Are the kernels of two builds the same device code?  For refactors that move kernels between translation units.
 
     hipcc <the flags build.py gives the file> --cuda-device-only -S old/qsv_kernels.hip -o old.s      (and so on)
-    python tools/device_code_diff.py --old old.s --new kernels.s readout.s pauli.s
+    python tools/device_code_diff.py --old old.s --new gate12.s gatek.s sequence.s pass.s state.s
+
+(the split of the gate-kernel file qsv_kernels.hip into its five families; profiles/r11_gate_split_device_code.txt)
 
 Each side is a list of assembly files whose kernels are pooled.  Per kernel three things are compared as text: the
 instructions, the .amdhsa_ descriptor block, and the kernel's entry in the metadata (argument offsets and sizes, register

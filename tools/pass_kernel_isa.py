@@ -2,8 +2,8 @@
 """What the compiler made of k_pass_tile: registers, and the instruction mix of every basic block that does gate arithmetic.
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Iquantum_computations_amd/csrc --cuda-device-only -S \
-          quantum_computations_amd/csrc/qsv_kernels.hip -o kernels.s
-    python tools/pass_kernel_isa.py kernels.s [--kernel k_pass_tileILb1E]
+          -mllvm -structurizecfg-skip-uniform-regions quantum_computations_amd/csrc/qsv_pass.hip -o pass.s
+    python tools/pass_kernel_isa.py pass.s [--kernel k_pass_tileILb1E]
 
 A gate body is one basic block (no control on register bits) or one block per register index (with such controls), so the
 blocks are listed by their instruction mix: how many blocks have it, FMAs, v_cndmask (selects), vector moves (copies of

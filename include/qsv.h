@@ -214,6 +214,43 @@ int qsv_apply_pauli_rotations(qsv_state *st, int n_terms, const int *term_offset
 #define QSV_QFT_NO_SWAPS 2
 #define QSV_QFT_CONJUGATE 4
 int qsv_apply_qft(qsv_state *st, int m, const int *qubits, int flags, uint64_t *passes);
+
+/* ---- reversible register arithmetic: classical maps on the value of a qubit register ---- */
+/* A map acts on the integer y that m TARGET qubits spell (the first listed qubit the most significant, as in qsv_apply_qft),
+ * may read the integer x of mx SOURCE qubits, which it leaves alone, and acts only where every control qubit is 1.  It is a
+ * permutation of basis states, so applying it is one gather pass over the register -- the traffic of a copy, no floating-
+ * point operation, bit-exact amplitudes.  M is the modulus (0 stands for 2^m); values y >= M stay where they are.
+ *   QSV_ARITH_ADD         y -> (y + c) mod M                              m <= 32, mx = 0
+ *   QSV_ARITH_MUL         y -> (a y) mod M, gcd(a, M) = 1                 m <= 32, mx = 0
+ *   QSV_ARITH_ADD_REG     y -> (y + a x + c) mod M                        m, mx <= 32
+ *   QSV_ARITH_MUL_POW     y -> (y a^x) mod M, gcd(a, M) = 1               m <= 32, 1 <= mx <= 24
+ *   QSV_ARITH_XOR_LOOKUP  y -> y xor table[x], 2^mx entries below 2^m     m <= 32, 1 <= mx <= 24, no modulus
+ *   QSV_ARITH_PERMUTE     y -> table[y], a bijection of 0 .. 2^m - 1      m <= 24, mx = 0, no modulus
+ * qsv_arith_create validates everything, forms the inverse map of the same family (M - c, the modular inverse of a, the
+ * table of inverse powers, the inverted table) and keeps both on `device`; an argument a kind does not use must be 0 / NULL.
+ * QSV_EINVAL with a message for: an unknown kind; m or mx out of range; a, c or a table entry out of range; M < 2 or
+ * M > 2^m; gcd(a, M) != 1; a table that is no bijection; a wrong table_len; a null pointer.
+ * qsv_apply_arith applies the map (QSV_ARITH_INVERSE in flags: its inverse) with target[0 .. m-1], source[0 .. mx-1] (NULL
+ * when mx = 0) and n_controls control qubits; a qubit may appear once in the three lists together.  QSV_EINVAL for null
+ * pointers, a handle on another device, repeated or out-of-range qubits, unknown flag bits; QSV_ESTATE for a mode register:
+ * each before the deferred queue is flushed or anything is launched.  The result is written to the register's spare buffer
+ * and swapped in (copied back into a view, whose pointer stays).  passes (may be NULL) = kernel launches made: 1, or 0 for
+ * a map that moves nothing (ADD with c = 0, MUL with a = 1, ...).  A handle may be used any number of times and by any
+ * register on its device; destroy it after the last use has been enqueued -- qsv_arith_destroy waits for the device. */
+#define QSV_ARITH_ADD 0
+#define QSV_ARITH_MUL 1
+#define QSV_ARITH_ADD_REG 2
+#define QSV_ARITH_MUL_POW 3
+#define QSV_ARITH_XOR_LOOKUP 4
+#define QSV_ARITH_PERMUTE 5
+#define QSV_ARITH_INVERSE 1
+typedef struct qsv_arith qsv_arith;
+int qsv_arith_create(int kind, int m, int mx, uint64_t a, uint64_t c, uint64_t modulus, const uint64_t *table,
+                     uint64_t table_len, int device, qsv_arith **out);
+int qsv_arith_destroy(qsv_arith *op);
+int qsv_arith_info(const qsv_arith *op, int *kind, int *m, int *mx);
+int qsv_apply_arith(qsv_state *st, qsv_arith *op, const int *target, const int *source, int n_controls,
+                    const int *controls, int flags, uint64_t *passes);
 /* Qubit-axis permutation of the ket: permute_tensor_product (numpy_quantum.py:227-240); the qubit
  * at position j moves to position new_ordering[j]. */
 int qsv_permute(qsv_state *st, const int *new_ordering);

@@ -13,6 +13,7 @@ OPT_SPECIALIZE, OPT_UNROLL, OPT_GRID_CAP, OPT_NONTEMPORAL, OPT_ITEM_STRIDE_BIT, 
 OPT_KQ_VARIANT, OPT_PLANE_KERNEL, OPT_READOUT_VARIANT, OPT_COMPLEX_PRODUCT, OPT_SEQUENCE_WORK = 7, 8, 9, 10, 11
 OPT_TILE_SEQUENCE_GATES, OPT_DEFER = 12, 13
 QFT_INVERSE, QFT_NO_SWAPS, QFT_CONJUGATE = 1, 2, 4     # flags of qsv_apply_qft
+ARITH_INVERSE = 1                                      # flag of qsv_apply_arith
 
 SITE_MAX_BOND = 128                 # QSV_SITE_MAX_BOND: widest bond qsv_tensor_site_orthogonalise takes
 RANK_NEEDS_OMEGA = (1 << 64) - 1     # qsv_tensor_rsvd_split without a test matrix: call again with one
@@ -67,6 +68,10 @@ SIGNATURES: dict[str, list] = {
     "qsv_apply_pauli_rotation": [_state_p, C.c_int, _int_p, C.c_char_p, C.c_double],
     "qsv_apply_pauli_rotations": [_state_p, C.c_int, _int_p, _int_p, C.c_char_p, _dbl_p, _u64_p],
     "qsv_apply_qft": [_state_p, C.c_int, _int_p, C.c_int, _u64_p],
+    "qsv_arith_create": [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, _u64_p, C.c_uint64, C.c_int, C.POINTER(_state_p)],
+    "qsv_arith_destroy": [_state_p],
+    "qsv_arith_info": [_state_p, _int_p, _int_p, _int_p],
+    "qsv_apply_arith": [_state_p, _state_p, _int_p, _int_p, C.c_int, _int_p, C.c_int, _u64_p],
     "qsv_apply_pauli_sum": [_state_p, _state_p, C.c_int, _int_p, _int_p, C.c_char_p, _dbl_p, C.c_int, _u64_p],
     "qsv_pauli_transition_sum": [_state_p, _state_p, C.c_int, _int_p, _int_p, C.c_char_p, _dbl_p, _dbl_p, _dbl_p, _dbl_p, _u64_p],
     "qsv_pauli_rotations_adjoint": [_state_p, _state_p, C.c_int, _int_p, _int_p, C.c_char_p, _dbl_p, _dbl_p, _u64_p],

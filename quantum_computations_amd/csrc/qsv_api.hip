@@ -1029,6 +1029,33 @@ int qsv_apply_qft(qsv_state *st, int m, const int *qubits, int flags, uint64_t *
     return QSV_OK;
 }
 
+int qsv_apply_arith(qsv_state *st, qsv_arith *op, const int *target, const int *source, int n_controls, const int *controls,
+                    int flags, uint64_t *passes) {
+    if (!valid(st) || !op || !target) return qsv_fail(QSV_EINVAL, "null pointer");
+    if (st->kind != 0) return qsv_fail(QSV_ESTATE, "this call needs a qubit register");
+    int device = 0, m = 0, mx = 0;
+    qsvk_arith_describe(op, &device, &m, &mx);
+    if ((mx > 0 && !source) || (n_controls > 0 && !controls)) return qsv_fail(QSV_EINVAL, "null pointer");
+    if (n_controls < 0 || n_controls > 64) return qsv_fail(QSV_EINVAL, "bad number of controls");
+    if (device != st->device) return qsv_fail(QSV_EINVAL, "register and register map on different devices");
+    if (flags & ~QSV_ARITH_INVERSE) return qsv_fail(QSV_EINVAL, "unknown flag for a register map");
+    // a qubit may appear once in target, source and controls together
+    std::vector<int> all(target, target + m);
+    if (mx > 0) all.insert(all.end(), source, source + mx);
+    if (n_controls > 0) all.insert(all.end(), controls, controls + n_controls);
+    int rc = check_qubits(st, static_cast<int>(all.size()), all.data());
+    if (rc) return rc;
+    if (passes) *passes = 0;
+    QSV_FLUSH(st);
+    QSV_HIP(hipSetDevice(st->device));
+    for (int &q : all) q = bit_of(st, q);
+    uint64_t launches = 0;
+    rc = qsvk_arith(st, op, all.data(), all.data() + m, n_controls, all.data() + m + mx, (flags & QSV_ARITH_INVERSE) != 0, &launches);
+    if (rc) return rc;
+    if (passes) *passes = launches;
+    return QSV_OK;
+}
+
 // Two registers that one launch reads and writes: qubit registers on one device.  check_disjoint: their first amps_a and
 // amps_b amplitudes (which must lie inside their allocations) do not meet.
 static int check_register_pair(const qsv_state *a, const qsv_state *b) {

@@ -192,6 +192,11 @@ int qsvk_pauli_adjoint_passes(qsv_state *psi, amp_t *lambda, const std::vector<q
 // qsv_qft.hip: the Fourier transform on index bits bits[0 .. m-1] (flags: QSV_QFT_*), in place and with no synchronisation;
 // *launches = tile passes plus the permutation
 int qsvk_qft(qsv_state *st, int m, const int *bits, int flags, uint64_t *launches);
+// qsv_arith.hip: a register map (or its inverse) on index bits tbits / sbits / cbits, most significant operand qubit first: one
+// gather into the spare buffer, which becomes the register; *launches = 0 for a map that moves nothing
+int qsvk_arith(qsv_state *st, const qsv_arith *op, const int *tbits, const int *sbits, int n_controls, const int *cbits, bool inverse,
+               uint64_t *launches);
+int qsvk_arith_describe(const qsv_arith *op, int *device, int *m, int *mx);
 int qsvk_reduced_density(qsv_state *st, int k, const int *bits, double *rho_out);
 int qsvk_expect_density(qsv_state *ket, qsv_state *rho, double *re, double *im);
 int qsvk_sample(qsv_state *st, int shots, const double *u, uint64_t *out);

@@ -433,6 +433,29 @@ class DeviceState:
         _lib.call("qsv_apply_qft", self._h, len(qubits), _ints(qubits), flags, C.byref(passes))
         return passes.value
 
+    # ---- reversible register arithmetic -------------------------------------------------------
+    def apply_register_map(self, op, target, source=None, controls=(), *, inverse: bool = False) -> "DeviceState":
+        """In-place classical map on the value of the ``target`` qubits (``arithmetic.RegisterMap``: modular addition and
+        multiplication, register-controlled versions of both, xor lookups, value permutations), reading the ``source``
+        qubits and acting where every qubit of ``controls`` is 1; the first listed qubit of an operand is its most
+        significant bit.  One gather pass over the register (``qsv_apply_arith``), bit-exact.  ``ShardedState`` has no such
+        method: out of scope there."""
+        self._apply_register_map(op, target, source, controls, inverse=inverse)
+        return self
+
+    def _apply_register_map(self, op, target, source=None, controls=(), *, inverse: bool = False, qubit_offset: int = 0) -> int:
+        """Launch; returns the number of passes (0 for a map that moves nothing)."""
+        target = [int(q) + qubit_offset for q in target]
+        source = [int(q) + qubit_offset for q in (source if source is not None else ())]
+        controls = [int(q) + qubit_offset for q in controls]
+        if len(target) != op.m or len(source) != op.mx:
+            raise ValueError(f"{op} needs {op.m} target and {op.mx} source qubits")
+        flags = _lib.ARITH_INVERSE if bool(inverse) != bool(op.inverted) else 0
+        passes = C.c_uint64()
+        _lib.call("qsv_apply_arith", self._h, op._handle(self.device), _ints(target), _ints(source), len(controls), _ints(controls),
+                  flags, C.byref(passes))
+        return passes.value
+
     def evolve(self, terms, t: float, steps: int = 1, order: int = 1) -> "DeviceState":
         """Trotterised ``exp(-i t H) ket`` for ``H = sum_t c_t P_t``, ``terms`` as for ``expect_pauli_sum`` (real
         coefficients): ``npq.trotter_rotations`` turned into shared passes by ``apply_pauli_rotations``."""
@@ -801,6 +824,17 @@ class DensityState(DeviceState):
             raise ValueError(f"qubit index out of range for a {n}-qubit register")
         self._apply_qft(qubits, inverse=inverse, swaps=swaps)
         self._apply_qft(qubits, inverse=inverse, swaps=swaps, qubit_offset=n, conjugate=True)
+        return self
+
+    def apply_register_map(self, op, target, source=None, controls=(), *, inverse: bool = False) -> "DensityState":
+        """``P rho P^T`` for the permutation matrix ``P`` of the map: the map on the row qubits, then on the column qubits
+        ``n + q`` (``P`` is real: there is no conjugate form)."""
+        n = self.num_qubits
+        listed = [int(q) for group in (target, source or (), controls) for q in group]
+        if any(not 0 <= q < n for q in listed):
+            raise ValueError(f"qubit index out of range for a {n}-qubit register")
+        self._apply_register_map(op, target, source, controls, inverse=inverse)
+        self._apply_register_map(op, target, source, controls, inverse=inverse, qubit_offset=n)
         return self
 
     def apply_pauli_sum(self, terms, out=None, accumulate: bool = False):

@@ -298,6 +298,73 @@ class QFT(Gate):
         return out
 
 
+def apply_register_map_on_host(state, op, target, source=None, controls=(), inverse: bool = False) -> np.ndarray:
+    """``arithmetic.RegisterMap`` on a host ket or density matrix through a borrowed device register (``P rho P^T`` for a
+    matrix: the map on the row qubits, then on the column qubits); returns a new array of the input's shape."""
+    state = np.asarray(state)
+    if state.ndim not in (1, 2):
+        raise ValueError("State has wrong dimensions.")
+    flat = np.ascontiguousarray(state).reshape(-1)
+    dev = _borrow_register(flat)
+    size = DeviceState.num_qubits.fget(dev)
+    try:
+        listed = [int(q) for group in (target, source or (), controls) for q in group]
+        if state.ndim == 2 and any(not 0 <= q < size // 2 for q in listed):
+            raise ValueError(f"qubit index out of range for a {size // 2}-qubit register")
+        dev._apply_register_map(op, target, source, controls, inverse=inverse)
+        if state.ndim == 2:
+            dev._apply_register_map(op, target, source, controls, inverse=inverse, qubit_offset=size // 2)
+        out = dev.to_numpy().reshape(state.shape)
+    except BaseException:
+        dev.close()
+        raise
+    _return_register(dev, size)
+    return _as_result_dtype(out, state)
+
+
+class RegisterMap(Gate):
+    """A classical reversible map (``arithmetic.RegisterMap``: modular addition and multiplication, register-controlled
+    versions of both, xor lookups, value permutations) on the value of the ``target`` qubits, reading the ``source`` qubits
+    and acting where every qubit of ``controls`` is 1; ``indices = target + source + controls``.  On a ``DeviceState`` /
+    ``DensityState`` (and on host arrays, which borrow one) it is one gather pass over the register
+    (``apply_register_map``).  ``matrix`` is the dense permutation matrix for at most six qubits in all, so that fusion,
+    ``TrajectoryEnsemble.apply`` and registers without that method (``distributed.ShardedState``: out of scope) keep
+    working through the matrix path, and ``None`` above."""
+
+    MAX_DENSE = 6                    # qsv_apply_kq takes matrices on at most six qubits (include/qsv.h)
+    result_dtype = np.float64        # what the gate contributes to NumPy's promotion when it has no matrix
+
+    def __init__(self, op, target, source=(), controls=(), inverse: bool = False):
+        target, source, controls = [int(q) for q in target], [int(q) for q in (source or ())], [int(q) for q in controls]
+        if len(target) != op.m or len(source) != op.mx:
+            raise ValueError(f"{op} needs {op.m} target and {op.mx} source qubits")
+        indices = target + source + controls
+        matrix = npq.register_map_matrix(op, len(controls), inverse) if len(indices) <= self.MAX_DENSE else None
+        super().__init__(indices, matrix)
+        self.op = op
+        self.inverse = bool(inverse)
+        self.n_controls = len(controls)
+
+    # the operands follow ``indices`` (``relabel`` renames them there)
+    target = property(lambda self: self.indices[:self.op.m])
+    source = property(lambda self: self.indices[self.op.m:self.op.m + self.op.mx])
+    controls = property(lambda self: self.indices[self.op.m + self.op.mx:])
+
+    def __repr__(self):
+        text = f"RegisterMap[{self.op!r}{'^-1' if self.inverse else ''}]_" + ",".join(str(q) for q in self.target)
+        text += ("<-" + ",".join(str(q) for q in self.source)) if self.source else ""
+        return text + (("|c" + ",".join(str(q) for q in self.controls)) if self.controls else "")
+
+    def apply(self, state):
+        if is_device_register(state):
+            if hasattr(state, "apply_register_map"):
+                return state.apply_register_map(self.op, self.target, self.source, self.controls, inverse=self.inverse)
+            if self.matrix is None:
+                raise ValueError(f"{type(state).__name__} has no apply_register_map and {self} has no dense matrix.")
+            return super().apply(state)
+        return apply_register_map_on_host(state, self.op, self.target, self.source, self.controls, self.inverse)
+
+
 def _fixed_2q(name: str, matrix_of, doc: str, **extra):
     def __init__(self, first, second):
         TwoQubitGate.__init__(self, first, second, matrix_of())

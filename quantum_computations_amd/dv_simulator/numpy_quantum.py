@@ -613,6 +613,31 @@ def qft_matrix(m: int, inverse: bool = False, swaps: bool = True) -> np.ndarray:
     return matrix.conj().T if inverse else matrix
 
 
+def register_map_matrix(op, n_controls: int = 0, inverse: bool = False) -> np.ndarray:
+    """Dense permutation matrix of an ``arithmetic.RegisterMap`` on ``m + mx + n_controls`` qubits, legs in the order
+    target, source, controls (each most significant first): column ``(y, x, c)`` holds its 1 in row ``(y', x, c)``, with
+    ``y' = y`` unless every control is 1.  Small sizes only (at most 12 qubits)."""
+    total = op.m + op.mx + int(n_controls)
+    if total > 12:
+        raise ValueError("register_map_matrix is for at most 12 qubits")
+    values = (op.inverse() if inverse else op).index_map()           # [x, y] -> y'
+    dim, all_on = 1 << total, (1 << n_controls) - 1
+    matrix = np.zeros((dim, dim))
+    for y in range(1 << op.m):
+        for x in range(1 << op.mx):
+            for c in range(1 << n_controls):
+                to = int(values[x, y]) if c == all_on else y
+                matrix[((to << op.mx | x) << n_controls) | c, ((y << op.mx | x) << n_controls) | c] = 1.0
+    return matrix
+
+
+def apply_register_map(state, op, target, source=None, controls=(), inverse: bool = False) -> np.ndarray:
+    """An ``arithmetic.RegisterMap`` on a host ket or density matrix (a new array; one gather pass on a borrowed device
+    register, as ``gates.QFT`` does for host arrays)."""
+    from . import gates
+    return gates.apply_register_map_on_host(state, op, target, source, controls, inverse)
+
+
 def add_control(gate: np.ndarray) -> np.ndarray:
     """``|0><0| x I + |1><1| x gate``."""
     dim = gate.shape[0]

@@ -46,6 +46,10 @@ def to_gates(ops: list[dict]) -> list:
             gate = G.Insert(idx[0], State[o["state"]])
         elif name == "MCPhase":
             gate = MCPhase(idx, o["phase"])
+        elif name == "QFT":
+            gate = G.QFT(idx, inverse=o.get("inverse", False), swaps=o.get("swaps", True))
+        elif name == "RegisterMap":
+            gate = G.RegisterMap(o["map"], o["target"], o["source"], o["controls"], inverse=o.get("inverse", False))
         else:
             gate = G.Gate(list(idx), np.asarray(o["matrix"]))
         ctl = o.get("control")
@@ -163,6 +167,35 @@ def qft_ops(qubits, inverse: bool = False, swaps: bool = True, conjugate: bool =
                         "phase": phase})
     tail = [op("SWAP", qubits[r], qubits[m - 1 - r]) for r in range(m // 2)] if swaps else []
     return (tail + ops[::-1]) if inverse else (ops + tail)
+
+
+def register_map_op(register_map, target, source=(), controls=(), inverse: bool = False) -> dict:
+    """An ``arithmetic.RegisterMap`` as an op (``to_gates`` makes a ``gates.RegisterMap`` of it); it carries the dense
+    permutation matrix when that is at most six qubits."""
+    gate = G.RegisterMap(register_map, target, source, controls, inverse=inverse)
+    return {"name": "RegisterMap", "indices": list(gate.indices), "matrix": gate.matrix, "map": register_map, "target": gate.target,
+            "source": gate.source, "controls": gate.controls, "inverse": bool(inverse)}
+
+
+def order_finding_ops(a: int, N: int, t: int, spelled: bool = False) -> list[dict]:
+    """Order finding for ``a`` modulo ``N`` with ``t`` counting qubits (qubits ``0 .. t-1``, qubit 0 the most significant)
+    and a work register of ``m = N.bit_length()`` qubits behind them: Hadamards on the counting qubits, the work register
+    in ``|1>``, ``|x>|y> -> |x>|y a^x mod N>`` and the inverse Fourier transform on the counting qubits.  The modular
+    exponentiation is ONE ``RegisterMap.modexp`` pass, or with ``spelled`` the ``t`` multiplications by ``a^(2^j) mod N``
+    controlled by the counting qubit of weight ``2^j`` -- the same permutation, so the kets agree exactly.  Apply to
+    ``|0 .. 0>`` of ``t + m`` qubits; the counting register then peaks at the multiples of ``2^t / r``, r the order."""
+    from .arithmetic import RegisterMap
+    a, N, t = int(a), int(N), int(t)
+    m = N.bit_length()
+    counting, work = list(range(t)), list(range(t, t + m))
+    ops = [op("H", q) for q in counting] + [op("X", work[-1])]
+    if spelled:
+        for j in range(t):
+            ops.append(register_map_op(RegisterMap.multiply(m, pow(a, 1 << j, N), N), work, controls=[counting[t - 1 - j]]))
+    else:
+        ops.append(register_map_op(RegisterMap.modexp(m, t, a, N), work, counting))
+    ops.append({"name": "QFT", "indices": counting, "matrix": None, "inverse": True, "swaps": True})
+    return ops
 
 
 def grover_circuit(n: int, marked: int, iterations: int) -> list:

@@ -504,6 +504,36 @@ int qsv_ensemble_apply_conditional(qsv_state *st, int member_qubits, int k /* 1 
                                    uint64_t all_of, uint64_t none_of);
 int qsv_ensemble_bits_read(qsv_state *st, int member_qubits, uint64_t *bits /* members */);
 int qsv_ensemble_bits_write(qsv_state *st, int member_qubits, const uint64_t *bits /* NULL = clear all */);
+/* ---- parameter ensembles: per-member angles, matrices and cost phases (csrc/qsv_sweep.hip) ----
+ * The members of an ensemble run the same circuit at different parameter points.  Notation as above: members =
+ * 2^(n_total - member_qubits), `qubits` are MEMBER qubits, qsv_diag objects have member_qubits qubits (not n_total).
+ *  - qsv_ensemble_apply_pauli_rotations: member m becomes what qsv_apply_pauli_rotations would make of it alone with row m of
+ *    thetas.  Same term list, same planner (on member-local masks), same *passes -- which never depends on the number of
+ *    members; the identity string (or an empty one) is a per-member global phase.  cos(theta / 2) and sin(theta / 2) are
+ *    formed on the host as in qsv_apply_pauli_rotations and travel as one table [members][n_terms][2]; a member's bits are
+ *    those of a register of its own, wherever it sits.  n_terms = 0 launches nothing.
+ *  - qsv_ensemble_apply_matrices: member m takes matrices[m] on `qubits` (k = 1 or 2).  Unitarity is not demanded; nothing is
+ *    drawn or logged.  The update pass of qsv_ensemble_apply_channel with the matrix slots filled by the caller.
+ *  - qsv_ensemble_apply_diag_phase: psi_m[i] *= exp(-i gammas[m] d[i]), the arithmetic of qsv_apply_diag_phase.
+ *  - qsv_ensemble_expect_diag: out[m] = { sum p, sum p d, sum p d^2, sum_{d <= *threshold} p } over member m, p = |psi_m[i]|^2
+ *    (slot 3 is 0 when threshold is NULL).  Read-only; a member's sums depend on member_qubits and QSV_OPT_GRID_CAP only; one
+ *    copy and one synchronisation at the end, as qsv_ensemble_norm2.
+ * After its checks a call flushes the deferred queue, is enqueued on the register's stream and (the read-out apart) returns
+ * without waiting for its kernels; the caller's arrays may be reused on return.  The diagonal's stream is synchronised as in
+ * qsv_apply_diag_phase.
+ * QSV_EINVAL for null pointers (passes and threshold may be NULL), a view, member_qubits outside k .. n_total for
+ * apply_matrices and 0 .. n_total for the others, a qubit >= member_qubits or repeated, k outside 1 .. 2, a diagonal of another
+ * size or on another device, any angle, gamma, matrix entry or threshold that is not finite; QSV_ESTATE for a mode register, or
+ * where apply_matrices would change the member size while the ensemble log holds steps: each before any launch and with the
+ * deferred queue untouched. */
+int qsv_ensemble_apply_pauli_rotations(qsv_state *st, int member_qubits, int n_terms, const int *term_offsets,
+                                       const int *qubits, const char *paulis,
+                                       const double *thetas /* [members][n_terms] */, uint64_t *passes);
+int qsv_ensemble_apply_matrices(qsv_state *st, int member_qubits, int k /* 1 or 2 */, const int *qubits,
+                                const double *matrices /* [members][4^k] complex, row-major, qubits[0] most significant */);
+int qsv_ensemble_apply_diag_phase(qsv_state *st, int member_qubits, qsv_diag *d, const double *gammas /* members */);
+int qsv_ensemble_expect_diag(qsv_state *st, int member_qubits, qsv_diag *d, const double *threshold /* NULL or one value */,
+                             double *out /* [members][4] */);
 /* Reduced density matrix of the k <= 6 qubits `qubits` (all others traced out) in one read pass over the register:
  * rho[i][j] = sum_rest psi[i, rest] conj(psi[j, rest]), written row-major as 4^k complex numbers, qubits[0] the most
  * significant bit of i and j.  What a caller of the reference gets from npq.ket2dm (numpy_quantum.py:110-113)

@@ -106,6 +106,10 @@ SIGNATURES: dict[str, list] = {
     "qsv_ensemble_apply_conditional": [_state_p, C.c_int, C.c_int, _int_p, _dbl_p, C.c_uint64, C.c_uint64],
     "qsv_ensemble_bits_read": [_state_p, C.c_int, _u64_p],
     "qsv_ensemble_bits_write": [_state_p, C.c_int, _u64_p],
+    "qsv_ensemble_apply_pauli_rotations": [_state_p, C.c_int, C.c_int, _int_p, _int_p, C.c_char_p, _dbl_p, _u64_p],
+    "qsv_ensemble_apply_matrices": [_state_p, C.c_int, C.c_int, _int_p, _dbl_p],
+    "qsv_ensemble_apply_diag_phase": [_state_p, C.c_int, _state_p, _dbl_p],
+    "qsv_ensemble_expect_diag": [_state_p, C.c_int, _state_p, _dbl_p, _dbl_p],
     "qsv_ensemble_expect_pauli_sum": [_state_p, C.c_int, C.c_int, _int_p, _int_p, C.c_char_p, _dbl_p, _dbl_p, _dbl_p],
     "qsv_reduced_density": [_state_p, C.c_int, _int_p, C.c_void_p],
     "qsv_reduced_density_state": [_state_p, C.c_int, _int_p, _state_p],

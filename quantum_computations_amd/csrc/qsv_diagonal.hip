@@ -6,7 +6,7 @@
 // qsv_diagonal_layout.h.
 
 #include "qsv_device.h"
-#include "qsv_diagonal_layout.h"
+#include "qsv_diagonal_device.h"
 
 #include <cstring>
 #include <limits>
@@ -16,29 +16,9 @@ using namespace qsv_diagonal_layout;
 
 static_assert(DIAG_BLOCK == QSV_BLOCK && DIAG_REDUCE_BLOCKS == QSV_REDUCE_BLOCKS, "qsv_diagonal_layout.h mirrors qsv_internal.h");
 
-struct qsv_diag {
-    int device = 0;
-    int n = 0;
-    uint64_t size = 1;               // 2^n doubles at `data`
-    double *data = nullptr;
-    hipStream_t stream = nullptr;
-    int grid_cap = 0;
-    DiagTerm *table = nullptr;       // device copy of the term table of the last qsv_diag_set_pauli_sum
-    size_t table_rows = 0;           // rows allocated
-    uint64_t *scratch = nullptr;     // partials of k_diag_extrema
-    size_t scratch_bytes = 0;
-    char last_kernel[96] = "";
-};
-
 namespace {
 
-template <bool NT>
-__device__ __forceinline__ double ld_real(const double *p) {
-    if constexpr (NT)
-        return __builtin_nontemporal_load(p);
-    else
-        return *p;
-}
+// qsv_diag itself, ld_real, phase_of and wait_for_diag: qsv_diagonal_device.h, shared with qsv_sweep.hip.
 
 // d[i] = (ACC ? d[i] : 0) + sum_t coeff_t (-1)^popcount(i & zmask_t), the additions in table order, one rounded add per
 // term: coeff * (+-1) is a flip of the sign bit.  The table index is wave-uniform and the table is never written by the
@@ -59,13 +39,6 @@ __global__ __launch_bounds__(QSV_BLOCK) void k_diag_build(double *__restrict__ d
         }
         d[i] = acc;
     }
-}
-
-// exp(-i gamma x): one double-precision sincos
-__device__ __forceinline__ cplx phase_of(double gamma, double x) {
-    double s, c;
-    sincos(gamma * x, &s, &c);
-    return cplx{c, -s};
 }
 
 // psi[i] *= exp(-i gamma d[i])
@@ -240,12 +213,6 @@ int check_pair(const qsv_state *st, const qsv_diag *d) {
     if (st->kind != 0) return qsv_fail(QSV_ESTATE, "this call needs qubit registers");
     if (st->device != d->device) return qsv_fail(QSV_EINVAL, "register and diagonal on different devices");
     if (st->n != d->n || st->amps != d->size) return qsv_fail(QSV_EINVAL, "register and diagonal of different sizes");
-    return QSV_OK;
-}
-
-// The diagonal's own work is finished before a kernel on another stream reads it.
-int wait_for_diag(const qsv_diag *d, hipStream_t launching) {
-    if (d->stream != launching) QSV_HIP(hipStreamSynchronize(d->stream));
     return QSV_OK;
 }
 

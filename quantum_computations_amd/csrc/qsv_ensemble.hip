@@ -11,12 +11,13 @@
 // its kernel arguments, takes the member's outcome by the same rule and writes it to one of the member's 64 classical bits;
 // k_ens_apply_conditional is k_ens_channel_apply with one matrix for all members and a predicate on those bits: members
 // that do not take the gate are neither read nor written.
+// qsv_ensemble_apply_matrices is k_ens_channel_apply with the matrix slots filled by the caller.
 // k_ens_expect_pauli_group / k_ens_sum_parts give <psi_m|P_t|psi_m> per member for the passes of qsv_pauli_plan.h.
 // The per-item bodies are those of k_channel_rdm, k_channel_apply and k_expect_pauli_group on a register of 2^n amplitudes;
 // what is new is the member dimension and where the sums stop.  Launch shapes: qsv_ensemble_layout.h.
 
 #include "qsv_device.h"
-#include "qsv_ensemble_layout.h"
+#include "qsv_ensemble_device.h"
 #include "qsv_ensemble_control_layout.h"
 
 #include <cmath>
@@ -162,67 +163,7 @@ __device__ __forceinline__ int own_combination(const ChannelArgs &g) {
     return l;
 }
 
-// What a thread works on in unit `unit` (ens_thread of qsv_ensemble_layout.h, step for step).
-struct Mine {
-    uint64_t group, part, member, first, stride, items;
-    uint32_t local;
-    bool live;       // member < members
-};
-__device__ __forceinline__ Mine mine(const EnsArgs &e, uint64_t unit) {
-    Mine t;
-    const uint32_t tid = threadIdx.x;
-    const bool shared = e.item_bits < ENS_BLOCK_BITS;
-    t.group = unit >> e.part_bits;
-    t.part = unit & ((1ull << e.part_bits) - 1ull);
-    t.member = (t.group << e.share_bits) + (shared ? tid >> e.item_bits : 0u);
-    t.local = shared ? tid & ((1u << e.item_bits) - 1u) : tid;
-    t.first = (t.part << ENS_BLOCK_BITS) + t.local;
-    t.stride = static_cast<uint64_t>(QSV_BLOCK) << e.part_bits;
-    t.items = 1ull << e.item_bits;
-    t.live = t.member < e.members;
-    return t;
-}
-
-// The sums of R doubles per thread, member by member: partials[(member * P + part) * R + e].  A member of fewer than 64 items
-// is a run of aligned lanes and is summed by a butterfly over that run alone; from 64 items on the waves of a member are
-// added in index order through LDS.  The order of every addition depends on the thread's place inside its member only.
-// Every thread of the workgroup must call this (shuffles and barriers).
-template <int R>
-__device__ __forceinline__ void member_store_sums(double (&v)[R], const EnsArgs &e, const Mine &t, double *__restrict__ partials) {
-    const int segment = 1 << (e.item_bits < 6 ? e.item_bits : 6);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        if (o < segment) {     // wave-uniform
-#pragma unroll
-            for (int r = 0; r < R; ++r) v[r] += __shfl_xor(v[r], o, 64);
-        }
-    }
-    if (e.item_bits < 6) {     // one part; the first lane of the member's run holds its sums
-        if (t.local == 0 && t.live) {
-#pragma unroll
-            for (int r = 0; r < R; ++r) partials[t.member * R + r] = v[r];
-        }
-        return;
-    }
-    __shared__ double sums[QSV_BLOCK / 64][R];
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) sums[threadIdx.x >> 6][r] = v[r];
-    }
-    __syncthreads();
-    const int wave_bits = e.item_bits - 6 < 2 ? e.item_bits - 6 : 2;     // log2 of the waves of one member in this workgroup
-    const int sharing = (QSV_BLOCK / 64) >> wave_bits;                    // members in this workgroup
-    if (threadIdx.x < sharing * R) {
-        const int s = threadIdx.x / R, r = threadIdx.x % R;
-        const uint64_t member = (t.group << e.share_bits) + s;
-        if (member < e.members) {
-            double sum = 0.0;
-            for (int wv = 0; wv < (1 << wave_bits); ++wv) sum += sums[(s << wave_bits) + wv][r];
-            partials[((member << e.part_bits) + t.part) * R + r] = sum;
-        }
-    }
-    __syncthreads();     // the next unit writes sums again
-}
+// Mine / mine (who works on what in a unit) and member_store_sums: qsv_ensemble_device.h, shared with qsv_sweep.hip.
 
 // k_channel_rdm's item body on member-local indices.  Read-only.
 template <int K, int KL, bool NT>
@@ -637,26 +578,7 @@ void with_shape(int k, int kl, bool nt, F &&f) {
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 
-// what every ensemble call refuses about the register and the member size
-int check_ensemble(const qsv_state *st, int member_qubits, int least) {
-    if (!st) return qsv_fail(QSV_EINVAL, "null pointer");
-    if (st->kind != 0) return qsv_fail(QSV_ESTATE, "this call needs a qubit register");
-    if (!st->owns_data) return qsv_fail(QSV_EINVAL, "an ensemble lives in a register the library allocated, not in a view");
-    if (member_qubits < least || member_qubits > st->n)
-        return qsv_fail(QSV_EINVAL, "member_qubits must lie between " + std::to_string(least) + " and the register's " + std::to_string(st->n) + " qubits");
-    return QSV_OK;
-}
-
-int check_member_qubits(int member_qubits, int count, const int *qubits) {
-    for (int i = 0; i < count; ++i) {
-        if (qubits[i] < 0) return qsv_fail(QSV_EINVAL, "Non-negative index");
-        if (qubits[i] >= member_qubits)
-            return qsv_fail(QSV_EINVAL, "qubit index " + std::to_string(qubits[i]) + " out of range for members of " + std::to_string(member_qubits) + " qubits");
-        for (int j = 0; j < i; ++j)
-            if (qubits[i] == qubits[j]) return qsv_fail(QSV_EINVAL, "Indices must be distinct.");
-    }
-    return QSV_OK;
-}
+// check_ensemble / check_member_qubits (what every ensemble call refuses): qsv_ensemble_device.h.
 
 // values[pass offset + m * width + t] for every pass, summed per member on the device; one copy, one synchronisation
 int expect_passes(qsv_state *st, int n, const std::vector<qsv_pauli_plan::Pass> &passes, std::vector<double> *host, std::vector<size_t> *offsets,
@@ -701,6 +623,13 @@ int expect_passes(qsv_state *st, int n, const std::vector<qsv_pauli_plan::Pass> 
 }
 
 }  // namespace
+
+// k_ens_sum_parts for the ensemble kernels of other translation units (qsv_sweep.hip): on st's stream, no synchronisation
+int qsvk_ens_sum_parts(qsv_state *st, const double *partials, uint64_t members, int parts, int R, double *out) {
+    hipLaunchKernelGGL(k_ens_sum_parts, dim3(grid_for(members * R, QSV_BLOCK, QSV_REDUCE_BLOCKS)), dim3(QSV_BLOCK), 0, st->stream, partials, members,
+                       parts, R, out);
+    return check_launch();
+}
 
 extern "C" {
 
@@ -906,6 +835,48 @@ int qsv_ensemble_apply_conditional(qsv_state *st, int member_qubits, int k, cons
                            st->data, plan.g, update, args, static_cast<const uint64_t *>(work->bits));
     });
     snprintf(st->last_kernel, sizeof(st->last_kernel), "k_ens_apply_conditional<%d, %d, %s>", k, plan.kl, nt ? "true" : "false");
+    return check_launch();
+}
+
+// Every member its own matrix: the update pass of a channel call with the matrix slots filled by the caller instead of by
+// k_ens_channel_select.  Nothing is drawn, nothing is logged.  The slots belong to the register's stream: the copy below is
+// queued behind the update pass of any earlier step that still reads them.
+int qsv_ensemble_apply_matrices(qsv_state *st, int member_qubits, int k, const int *qubits, const double *matrices) {
+    if (!st || !qubits || !matrices) return qsv_fail(QSV_EINVAL, "null pointer");
+    if (k < 1 || k > 2) return qsv_fail(QSV_EINVAL, "per-member matrices act on 1 or 2 qubits");
+    int rc = check_ensemble(st, member_qubits, k);
+    if (rc) return rc;
+    rc = check_member_qubits(member_qubits, k, qubits);
+    if (rc) return rc;
+    const int n = member_qubits;
+    const uint64_t members = st->amps >> n;
+    const size_t entries = size_t(2) << (2 * k);     // doubles of one matrix
+    for (size_t i = 0; i < members * entries; ++i)
+        if (!std::isfinite(matrices[i])) return qsv_fail(QSV_EINVAL, "every matrix entry must be finite");
+    EnsembleWork *work = work_of(st);
+    rc = check_member_size(work, n, members);
+    if (rc) return rc;
+    rc = qsv_flush(st);
+    if (rc) return rc;
+    QSV_HIP(hipSetDevice(st->device));
+    rc = ensure_workspace(st, work, n, members);
+    if (rc) return rc;
+    std::vector<double> slots(static_cast<size_t>(members) * 32, 0.0);
+    for (uint64_t m = 0; m < members; ++m) std::memcpy(&slots[32 * m], matrices + m * entries, sizeof(double) * entries);
+    double *matrix = work->dev + work->ws.matrix;
+    // pageable memory: the copy has left `slots` when this returns, and is ordered on the register's stream
+    QSV_HIP(hipMemcpyAsync(matrix, slots.data(), sizeof(double) * slots.size(), hipMemcpyHostToDevice, st->stream));
+    int bits[2] = {0, 0};
+    for (int i = 0; i < k; ++i) bits[i] = n - 1 - qubits[i];
+    const ChannelPlan plan = ens_channel_plan(n, k, bits, ens_lanes(n, st->readout_variant != 1));
+    const bool nt = st->nontemporal != 0;
+    const int item_bits = n - plan.kh;
+    const EnsArgs update = ens_args(n, members, item_bits, apply_part_bits(item_bits, st->grid_cap));
+    with_shape(plan.k, plan.kl, nt, [&](auto K, auto KL, auto NT) {
+        hipLaunchKernelGGL((k_ens_channel_apply<K.value, KL.value, NT.value>), dim3(ens_grid(update, st->grid_cap)), dim3(QSV_BLOCK), 0, st->stream,
+                           st->data, plan.g, update, static_cast<const double *>(matrix));
+    });
+    snprintf(st->last_kernel, sizeof(st->last_kernel), "k_ens_channel_apply<%d, %d, %s>", plan.k, plan.kl, nt ? "true" : "false");
     return check_launch();
 }
 

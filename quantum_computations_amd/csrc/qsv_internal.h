@@ -197,6 +197,8 @@ int qsvk_qft(qsv_state *st, int m, const int *bits, int flags, uint64_t *launche
 int qsvk_arith(qsv_state *st, const qsv_arith *op, const int *tbits, const int *sbits, int n_controls, const int *cbits, bool inverse,
                uint64_t *launches);
 int qsvk_arith_describe(const qsv_arith *op, int *device, int *m, int *mx);
+// qsv_ensemble.hip: out[m * R + r] = the sum over member m's parts of partials[(m * parts + p) * R + r], in index order, on st's stream
+int qsvk_ens_sum_parts(qsv_state *st, const double *partials, uint64_t members, int parts, int R, double *out);
 int qsvk_reduced_density(qsv_state *st, int k, const int *bits, double *rho_out);
 int qsvk_expect_density(qsv_state *ket, qsv_state *rho, double *re, double *im);
 int qsvk_sample(qsv_state *st, int shots, const double *u, uint64_t *out);

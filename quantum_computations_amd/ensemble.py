@@ -17,7 +17,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .device import DeviceState, _check_terms, _flat_terms, _ints, _real_terms
+from .device import DeviceState, DiagonalMoments, _check_terms, _diagonal_operand, _flat_terms, _ints, _real_terms
 
 
 class TrajectoryEnsemble:
@@ -32,6 +32,7 @@ class TrajectoryEnsemble:
         self.member_bits = total - self.member_qubits
         self.members = 1 << self.member_bits
         self._measured: list[int] = []        # the classical bit of the k-th measurement since reset(): ClassicalControl's indices
+        self.last_passes = 0                  # passes of the last apply_pauli_rotations
 
     @classmethod
     def from_ket(cls, ket, members: int, device: int = 0) -> "TrajectoryEnsemble":
@@ -174,6 +175,64 @@ class TrajectoryEnsemble:
                   buf.ctypes.data_as(C.POINTER(C.c_double)), C.c_uint64(all_of), C.c_uint64(none_of))
         return self
 
+    # ---- per-member parameters: the same circuit at many parameter points ---------------------------
+    def apply_pauli_rotations(self, rotations, thetas=None) -> "TrajectoryEnsemble":
+        """``rotations = [(theta, letters, member qubits), ...]`` as in ``DeviceState.apply_pauli_rotations``, the first
+        applied first.  ``thetas[members, R]`` gives member ``m`` row ``m`` instead of the list's angles; without it every
+        member takes the list's.  The passes are those of the list on one member, whatever the number of members."""
+        offsets, qubits, letters, angles = [0], [], [], []
+        for theta, paulis, qs in rotations:
+            paulis, qs = str(paulis), [int(q) for q in qs]
+            if len(paulis) != len(qs):
+                raise ValueError("one Pauli letter per qubit")
+            qubits += qs
+            letters.append(paulis)
+            offsets.append(len(qubits))
+            angles.append(float(theta))
+        count = len(angles)
+        if thetas is None:
+            table = np.ascontiguousarray(np.broadcast_to(np.asarray(angles, dtype=np.float64), (self.members, count)))
+        else:
+            table = np.ascontiguousarray(thetas, dtype=np.float64)
+            if table.shape != (self.members, count):
+                raise ValueError(f"thetas must have shape [members, rotations] = [{self.members}, {count}]")
+        passes = C.c_uint64()
+        _lib.call("qsv_ensemble_apply_pauli_rotations", self.state._h, self.member_qubits, count, _ints(offsets), _ints(qubits),
+                  "".join(letters).encode(), table.ctypes.data_as(C.POINTER(C.c_double)), C.byref(passes))
+        self.last_passes = int(passes.value)
+        return self
+
+    def apply_matrices(self, matrices, qubits) -> "TrajectoryEnsemble":
+        """Member ``m`` takes ``matrices[m]`` (``[members, 2^k, 2^k]``, ``k`` = 1 or 2, ``qubits[0]`` the most significant
+        bit of the row index) on member qubits ``qubits``.  Unitarity is not demanded; nothing is logged."""
+        qubits = [int(q) for q in qubits]
+        if len(qubits) not in (1, 2):
+            raise ValueError("per-member matrices act on 1 or 2 qubits")
+        dim = 1 << len(qubits)
+        buf = np.ascontiguousarray(matrices, dtype=np.complex128)
+        if buf.shape != (self.members, dim, dim):
+            raise ValueError(f"matrices must have shape [members, 2^k, 2^k] = [{self.members}, {dim}, {dim}]")
+        _lib.call("qsv_ensemble_apply_matrices", self.state._h, self.member_qubits, len(qubits), _ints(qubits),
+                  buf.view(np.float64).ctypes.data_as(C.POINTER(C.c_double)))
+        return self
+
+    def apply_diagonal_phase(self, diag, gammas) -> "TrajectoryEnsemble":
+        """``psi_m[i] *= exp(-i gammas[m] d[i])`` for a ``DiagonalOperator`` of ``member_qubits`` qubits: one gamma per member."""
+        _diagonal_operand(diag)
+        gbuf = np.ascontiguousarray(gammas, dtype=np.float64)
+        if gbuf.shape != (self.members,):
+            raise ValueError("one gamma per member")
+        _lib.call("qsv_ensemble_apply_diag_phase", self.state._h, self.member_qubits, diag._h, gbuf.ctypes.data_as(C.POINTER(C.c_double)))
+        return self
+
+    def expect_diagonal(self, diag, threshold: float | None = None) -> DiagonalMoments:
+        """The fields of ``DeviceState.expect_diagonal`` as arrays with one entry per member; nothing is divided by a norm."""
+        _diagonal_operand(diag)
+        out = np.zeros((self.members, 4), dtype=np.float64)
+        thr = None if threshold is None else C.byref(C.c_double(float(threshold)))
+        _lib.call("qsv_ensemble_expect_diag", self.state._h, self.member_qubits, diag._h, thr, out.ctypes.data_as(C.POINTER(C.c_double)))
+        return DiagonalMoments(*(np.ascontiguousarray(out[:, k]) for k in range(4)))
+
     def bits(self) -> np.ndarray:
         """The classical bits: one ``uint64`` per member."""
         out = np.zeros(self.members, dtype=np.uint64)
@@ -238,3 +297,6 @@ class TrajectoryEnsemble:
             raise ValueError("no such member")
         size = 1 << self.member_qubits
         return self.state.download(m * size, size)
+
+
+Ensemble = TrajectoryEnsemble      # the same object when its members differ by parameters instead of draws

@@ -83,6 +83,54 @@ def energy_and_gradient(diag: DiagonalOperator, gammas, betas, state: DeviceStat
     return energy, d_gamma, d_beta
 
 
+def energies(diag: DiagonalOperator, gammas, betas, batch: int = 256, threshold: float | None = None):
+    """``<D>`` at ``M`` parameter points, ``gammas[M, p]`` and ``betas[M, p]``, ``batch`` points per register: every point is a
+    member of an ``Ensemble``.  Per layer one per-member cost phase, then the mixer as ``n``
+    per-member ``X`` rotations of angle ``2 beta_m``.  Returns ``E[M]``; with a ``threshold`` also
+    ``P(D <= threshold)[M]``.  Surplus members of the last chunk take angles of zero and are dropped."""
+    from . import sweep
+    from .ensemble import Ensemble
+
+    gammas = np.atleast_2d(np.asarray(gammas, dtype=np.float64))
+    betas = np.atleast_2d(np.asarray(betas, dtype=np.float64))
+    if gammas.ndim != 2 or gammas.shape != betas.shape:
+        raise ValueError("gammas and betas must both have shape [points, layers]")
+    points, layers = gammas.shape
+    n = diag.num_qubits
+    plus = np.full(1 << n, 2.0 ** (-0.5 * n), dtype=np.complex128)
+    x_rotations = [(0.0, "X", [q]) for q in range(n)]
+    energy, below = np.zeros(points), np.zeros(points)
+    ens = None
+    try:
+        for first, count, members in sweep.chunks(points, batch):
+            if ens is None or ens.members != members:
+                if ens is not None:
+                    ens.close()
+                ens = Ensemble.from_ket(plus, members, diag.device)
+            else:
+                ens.reset(plus)
+            g, b = np.zeros((members, layers)), np.zeros((members, layers))
+            g[:count], b[:count] = gammas[first:first + count], betas[first:first + count]
+            for layer in range(layers):
+                ens.apply_diagonal_phase(diag, g[:, layer])
+                ens.apply_pauli_rotations(x_rotations, np.repeat(2.0 * b[:, layer, None], n, axis=1))
+            moments = ens.expect_diagonal(diag, threshold)
+            energy[first:first + count] = moments.mean[:count]
+            below[first:first + count] = moments.probability_below[:count]
+    finally:
+        if ens is not None:
+            ens.close()
+    return energy if threshold is None else (energy, below)
+
+
+def landscape(diag: DiagonalOperator, gamma_grid, beta_grid, batch: int = 256) -> np.ndarray:
+    """The ``p = 1`` surface ``E[G, B]`` over ``gamma_grid x beta_grid`` through ``energies``."""
+    gamma_grid = np.asarray(gamma_grid, dtype=np.float64).reshape(-1)
+    beta_grid = np.asarray(beta_grid, dtype=np.float64).reshape(-1)
+    g, b = np.meshgrid(gamma_grid, beta_grid, indexing="ij")
+    return energies(diag, g.reshape(-1, 1), b.reshape(-1, 1), batch=batch).reshape(gamma_grid.size, beta_grid.size)
+
+
 def minimise(diag: DiagonalOperator, p: int, x0=None, **scipy_options):
     """Minimise ``<D>`` over the ``2 p`` angles ``x = (gammas, betas)`` with L-BFGS-B on ``energy_and_gradient``.
     ``x0``: the starting angles (default: ``gamma_l = 0.1 (l + 1) / p``, ``beta_l = 0.1 (p - l) / p``); keyword options

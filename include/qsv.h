@@ -564,7 +564,9 @@ int qsv_marginal_probabilities(qsv_state *st, int k, const int *qubits, double *
 int qsv_expect_density(qsv_state *ket, qsv_state *rho, double *re, double *im);
 /* Draw `shots` computational-basis outcomes from |amp|^2 by inverse-CDF sampling: out[s] is the smallest basis
  * index whose cumulative probability exceeds u[s] * norm^2 (u[s] in [0, 1), drawn by the caller).  The register
- * is not collapsed.  Equivalent to measuring every qubit with MZ (gates.py:188-190) on independent copies. */
+ * is not collapsed.  Equivalent to measuring every qubit with MZ (gates.py:188-190) on independent copies.  An index of
+ * |amp|^2 = 0 is never returned: where rounding lets a draw fall past the last amplitude of positive weight that could
+ * hold it, that amplitude is the answer. */
 int qsv_sample(qsv_state *st, int shots, const double *u, uint64_t *out);
 
 /* ---- d-level mode registers: the "d x d (d^2 x d^2) operator along mode axes" contraction of

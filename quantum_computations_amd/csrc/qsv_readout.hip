@@ -106,6 +106,10 @@ __global__ __launch_bounds__(QSV_BLOCK) void k_inner(const amp_t *__restrict__ a
 // Sampling, pass 1: chunk_sums[c] = sum of |amp|^2 over chunk c (SAMPLE_CHUNK consecutive amplitudes per workgroup).
 constexpr int SAMPLE_CHUNK = 4096;
 
+// |amp|^2 as BOTH passes form it: written with fma so that no pass is left to the compiler's contraction (pass 1 adds the
+// weight to a sum in the same statement, pass 2 stores it first) -- a weight is the same double wherever it is formed.
+__device__ __forceinline__ double sample_weight(amp_t v) { return fma(v.x, v.x, v.y * v.y); }
+
 __global__ __launch_bounds__(QSV_BLOCK) void k_chunk_sums(const amp_t *__restrict__ a, uint64_t amps,
                                                          double *__restrict__ chunk_sums) {
     const uint64_t chunks = (amps + SAMPLE_CHUNK - 1) / SAMPLE_CHUNK;
@@ -115,23 +119,25 @@ __global__ __launch_bounds__(QSV_BLOCK) void k_chunk_sums(const amp_t *__restric
         constexpr int PER = SAMPLE_CHUNK / QSV_BLOCK;
         const uint64_t first = c * SAMPLE_CHUNK + static_cast<uint64_t>(threadIdx.x) * PER;
         for (int k = 0; k < PER; ++k)
-            if (first + k < amps) {
-                const amp_t v = a[first + k];
-                s += v.x * v.x + v.y * v.y;
-            }
+            if (first + k < amps) s += sample_weight(a[first + k]);
         __syncthreads();  // block_sum2 reuses its shared scratch across iterations
         block_sum2(s, unused);
         if (threadIdx.x == 0) chunk_sums[c] = s;
     }
 }
 
-// Sampling, pass 2: one workgroup per shot walks its chunk and returns the first index whose running sum of
-// |amp|^2 exceeds `residual` (clamped to the chunk's last amplitude against rounding).
+// Sampling, pass 2: one workgroup per shot walks its chunk and returns the first index whose running sum of |amp|^2
+// exceeds `residual`; where rounding leaves no such index -- this walk and pass 1 add the same weights in different
+// orders -- the last one of positive weight, never an amplitude of weight zero.  sample_walk of qsv_readout_layout.h is
+// this rule on the host, step for step.
 __global__ __launch_bounds__(QSV_BLOCK) void k_sample_in_chunk(const amp_t *__restrict__ a, uint64_t amps,
                                                               const uint64_t *__restrict__ chunk_of_shot,
                                                               const double *__restrict__ residual_of_shot,
                                                               uint64_t *__restrict__ out) {
     __shared__ double part[QSV_BLOCK];
+    __shared__ double before;      // the running sum in front of the owner thread
+    __shared__ int owner_thread;   // the thread that holds the answer
+    __shared__ int crossed;        // the thread sums crossed the residual (else: the last thread of positive sum)
     constexpr int PER = SAMPLE_CHUNK / QSV_BLOCK;
     const uint64_t c = chunk_of_shot[blockIdx.x];
     const double residual = residual_of_shot[blockIdx.x];
@@ -139,11 +145,7 @@ __global__ __launch_bounds__(QSV_BLOCK) void k_sample_in_chunk(const amp_t *__re
     double mine[PER];
     double s = 0.0;
     for (int k = 0; k < PER; ++k) {
-        double p = 0.0;
-        if (first + k < amps) {
-            const amp_t v = a[first + k];
-            p = v.x * v.x + v.y * v.y;
-        }
+        const double p = first + k < amps ? sample_weight(a[first + k]) : 0.0;
         mine[k] = p;
         s += p;
     }
@@ -151,25 +153,35 @@ __global__ __launch_bounds__(QSV_BLOCK) void k_sample_in_chunk(const amp_t *__re
     __syncthreads();
     if (threadIdx.x == 0) {
         double run = 0.0;
-        int t = 0;
-        for (; t < QSV_BLOCK - 1; ++t) {
-            if (run + part[t] > residual) break;
-            run += part[t];
+        int owner = -1, last = -1;
+        for (int t = 0; t < QSV_BLOCK; ++t) {
+            const double sum = part[t];
+            if (sum > 0.0) last = t;
+            if (run + sum > residual) {
+                owner = t;
+                break;
+            }
+            run += sum;
         }
-        part[0] = run;                       // sum before thread t
-        part[1] = static_cast<double>(t);    // the thread that holds the crossing
+        before = run;
+        crossed = owner >= 0;
+        owner_thread = owner >= 0 ? owner : (last < 0 ? 0 : last);
     }
     __syncthreads();
-    const int owner = static_cast<int>(part[1]);
-    if (threadIdx.x == owner) {
-        double run = part[0];
-        int k = 0;
-        for (; k < PER - 1; ++k) {
-            if (run + mine[k] > residual) break;
+    if (static_cast<int>(threadIdx.x) == owner_thread) {
+        double run = before;
+        int slot = -1, last = -1;
+        for (int k = 0; k < PER; ++k) {
+            if (mine[k] > 0.0) last = k;
+            if (crossed && run + mine[k] > residual) {
+                slot = k;
+                break;
+            }
             run += mine[k];
         }
-        uint64_t idx = first + k;
-        if (idx >= amps) idx = amps - 1;
+        if (slot < 0) slot = last < 0 ? 0 : last;
+        uint64_t idx = first + slot;
+        if (idx >= amps) idx = amps - 1;   // a chunk of zero weight only: sample_chunks never picks one
         out[blockIdx.x] = idx;
     }
 }

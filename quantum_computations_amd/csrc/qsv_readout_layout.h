@@ -275,6 +275,42 @@ inline SampleChunks sample_chunks(const std::vector<double> &sums, const double 
     return out;
 }
 
+// The walk inside the chosen chunk (k_sample_in_chunk spells out the same steps): thread t owns p[t * slots .. (t + 1) * slots),
+// the |amp|^2 of its amplitudes, 0 past the end of the register.  Returns the offset in the chunk of the first amplitude
+// at which the running sum exceeds `residual` -- over the thread sums first, then over the owner's slots -- and, where
+// rounding leaves no such amplitude, of the last one with p > 0: the rule of qsv_channel_layout.h's pick_branch, at both
+// levels.  The two levels and pass 1 add the same numbers in different orders, so a residual within rounding of the
+// chunk's (or the owner's) sum can find no crossing; an amplitude of weight zero is never the answer (0 if all are zero).
+inline int sample_walk(const double *p, int threads, int slots, double residual) {
+    double run = 0.0;
+    int owner = -1, last = -1;
+    for (int t = 0; t < threads; ++t) {
+        double s = 0.0;
+        for (int k = 0; k < slots; ++k) s += p[t * slots + k];
+        if (s > 0.0) last = t;
+        if (run + s > residual) {
+            owner = t;
+            break;
+        }
+        run += s;
+    }
+    const bool crossed = owner >= 0;   // `run` is then the sum in front of the owner
+    if (!crossed) owner = last < 0 ? 0 : last;
+    int slot = -1;
+    last = -1;
+    for (int k = 0; k < slots; ++k) {
+        const double m = p[owner * slots + k];
+        if (m > 0.0) last = k;
+        if (crossed && run + m > residual) {
+            slot = k;
+            break;
+        }
+        run += m;
+    }
+    if (slot < 0) slot = last < 0 ? 0 : last;
+    return owner * slots + slot;
+}
+
 // ---- Pauli passes (k_expect_pauli_group, k_pauli_rotate_group) ----------------------------------------------------------
 inline int pauli_width(int count) { return count <= 1 ? 1 : count <= 2 ? 2 : count <= 4 ? 4 : 8; }   // the kernels' T
 

@@ -24,6 +24,7 @@
 //                                               W nins D pos[0..8) | tiles nins k l h lmask log_s regions pos[0..8) | hoff[0..64)
 //   rdmunpack n amps k variant remap cus bits.. raw[0 .. entries)  -> rho_out[0 .. 2 D D)
 //   sample chunks shots sums.. u..           -> status total | chunk.. | resid..
+//   samplewalk threads slots residual p..    -> offset in the chunk   (p: threads * slots doubles)
 //   paulisum n terms {xmask zmask}..         -> per pass of qsv_pauli_plan::plan: ok width items xmask pivot odd zmask[0..8) |
 //   passraw n xmask pivot count {zmask n_y}..  -> ok width            (a pass as given, well-formed or not)
 //   paulirot n terms {xmask zmask cs sn}..   -> per pass of qsv_pauli_rotation_plan::plan:
@@ -266,6 +267,13 @@ int main() {
                 std::printf(" |");
                 put_doubles(c.resid.data(), c.resid.size());
             }
+        } else if (what == "samplewalk") {
+            int threads, slots;
+            double residual;
+            in >> threads >> slots >> residual;
+            if (threads < 1 || slots < 1) std::exit(3);
+            const std::vector<double> p = doubles(in, static_cast<size_t>(threads) * slots);
+            std::printf("%d", sample_walk(p.data(), threads, slots, residual));
         } else if (what == "paulisum") {
             int n, count;
             in >> n >> count;

@@ -5,7 +5,8 @@ tests/layout/layout_driver.cpp is compiled against the header with AddressSaniti
 tests/test_layout_host.py compiles it; requests go in as text and answers come back as text.  Every check compares the
 header with a NumPy model written here: the tile and byte tables of the qubit permutation (end to end against the oracle),
 the plan of a reduced density matrix (form, tile sizes, offset tables, argument structs, grid) and the unpacking of the
-matrix cores' result layout, the chunk choice of the sampler, and the argument structs of the Pauli passes.
+matrix cores' result layout, the chunk choice of the sampler and its walk inside the chunk, and the argument structs of
+the Pauli passes.
 """
 from __future__ import annotations
 
@@ -279,6 +280,108 @@ def test_sample_chunks(ask):
             assert nums(rest[0]) == chunk and np.array_equal(floats(rest[1]), np.array(resid))
             assert all(sums[c] > 0.0 for c in chunk) and all(r >= 0.0 for r in resid)
     assert statuses[:len(lists)] == [0] * len(lists) and statuses[len(lists):] == [1, 1, 2, 2]
+
+
+def walk_model(p, threads, slots, residual):
+    """sample_walk: the first crossing of the running sum, thread sums first and the owner's slots next; where rounding
+    leaves none, the last thread of positive sum and its last slot of positive weight."""
+    sums = []
+    for t in range(threads):
+        s = 0.0
+        for k in range(slots):
+            s += p[t * slots + k]
+        sums.append(s)
+    run, owner, last = 0.0, -1, -1
+    for t, s in enumerate(sums):
+        if s > 0.0:
+            last = t
+        if run + s > residual:
+            owner = t
+            break
+        run += s
+    crossed = owner >= 0
+    if not crossed:
+        owner = max(last, 0)
+    slot, last = -1, -1
+    for k in range(slots):
+        m = p[owner * slots + k]
+        if m > 0.0:
+            last = k
+        if crossed and run + m > residual:
+            slot = k
+            break
+        run += m
+    if slot < 0:
+        slot = max(last, 0)
+    return owner * slots + slot
+
+
+def walk_sums(p, threads, slots):
+    """What the walk can compare a residual with: the running sum over the thread sums, as the first level forms it, and
+    for every thread the running sum over its slots on top of the sum in front of it, as the second level does."""
+    firsts, seconds, run = [], [], 0.0
+    for t in range(threads):
+        s, inner = 0.0, run
+        for k in range(slots):
+            s += p[t * slots + k]
+            inner += p[t * slots + k]
+            seconds.append(inner)
+        run += s
+        firsts.append(run)
+    return firsts, seconds
+
+
+def test_sample_walk(ask):
+    rng = np.random.default_rng(13)
+
+    def weights(threads, slots, support):
+        p = np.zeros(threads * slots)
+        p[support] = rng.normal(size=len(support)) ** 2 + rng.normal(size=len(support)) ** 2
+        return [float(x) for x in p]
+    shapes = [(256, 16), (4, 4), (1, 16), (8, 1)]
+    cases = []
+    for threads, slots in shapes:
+        size = threads * slots
+        lists = [weights(threads, slots, np.arange(size)),                                              # dense
+                 weights(threads, slots, np.arange(max(1, size // 40))),                                # trailing zeros
+                 weights(threads, slots, np.arange(size // 2, size // 2 + max(1, slots // 2))),         # leading and trailing
+                 weights(threads, slots, rng.choice(size, size=max(1, size // 14), replace=False)),     # scattered
+                 weights(threads, slots, [size // 3]), weights(threads, slots, [0]), weights(threads, slots, [size - 1]),
+                 [0.0] * size]                                                                          # all zero: offset 0
+        for p in lists:
+            firsts, seconds = walk_sums(p, threads, slots)
+            marks = {0.0, firsts[-1], seconds[-1], sum(p), float(np.sum(p))}                            # the sequential sums
+            if size <= 64:                                                                              # and inner ones
+                marks |= set(firsts) | set(seconds[::3])
+            residuals = set()
+            for mark in marks:                                                                          # equal, one ulp above and below
+                residuals |= {mark, float(np.nextafter(mark, np.inf)), float(np.nextafter(mark, -np.inf)), 0.5 * mark}
+            residuals.add(2.0 * firsts[-1] + 1.0)                                                       # far past the end
+            cases += [(threads, slots, r, p) for r in sorted(residuals) if r >= 0.0]
+    answers = ask([f"samplewalk {threads} {slots} {r!r} {text(p)}" for threads, slots, r, p in cases])
+    fell_through = 0
+    for (threads, slots, r, p), (tokens,) in zip(cases, answers):
+        got, = nums(tokens)
+        assert got == walk_model(p, threads, slots, r), (threads, slots, r)
+        if any(p):
+            assert p[got] > 0.0, "never an amplitude of weight zero"
+            last = max(i for i, x in enumerate(p) if x > 0.0)
+            firsts, seconds = walk_sums(p, threads, slots)
+            if r >= max(firsts[-1], max(seconds)):
+                assert got == last, "past every running sum: the last possible amplitude"
+                fell_through += 1
+            if r == 0.0:
+                assert got == min(i for i, x in enumerate(p) if x > 0.0), "a residual of 0: the first possible amplitude"
+            # away from rounding the answer is the plain inverse CDF over the flat list
+            exact = np.cumsum(np.array(p, dtype=np.longdouble))
+            slack = 1e-12 * float(exact[-1])
+            if r < float(exact[-1]) - slack:
+                want = int(np.searchsorted(exact, np.longdouble(r), side="right"))
+                if abs(float(exact[want]) - r) > slack and (want == 0 or abs(float(exact[want - 1]) - r) > slack):
+                    assert got == want, (threads, slots, r)
+        else:
+            assert got == 0
+    assert fell_through >= 8 * len(shapes)
 
 
 # ---- Pauli passes ----------------------------------------------------------------------------------------------------------

@@ -101,7 +101,7 @@ typedef struct qsv_state qsv_state;
  *  - Every other entry point that takes the register flushes the queue first: sync, download, upload, copy (both
  *    registers), fill_random, scale, set_basis, norm2, inner, expect_*, probabilities, reduced_density, sample,
  *    measure*, collapse, insert, permute, apply_kq, apply_mcphase, apply_sequence, apply_pauli_rotation(s) (never
- *    queued themselves), apply_pauli_sum, pauli_transition_sum, pauli_rotations_adjoint (both registers), set_stream,
+ *    queued themselves), apply_layer and ensemble_apply_layer (likewise), apply_pauli_sum, pauli_transition_sum, pauli_rotations_adjoint (both registers), set_stream,
  *    set_option, device_ptr,
  *    timer_*, event_*, last_kernel, density_expect_paulis, apply_channel with a general channel, and qsv_flush itself.
  *    qsv_apply_channel with a mixed-unitary channel does NOT flush: its gate is queued like any other, and
@@ -214,6 +214,28 @@ int qsv_apply_pauli_rotations(qsv_state *st, int n_terms, const int *term_offset
 #define QSV_QFT_NO_SWAPS 2
 #define QSV_QFT_CONJUGATE 4
 int qsv_apply_qft(qsv_state *st, int m, const int *qubits, int flags, uint64_t *passes);
+/* ---- product layers: a one-qubit gate on each of many qubits in a few tile passes (csrc/qsv_layer.hip) ----
+ * psi <- (U_1 on qubits[0]) (x) ... (x) (U_k on qubits[k-1]) psi for k distinct qubits and any finite 2x2 complex matrices
+ * (unitarity is not demanded), the identity on every other qubit: what k calls of qsv_apply_1q give, to rounding.  The
+ * factors commute, so the layer is a SET: its stages are always applied in ascending order of the index bit n-1-qubit,
+ * whatever order the list has, and the rounded result does not depend on that order.  Every stage whose bit lies in one
+ * 4096-amplitude tile (index bits 0..5 and six more) runs in the same pass over the register (k_layer_tile;
+ * csrc/qsv_layer_plan.h): *passes (may be NULL) = max(1, ceil(h / 6)) with h the stage bits >= 6 -- a full 28-qubit layer
+ * is 4 passes, not 28; registers of at most 12 qubits take one.  k = 0 does nothing and launches nothing.
+ * qsv_ensemble_apply_layer gives every member of an ensemble (notation of the ensemble calls below: members =
+ * 2^(n_total - member_qubits), `qubits` are MEMBER qubits) matrices of its own, matrices[m][j] on qubits[j]; the plan is made on
+ * member bits and never depends on the number of members.  One stage has one statement of its arithmetic
+ * (csrc/qsv_layer_item.h): a member's amplitudes are bit for bit those of a register of its own after qsv_apply_layer with
+ * the member's matrices, wherever it sits, and qsv_apply_layer on the member part of an ensemble register gives the bits of
+ * qsv_ensemble_apply_layer with equal rows.
+ * The arguments are checked before the deferred queue is flushed or anything is launched: QSV_EINVAL (null pointer where
+ * k > 0, k < 0 or above the register's / member's qubits, a repeated or out-of-range qubit, an entry that is not finite; for
+ * the ensemble call also a view or member_qubits outside 0 .. n_total) leaves the register and the queue as they were;
+ * QSV_ESTATE on a mode register.  A valid call flushes the queue (a layer is never queued), is enqueued on the register's
+ * stream and returns without waiting; the caller's arrays may be reused on return.  qsv_apply_layer works on views. */
+int qsv_apply_layer(qsv_state *st, int k, const int *qubits, const double *matrices /* [k][2][2] complex, row-major */, uint64_t *passes);
+int qsv_ensemble_apply_layer(qsv_state *st, int member_qubits, int k, const int *qubits /* member-local */,
+                             const double *matrices /* [members][k][2][2] complex */, uint64_t *passes);
 
 /* ---- reversible register arithmetic: classical maps on the value of a qubit register ---- */
 /* A map acts on the integer y that m TARGET qubits spell (the first listed qubit the most significant, as in qsv_apply_qft),

@@ -68,6 +68,7 @@ SIGNATURES: dict[str, list] = {
     "qsv_apply_pauli_rotation": [_state_p, C.c_int, _int_p, C.c_char_p, C.c_double],
     "qsv_apply_pauli_rotations": [_state_p, C.c_int, _int_p, _int_p, C.c_char_p, _dbl_p, _u64_p],
     "qsv_apply_qft": [_state_p, C.c_int, _int_p, C.c_int, _u64_p],
+    "qsv_apply_layer": [_state_p, C.c_int, _int_p, _dbl_p, _u64_p],
     "qsv_arith_create": [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, _u64_p, C.c_uint64, C.c_int, C.POINTER(_state_p)],
     "qsv_arith_destroy": [_state_p],
     "qsv_arith_info": [_state_p, _int_p, _int_p, _int_p],
@@ -110,6 +111,7 @@ SIGNATURES: dict[str, list] = {
     "qsv_ensemble_apply_matrices": [_state_p, C.c_int, C.c_int, _int_p, _dbl_p],
     "qsv_ensemble_apply_diag_phase": [_state_p, C.c_int, _state_p, _dbl_p],
     "qsv_ensemble_expect_diag": [_state_p, C.c_int, _state_p, _dbl_p, _dbl_p],
+    "qsv_ensemble_apply_layer": [_state_p, C.c_int, C.c_int, _int_p, _dbl_p, _u64_p],
     "qsv_ensemble_expect_pauli_sum": [_state_p, C.c_int, C.c_int, _int_p, _int_p, C.c_char_p, _dbl_p, _dbl_p, _dbl_p],
     "qsv_reduced_density": [_state_p, C.c_int, _int_p, C.c_void_p],
     "qsv_reduced_density_state": [_state_p, C.c_int, _int_p, _state_p],

@@ -433,6 +433,25 @@ class DeviceState:
         _lib.call("qsv_apply_qft", self._h, len(qubits), _ints(qubits), flags, C.byref(passes))
         return passes.value
 
+    # ---- product layers ---------------------------------------------------------------------------
+    def apply_layer(self, matrices, qubits=None) -> "DeviceState":
+        """In-place one-qubit gate on each of ``qubits`` (``None``: all of them): ``matrices`` of shape ``(2, 2)`` is the same
+        gate on every listed qubit, ``(k, 2, 2)`` gives ``matrices[j]`` to ``qubits[j]``.  What ``k`` calls of
+        ``apply_matrix`` give, to rounding, in ``max(1, ceil(h / 6))`` passes over the register (``qsv_apply_layer``), ``h``
+        the listed qubits whose index bit is 6 or above.  The order of the list never changes a bit of the result; any
+        finite matrices are taken.  ``ShardedState`` has no such method: out of scope there."""
+        self._apply_layer(matrices, range(self.num_qubits) if qubits is None else qubits)
+        return self
+
+    def _apply_layer(self, matrices, qubits) -> int:
+        """Check the shapes and launch; returns the number of passes."""
+        from .layers import layer_table
+        qubits = [int(q) for q in qubits]
+        table = layer_table(matrices, len(qubits))
+        passes = C.c_uint64()
+        _lib.call("qsv_apply_layer", self._h, len(qubits), _ints(qubits), _dbl(table.view(np.float64)), C.byref(passes))
+        return passes.value
+
     # ---- reversible register arithmetic -------------------------------------------------------
     def apply_register_map(self, op, target, source=None, controls=(), *, inverse: bool = False) -> "DeviceState":
         """In-place classical map on the value of the ``target`` qubits (``arithmetic.RegisterMap``: modular addition and
@@ -824,6 +843,18 @@ class DensityState(DeviceState):
             raise ValueError(f"qubit index out of range for a {n}-qubit register")
         self._apply_qft(qubits, inverse=inverse, swaps=swaps)
         self._apply_qft(qubits, inverse=inverse, swaps=swaps, qubit_offset=n, conjugate=True)
+        return self
+
+    def apply_layer(self, matrices, qubits=None) -> "DensityState":
+        """``U rho U^dagger`` for the product ``U`` of the layer: ``matrices[j]`` on the row qubit ``qubits[j]`` and its complex
+        conjugate on the column qubit ``n + qubits[j]``, in ONE layer of ``2 k`` stages."""
+        from .layers import layer_table
+        n = self.num_qubits
+        qubits = list(range(n)) if qubits is None else [int(q) for q in qubits]
+        if any(not 0 <= q < n for q in qubits):
+            raise ValueError(f"qubit index out of range for a {n}-qubit register")
+        table = layer_table(matrices, len(qubits))
+        self._apply_layer(np.concatenate([table, np.conjugate(table)]), qubits + [n + q for q in qubits])
         return self
 
     def apply_register_map(self, op, target, source=None, controls=(), *, inverse: bool = False) -> "DensityState":

@@ -216,6 +216,29 @@ class TrajectoryEnsemble:
                   buf.view(np.float64).ctypes.data_as(C.POINTER(C.c_double)))
         return self
 
+    def apply_layer(self, matrices, qubits=None) -> "TrajectoryEnsemble":
+        """A one-qubit gate on each of the member qubits ``qubits`` (``None``: all of them) of every member, in a few tile
+        passes.  ``matrices`` of shape ``(2, 2)`` or ``(k, 2, 2)``: the same gates for every member
+        (``DeviceState.apply_layer`` on the member part of the register); ``(members, k, 2, 2)``: member ``m`` takes
+        ``matrices[m]`` (``qsv_ensemble_apply_layer``).  Either way a member's amplitudes are bit for bit those of a register
+        of its own after ``apply_layer`` with its matrices.  ``last_passes`` holds the passes."""
+        from .layers import layer_table
+        qubits = list(range(self.member_qubits)) if qubits is None else [int(q) for q in qubits]
+        k = len(qubits)
+        if np.ndim(matrices) < 4:
+            if any(not 0 <= q < self.member_qubits for q in qubits):
+                raise ValueError(f"qubit index out of range for members of {self.member_qubits} qubits")
+            self.last_passes = self.state._apply_layer(layer_table(matrices, k), [q + self.member_bits for q in qubits])
+            return self
+        table = np.ascontiguousarray(matrices, dtype=np.complex128)
+        if table.shape != (self.members, k, 2, 2):
+            raise ValueError(f"per-member matrices must have shape [members, k, 2, 2] = [{self.members}, {k}, 2, 2]")
+        passes = C.c_uint64()
+        _lib.call("qsv_ensemble_apply_layer", self.state._h, self.member_qubits, k, _ints(qubits),
+                  table.view(np.float64).ctypes.data_as(C.POINTER(C.c_double)), C.byref(passes))
+        self.last_passes = int(passes.value)
+        return self
+
     def apply_diagonal_phase(self, diag, gammas) -> "TrajectoryEnsemble":
         """``psi_m[i] *= exp(-i gammas[m] d[i])`` for a ``DiagonalOperator`` of ``member_qubits`` qubits: one gamma per member."""
         _diagonal_operand(diag)

@@ -1,0 +1,70 @@
+"""Product layers: a one-qubit gate on each of many qubits, applied in a few tile passes.
+
+The helpers here build the ``(..., 2, 2)`` arrays that ``DeviceState.apply_layer``, ``DensityState.apply_layer`` and
+``TrajectoryEnsemble.apply_layer`` take; they broadcast over their angle, so ``rx(betas[:, None] * np.ones(n))`` is the
+``[members, n, 2, 2]`` table of a per-member mixer.  Conventions are the project's: ``rz(t) = exp(-i t/2 Z)``.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+
+def _half(theta) -> np.ndarray:
+    return 0.5 * np.asarray(theta, dtype=np.float64)
+
+
+def rx(theta) -> np.ndarray:
+    """``[[cos t/2, -i sin t/2], [-i sin t/2, cos t/2]]`` for every entry of ``theta``."""
+    h = _half(theta)
+    c, s = np.cos(h), np.sin(h)
+    out = np.empty(h.shape + (2, 2), dtype=np.complex128)
+    out[..., 0, 0] = out[..., 1, 1] = c
+    out[..., 0, 1] = out[..., 1, 0] = -1j * s
+    return out
+
+
+def ry(theta) -> np.ndarray:
+    """``[[cos t/2, -sin t/2], [sin t/2, cos t/2]]`` for every entry of ``theta``."""
+    h = _half(theta)
+    c, s = np.cos(h), np.sin(h)
+    out = np.empty(h.shape + (2, 2), dtype=np.complex128)
+    out[..., 0, 0] = out[..., 1, 1] = c
+    out[..., 0, 1] = -s
+    out[..., 1, 0] = s
+    return out
+
+
+def rz(theta) -> np.ndarray:
+    """``diag(exp(-i t/2), exp(+i t/2))`` for every entry of ``theta``."""
+    h = _half(theta)
+    out = np.zeros(h.shape + (2, 2), dtype=np.complex128)
+    out[..., 0, 0] = np.cos(h) - 1j * np.sin(h)
+    out[..., 1, 1] = np.cos(h) + 1j * np.sin(h)
+    return out
+
+
+def hadamard() -> np.ndarray:
+    return np.array([[1.0, 1.0], [1.0, -1.0]], dtype=np.complex128) / np.sqrt(2.0)
+
+
+def product_matrix(matrices) -> np.ndarray:
+    """``matrices[0] (x) matrices[1] (x) ...``: the ``2^k x 2^k`` matrix of a layer whose first listed qubit is the most
+    significant leg, as ``apply_matrix`` takes it.  For tests and small hosts."""
+    matrices = np.asarray(matrices, dtype=np.complex128)
+    if matrices.ndim != 3 or matrices.shape[1:] != (2, 2):
+        raise ValueError("matrices must have shape [k, 2, 2]")
+    out = np.ones((1, 1), dtype=np.complex128)
+    for m in matrices:
+        out = np.kron(out, m)
+    return out
+
+
+def layer_table(matrices, k: int, what: str = "matrices") -> np.ndarray:
+    """``matrices`` of shape ``(2, 2)`` (the same gate on each of the ``k`` qubits) or ``(k, 2, 2)`` as a contiguous
+    ``[k, 2, 2]`` complex128 array; ``ValueError`` for any other shape."""
+    m = np.asarray(matrices, dtype=np.complex128)
+    if m.shape == (2, 2):
+        m = np.broadcast_to(m, (k, 2, 2))
+    if m.shape != (k, 2, 2):
+        raise ValueError(f"{what} must have shape (2, 2) or (k, 2, 2) = ({k}, 2, 2), not {np.shape(matrices)}")
+    return np.ascontiguousarray(m)

@@ -2,12 +2,14 @@
 ``|+>^n`` with the mixer ``B = sum_q X_q``, the energy ``<D>`` and its gradient in all ``2 p`` angles by one adjoint walk.
 
 The cost layer is one pass over the register whatever ``D`` was built from (``DeviceState.apply_diagonal_phase``); the
-mixer is ``RX(2 beta)`` on every qubit through ``apply_matrix``, which the deferred queue batches into shared passes.
+mixer is ``RX(2 beta)`` on every qubit through ``apply_matrix``, which the deferred queue batches into shared passes, or
+-- ``mixer="layer"`` -- one product layer (``apply_layer``): ``max(1, ceil((n - 6) / 6))`` passes.
 """
 from __future__ import annotations
 
 import numpy as np
 
+from . import layers
 from .device import DeviceState
 from .diagonal import DiagonalOperator
 
@@ -30,8 +32,17 @@ def plus_state(n_qubits: int, device: int = 0) -> DeviceState:
     return state
 
 
-def mixer(state: DeviceState, beta: float) -> DeviceState:
-    """In place ``exp(-i beta sum_q X_q) state``: ``RX(2 beta)`` on every qubit."""
+def _mixer_kind(mixer: str, kinds: tuple) -> str:
+    if mixer not in kinds:
+        raise ValueError(f"mixer must be one of {kinds}, not {mixer!r}")
+    return mixer
+
+
+def mixer(state: DeviceState, beta: float, mixer: str = "gates") -> DeviceState:
+    """In place ``exp(-i beta sum_q X_q) state``: ``RX(2 beta)`` on every qubit -- ``mixer="gates"``: one ``apply_matrix``
+    per qubit; ``"layer"``: one ``apply_layer``."""
+    if _mixer_kind(mixer, ("gates", "layer")) == "layer":
+        return state.apply_layer(layers.rx(2.0 * float(beta)))
     c, s = np.cos(beta), np.sin(beta)
     rx = np.array([[c, -1j * s], [-1j * s, c]], dtype=complex)
     for q in range(state.num_qubits):
@@ -39,42 +50,47 @@ def mixer(state: DeviceState, beta: float) -> DeviceState:
     return state
 
 
+_apply_mixer = mixer      # for the functions below, whose ``mixer`` keyword hides the function
+
 def mixer_terms(n_qubits: int) -> list[tuple]:
     """``B = sum_q X_q`` as a Pauli term list."""
     return [(1.0, "X", [q]) for q in range(n_qubits)]
 
 
-def run(diag: DiagonalOperator, gammas, betas, state: DeviceState | None = None) -> DeviceState:
+def run(diag: DiagonalOperator, gammas, betas, state: DeviceState | None = None, mixer: str = "gates") -> DeviceState:
     """The QAOA state: for every layer the cost phase ``exp(-i gamma_l D)`` and then the mixer ``exp(-i beta_l B)``, on
-    ``state`` in place (``|+>^n`` on the diagonal's device when None).  Returns the register."""
+    ``state`` in place (``|+>^n`` on the diagonal's device when None).  ``mixer``: as in ``mixer()``.  Returns the register."""
     gammas, betas = _angles(gammas, betas)
+    kind = _mixer_kind(mixer, ("gates", "layer"))
     if state is None:
         state = plus_state(diag.num_qubits, diag.device)
     for gamma, beta in zip(gammas, betas):
         state.apply_diagonal_phase(diag, gamma)
-        mixer(state, beta)
+        _apply_mixer(state, beta, kind)
     return state
 
 
-def energy_and_gradient(diag: DiagonalOperator, gammas, betas, state: DeviceState | None = None):
+def energy_and_gradient(diag: DiagonalOperator, gammas, betas, state: DeviceState | None = None, mixer: str = "gates"):
     """``(E, dE/dgamma, dE/dbeta)`` of ``E = <psi_p| D |psi_p>`` by one adjoint walk: the layers forward, ``E`` and
     ``lambda = D psi``, then for the last layer first ``dE/dbeta_l = 2 Im <lambda| B |psi>``, the mixer undone on both
     registers, and ``dE/dgamma_l = 2 Im <lambda| D |psi>`` from ``qsv_diag_phase_adjoint``, which undoes the cost phase
-    on both in the same pass.  ``state`` (``|+>^n`` when None) holds its input again on return, up to rounding."""
+    on both in the same pass.  ``state`` (``|+>^n`` when None) holds its input again on return, up to rounding.
+    ``mixer``: as in ``mixer()``, for the walk forward and the walk back."""
     gammas, betas = _angles(gammas, betas)
+    kind = _mixer_kind(mixer, ("gates", "layer"))
     own = state is None
     psi = plus_state(diag.num_qubits, diag.device) if own else state
     lam = DeviceState.zeros(psi.num_qubits, psi.device)
     try:
-        run(diag, gammas, betas, psi)
+        run(diag, gammas, betas, psi, kind)
         energy = psi.expect_diagonal(diag).mean
         psi.apply_diagonal_operator(diag, out=lam)
         b_terms = mixer_terms(psi.num_qubits)
         d_gamma, d_beta = np.zeros_like(gammas), np.zeros_like(betas)
         for layer in range(len(gammas) - 1, -1, -1):
             d_beta[layer] = 2.0 * lam.transition_pauli_sum(b_terms, psi).imag
-            mixer(psi, -betas[layer])
-            mixer(lam, -betas[layer])
+            _apply_mixer(psi, -betas[layer], kind)
+            _apply_mixer(lam, -betas[layer], kind)
             d_gamma[layer] = 2.0 * psi.diagonal_phase_adjoint(diag, lam, -gammas[layer]).imag
     finally:
         lam.close()
@@ -83,10 +99,11 @@ def energy_and_gradient(diag: DiagonalOperator, gammas, betas, state: DeviceStat
     return energy, d_gamma, d_beta
 
 
-def energies(diag: DiagonalOperator, gammas, betas, batch: int = 256, threshold: float | None = None):
+def energies(diag: DiagonalOperator, gammas, betas, batch: int = 256, threshold: float | None = None, mixer: str = "rotations"):
     """``<D>`` at ``M`` parameter points, ``gammas[M, p]`` and ``betas[M, p]``, ``batch`` points per register: every point is a
     member of an ``Ensemble``.  Per layer one per-member cost phase, then the mixer as ``n``
-    per-member ``X`` rotations of angle ``2 beta_m``.  Returns ``E[M]``; with a ``threshold`` also
+    per-member ``X`` rotations of angle ``2 beta_m`` (``mixer="rotations"``) or as one per-member product layer of
+    ``layers.rx(2 beta_m)`` on every qubit (``mixer="layer"``).  Returns ``E[M]``; with a ``threshold`` also
     ``P(D <= threshold)[M]``.  Surplus members of the last chunk take angles of zero and are dropped."""
     from . import sweep
     from .ensemble import Ensemble
@@ -95,7 +112,8 @@ def energies(diag: DiagonalOperator, gammas, betas, batch: int = 256, threshold:
     betas = np.atleast_2d(np.asarray(betas, dtype=np.float64))
     if gammas.ndim != 2 or gammas.shape != betas.shape:
         raise ValueError("gammas and betas must both have shape [points, layers]")
-    points, layers = gammas.shape
+    as_layer = _mixer_kind(mixer, ("rotations", "layer")) == "layer"
+    points, n_layers = gammas.shape
     n = diag.num_qubits
     plus = np.full(1 << n, 2.0 ** (-0.5 * n), dtype=np.complex128)
     x_rotations = [(0.0, "X", [q]) for q in range(n)]
@@ -109,11 +127,14 @@ def energies(diag: DiagonalOperator, gammas, betas, batch: int = 256, threshold:
                 ens = Ensemble.from_ket(plus, members, diag.device)
             else:
                 ens.reset(plus)
-            g, b = np.zeros((members, layers)), np.zeros((members, layers))
+            g, b = np.zeros((members, n_layers)), np.zeros((members, n_layers))
             g[:count], b[:count] = gammas[first:first + count], betas[first:first + count]
-            for layer in range(layers):
+            for layer in range(n_layers):
                 ens.apply_diagonal_phase(diag, g[:, layer])
-                ens.apply_pauli_rotations(x_rotations, np.repeat(2.0 * b[:, layer, None], n, axis=1))
+                if as_layer:
+                    ens.apply_layer(layers.rx(np.repeat(2.0 * b[:, layer, None], n, axis=1)))
+                else:
+                    ens.apply_pauli_rotations(x_rotations, np.repeat(2.0 * b[:, layer, None], n, axis=1))
             moments = ens.expect_diagonal(diag, threshold)
             energy[first:first + count] = moments.mean[:count]
             below[first:first + count] = moments.probability_below[:count]
@@ -123,12 +144,12 @@ def energies(diag: DiagonalOperator, gammas, betas, batch: int = 256, threshold:
     return energy if threshold is None else (energy, below)
 
 
-def landscape(diag: DiagonalOperator, gamma_grid, beta_grid, batch: int = 256) -> np.ndarray:
+def landscape(diag: DiagonalOperator, gamma_grid, beta_grid, batch: int = 256, mixer: str = "rotations") -> np.ndarray:
     """The ``p = 1`` surface ``E[G, B]`` over ``gamma_grid x beta_grid`` through ``energies``."""
     gamma_grid = np.asarray(gamma_grid, dtype=np.float64).reshape(-1)
     beta_grid = np.asarray(beta_grid, dtype=np.float64).reshape(-1)
     g, b = np.meshgrid(gamma_grid, beta_grid, indexing="ij")
-    return energies(diag, g.reshape(-1, 1), b.reshape(-1, 1), batch=batch).reshape(gamma_grid.size, beta_grid.size)
+    return energies(diag, g.reshape(-1, 1), b.reshape(-1, 1), batch=batch, mixer=mixer).reshape(gamma_grid.size, beta_grid.size)
 
 
 def minimise(diag: DiagonalOperator, p: int, x0=None, **scipy_options):

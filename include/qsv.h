@@ -101,7 +101,7 @@ typedef struct qsv_state qsv_state;
  *  - Every other entry point that takes the register flushes the queue first: sync, download, upload, copy (both
  *    registers), fill_random, scale, set_basis, norm2, inner, expect_*, probabilities, reduced_density, sample,
  *    measure*, collapse, insert, permute, apply_kq, apply_mcphase, apply_sequence, apply_pauli_rotation(s) (never
- *    queued themselves), apply_layer and ensemble_apply_layer (likewise), apply_pauli_sum, pauli_transition_sum, pauli_rotations_adjoint (both registers), set_stream,
+ *    queued themselves), apply_layer and ensemble_apply_layer (likewise), layer_adjoint and layer_transition (both registers), apply_pauli_sum, pauli_transition_sum, pauli_rotations_adjoint (both registers), set_stream,
  *    set_option, device_ptr,
  *    timer_*, event_*, last_kernel, density_expect_paulis, apply_channel with a general channel, and qsv_flush itself.
  *    qsv_apply_channel with a mixed-unitary channel does NOT flush: its gate is queued like any other, and
@@ -236,6 +236,40 @@ int qsv_apply_qft(qsv_state *st, int m, const int *qubits, int flags, uint64_t *
 int qsv_apply_layer(qsv_state *st, int k, const int *qubits, const double *matrices /* [k][2][2] complex, row-major */, uint64_t *passes);
 int qsv_ensemble_apply_layer(qsv_state *st, int member_qubits, int k, const int *qubits /* member-local */,
                              const double *matrices /* [members][k][2][2] complex */, uint64_t *passes);
+/* ---- adjoint walk through a product layer: every qubit's transition matrix in the layer's own passes
+ *      (csrc/qsv_layer_adjoint.hip) ----
+ * For a qubit q (index bit n-1-q) and two registers,
+ *     T_q[a][b] = <lambda| (|a><b| on q) |psi> = sum over the other qubits of conj(lambda[a, rest]) psi[b, rest].
+ * qsv_layer_adjoint walks the plan of qsv_apply_layer for `qubits` unchanged (csrc/qsv_layer_plan.h: the same passes in the
+ * same order, the stages in ascending order of the index bit).  For stage s with W = inverse[s] it first sets
+ * values[s][a][b] = T_q (interleaved complex, row-major: re T[0][0], im T[0][0], re T[0][1], ...; `values` and `inverse` are
+ * indexed as `qubits` is) on the registers AS THEY STAND, the stages of lower bits already undone, and then applies W to that
+ * qubit of BOTH registers with the one statement of a stage's arithmetic (csrc/qsv_layer_item.h).  So
+ *  - on return each register holds, bit for bit, what qsv_apply_layer(reg, k, qubits, inverse) would have left in it: BOTH
+ *    registers are consumed / rewound, as by qsv_pauli_rotations_adjoint;
+ *  - for UNITARY inverse[s] every values[s] equals, up to rounding, the value on the registers at entry: a unitary on
+ *    another qubit cancels in the sum over that qubit.  For other matrices the operational definition above is what holds.
+ * With psi = (U_1 (x) ... (x) U_k) psi0, inverse[s] = U_s^dagger and lambda = H psi, the derivative of E = <psi|H|psi> in a
+ * parameter of U_s is 2 Re sum_ab G[a][b] values[s][a][b], G = (dU_s/dtheta) U_s^dagger; for U = exp(-i theta/2 P) that is
+ * Im <lambda|P|psi>, the convention of qsv_pauli_rotations_adjoint.
+ * qsv_layer_transition returns the same values with nothing applied and nothing stored: both registers are read only, and
+ * bra may be ket (the same handle or the same memory), which gives the one-qubit reduced density matrices of a ket,
+ * rho_q[b][a] = values[q][a][b].
+ * *passes (may be NULL) = the kernel launches = the passes of the forward plan, max(1, ceil(h / 6)); the sums add no launch.
+ * A stage's eight doubles are summed in a fixed order -- over a wave by shuffles, over the four waves of a workgroup in wave
+ * order, over the tiles a workgroup walks in index order, and over the workgroups' partials by the host in index order: no
+ * atomics, and a call's values are the same bits from run to run at a given grid (QSV_OPT_GRID_CAP).
+ * Everything is checked before either deferred queue is flushed or anything is launched: QSV_EINVAL for a null handle, a
+ * null array where k > 0, k < 0 or above the register's qubits, a repeated or out-of-range qubit, an entry of `inverse` that
+ * is not finite, registers of different sizes or devices and -- qsv_layer_adjoint only -- psi and lambda whose memory meets
+ * (the same handle included); QSV_ESTATE for a mode register.  k = 0 returns QSV_OK with 0 passes, no launch and `values`
+ * untouched.  A valid call flushes both queues, synchronises lambda's (bra's) stream, sends its launches back to back on
+ * psi's (ket's) stream, and ends with one copy of the partial sums and one synchronisation: it returns with both
+ * registers finished.  Both calls work on views.  Ensembles (values per member) and density registers are not served. */
+int qsv_layer_adjoint(qsv_state *psi, qsv_state *lambda, int k, const int *qubits, const double *inverse /* [k][2][2] complex */,
+                      double *values /* [k][2][2] complex */, uint64_t *passes);
+int qsv_layer_transition(qsv_state *bra, qsv_state *ket, int k, const int *qubits, double *values /* [k][2][2] complex */,
+                         uint64_t *passes);
 
 /* ---- reversible register arithmetic: classical maps on the value of a qubit register ---- */
 /* A map acts on the integer y that m TARGET qubits spell (the first listed qubit the most significant, as in qsv_apply_qft),

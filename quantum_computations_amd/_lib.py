@@ -69,6 +69,8 @@ SIGNATURES: dict[str, list] = {
     "qsv_apply_pauli_rotations": [_state_p, C.c_int, _int_p, _int_p, C.c_char_p, _dbl_p, _u64_p],
     "qsv_apply_qft": [_state_p, C.c_int, _int_p, C.c_int, _u64_p],
     "qsv_apply_layer": [_state_p, C.c_int, _int_p, _dbl_p, _u64_p],
+    "qsv_layer_adjoint": [_state_p, _state_p, C.c_int, _int_p, _dbl_p, _dbl_p, _u64_p],
+    "qsv_layer_transition": [_state_p, _state_p, C.c_int, _int_p, _dbl_p, _u64_p],
     "qsv_arith_create": [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, _u64_p, C.c_uint64, C.c_int, C.POINTER(_state_p)],
     "qsv_arith_destroy": [_state_p],
     "qsv_arith_info": [_state_p, _int_p, _int_p, _int_p],

@@ -452,6 +452,48 @@ class DeviceState:
         _lib.call("qsv_apply_layer", self._h, len(qubits), _ints(qubits), _dbl(table.view(np.float64)), C.byref(passes))
         return passes.value
 
+    # ---- adjoint walk through a product layer ------------------------------
+    def layer_adjoint(self, matrices, lam: "DeviceState", qubits=None) -> np.ndarray:
+        """The backward walk through the layer ``apply_layer(matrices, qubits)`` made ``self`` with: ``matrices`` are the
+        FORWARD factors (``(2, 2)`` or ``(k, 2, 2)``), the library is handed their conjugate transposes.  Returns
+        ``T[k, 2, 2]`` with ``T[j][a][b] = <lam| (|a><b| on qubits[j]) |self>`` and leaves in both registers, bit for bit,
+        what ``apply_layer`` with the conjugate transposes leaves: ``self`` is the register from before the layer (for
+        unitary factors, up to rounding) and ``lam`` has gone back with it -- both are consumed.  Costs the passes of the
+        forward layer.  ``layers.gradient(T, generators)`` turns ``T`` into derivatives."""
+        return self._layer_adjoint(matrices, lam, range(self.num_qubits) if qubits is None else qubits)[0]
+
+    def _layer_adjoint(self, matrices, lam: "DeviceState", qubits) -> tuple[np.ndarray, int]:
+        """Check the shapes and launch; returns ``(T, passes)``."""
+        from .layers import layer_table
+        _ket_operand(lam, "lam")
+        qubits = [int(q) for q in qubits]
+        inverse = np.ascontiguousarray(np.conjugate(np.swapaxes(layer_table(matrices, len(qubits)), 1, 2)))
+        values = np.zeros((len(qubits), 2, 2), dtype=np.complex128)
+        passes = C.c_uint64()
+        _lib.call("qsv_layer_adjoint", self._h, lam._h, len(qubits), _ints(qubits), _dbl(inverse.view(np.float64)),
+                  _dbl(values.view(np.float64)), C.byref(passes))
+        return values, passes.value
+
+    def layer_transition(self, ket: "DeviceState", qubits=None) -> np.ndarray:
+        """``T[k, 2, 2]`` with ``T[j][a][b] = <self| (|a><b| on qubits[j]) |ket>`` for each of ``qubits`` (``None``: all of
+        them); ``self`` is the bra and ``ket`` may be ``self``.  Read-only, in the passes of a product layer on ``qubits``."""
+        return self._layer_transition(ket, range(self.num_qubits) if qubits is None else qubits)[0]
+
+    def _layer_transition(self, ket: "DeviceState", qubits) -> tuple[np.ndarray, int]:
+        _ket_operand(ket, "ket")
+        qubits = [int(q) for q in qubits]
+        values = np.zeros((len(qubits), 2, 2), dtype=np.complex128)
+        passes = C.c_uint64()
+        _lib.call("qsv_layer_transition", self._h, ket._h, len(qubits), _ints(qubits), _dbl(values.view(np.float64)), C.byref(passes))
+        return values, passes.value
+
+    def one_qubit_densities(self, qubits=None) -> np.ndarray:
+        """The one-qubit reduced density matrix of each of ``qubits`` (``None``: all of them) as ``[k, 2, 2]``:
+        ``rho_q[b][a] = T_q[a][b]`` of ``layer_transition`` with ``bra = ket = self``, made exactly hermitian by averaging
+        with its conjugate transpose.  The trace of each is ``norm2()`` up to rounding; nothing is divided by it."""
+        rho = np.swapaxes(self.layer_transition(self, qubits), 1, 2)
+        return 0.5 * (rho + np.conjugate(np.swapaxes(rho, 1, 2)))
+
     # ---- reversible register arithmetic -------------------------------------------------------
     def apply_register_map(self, op, target, source=None, controls=(), *, inverse: bool = False) -> "DeviceState":
         """In-place classical map on the value of the ``target`` qubits (``arithmetic.RegisterMap``: modular addition and
@@ -879,6 +921,15 @@ class DensityState(DeviceState):
 
     def pauli_rotations_adjoint(self, rotations, lam):
         raise ValueError("pauli_rotations_adjoint is not defined for a density register")
+
+    def layer_adjoint(self, matrices, lam, qubits=None):
+        raise ValueError("layer_adjoint is not defined for a density register")
+
+    def layer_transition(self, ket, qubits=None):
+        raise ValueError("layer_transition is not defined for a density register")
+
+    def one_qubit_densities(self, qubits=None):
+        raise ValueError("one_qubit_densities is not defined for a density register: use reduced_density")
 
     def energy_and_gradient(self, rotations, terms):
         raise ValueError("energy_and_gradient is not defined for a density register")

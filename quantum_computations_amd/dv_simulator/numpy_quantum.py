@@ -236,6 +236,26 @@ def reduced_density(state, qubits):
     return m @ m.conj().T
 
 
+def one_qubit_densities(state, qubits=None) -> np.ndarray:
+    """The one-qubit reduced density matrix of each of ``qubits`` (``None``: every qubit, in order) as one ``[k, 2, 2]``
+    array: ``rho_q[b][a] = sum_rest conj(state[a, rest]) state[b, rest]``, nothing divided by the norm.  A host ket is
+    contracted on the host; a ``DeviceState`` goes to ``DeviceState.one_qubit_densities`` (all of them in the passes of one
+    product layer)."""
+    from ..device import DeviceState
+    if isinstance(state, DeviceState):
+        return state.one_qubit_densities(qubits)
+    ket = np.asarray(state, dtype=np.complex128).reshape(-1)
+    n = ket.size.bit_length() - 1
+    qubits = list(range(n)) if qubits is None else [int(q) for q in qubits]
+    out = np.zeros((len(qubits), 2, 2), dtype=np.complex128)
+    for j, q in enumerate(qubits):
+        if not 0 <= q < n:
+            raise ValueError(f"qubit index out of range for a {n}-qubit register")
+        m = ket.reshape(1 << q, 2, -1)
+        out[j] = np.einsum("xby,xay->ba", m, m.conj())
+    return out
+
+
 def marginal_probabilities(state, qubits) -> np.ndarray:
     """Probabilities of the ``2^k`` outcomes of ``qubits`` with every other qubit summed over (host ket or
     ``DeviceState``)."""

@@ -47,6 +47,38 @@ def hadamard() -> np.ndarray:
     return np.array([[1.0, 1.0], [1.0, -1.0]], dtype=np.complex128) / np.sqrt(2.0)
 
 
+_PAULI = {"rx": np.array([[0.0, 1.0], [1.0, 0.0]], dtype=np.complex128),
+          "ry": np.array([[0.0, -1.0j], [1.0j, 0.0]], dtype=np.complex128),
+          "rz": np.array([[1.0, 0.0], [0.0, -1.0]], dtype=np.complex128)}
+_ROTATION = {"rx": rx, "ry": ry, "rz": rz}
+
+
+def rotation(kind: str, theta) -> np.ndarray:
+    """``rx`` / ``ry`` / ``rz`` by name, for every entry of ``theta``."""
+    if kind not in _ROTATION:
+        raise ValueError(f"kind must be one of {tuple(_ROTATION)}, not {kind!r}")
+    return _ROTATION[kind](theta)
+
+
+def generator(kind: str) -> np.ndarray:
+    """The constant ``G = (dU/dtheta) U^dagger = -i/2 P`` of ``U = exp(-i theta/2 P)`` for ``kind`` in ``rx`` / ``ry`` /
+    ``rz`` (``P = X`` / ``Y`` / ``Z``): what ``gradient`` contracts with the transition matrices of ``layer_adjoint``."""
+    if kind not in _PAULI:
+        raise ValueError(f"kind must be one of {tuple(_PAULI)}, not {kind!r}")
+    return -0.5j * _PAULI[kind]
+
+
+def gradient(T, generators) -> np.ndarray:
+    """``2 Re sum_ab G[a][b] T[a][b]`` per stage: ``dE/dtheta`` of every factor of a layer from ``T[k, 2, 2]``
+    (``DeviceState.layer_adjoint`` with ``lam = H psi``) and the factors' generators, ``(2, 2)`` for all or ``(k, 2, 2)``.
+    For ``generator(kind)`` this is ``Im <lam|P|psi>``."""
+    T = np.asarray(T, dtype=np.complex128)
+    if T.ndim != 3 or T.shape[1:] != (2, 2):
+        raise ValueError("T must have shape [k, 2, 2]")
+    G = layer_table(generators, T.shape[0], "generators")
+    return 2.0 * np.real(np.sum(G * T, axis=(1, 2)))
+
+
 def product_matrix(matrices) -> np.ndarray:
     """``matrices[0] (x) matrices[1] (x) ...``: the ``2^k x 2^k`` matrix of a layer whose first listed qubit is the most
     significant leg, as ``apply_matrix`` takes it.  For tests and small hosts."""

@@ -70,14 +70,22 @@ def run(diag: DiagonalOperator, gammas, betas, state: DeviceState | None = None,
     return state
 
 
-def energy_and_gradient(diag: DiagonalOperator, gammas, betas, state: DeviceState | None = None, mixer: str = "gates"):
+def energy_and_gradient(diag: DiagonalOperator, gammas, betas, state: DeviceState | None = None, mixer: str = "gates",
+                        walk: str = "calls"):
     """``(E, dE/dgamma, dE/dbeta)`` of ``E = <psi_p| D |psi_p>`` by one adjoint walk: the layers forward, ``E`` and
     ``lambda = D psi``, then for the last layer first ``dE/dbeta_l = 2 Im <lambda| B |psi>``, the mixer undone on both
     registers, and ``dE/dgamma_l = 2 Im <lambda| D |psi>`` from ``qsv_diag_phase_adjoint``, which undoes the cost phase
     on both in the same pass.  ``state`` (``|+>^n`` when None) holds its input again on return, up to rounding.
-    ``mixer``: as in ``mixer()``, for the walk forward and the walk back."""
+    ``mixer``: as in ``mixer()``, for the walk forward and the walk back.  ``walk="fused"`` (needs ``mixer="layer"``) takes
+    ``dE/dbeta_l`` and the undone mixer on both registers from one ``layer_adjoint``:
+    ``dE/dbeta_l = sum_q 2 Im <lambda|X_q|psi>`` from the transition matrices, ``RX(2 beta)`` having the generator ``-i X``
+    in ``beta``; ``walk="calls"`` is the transition sum and the two mixer calls."""
     gammas, betas = _angles(gammas, betas)
     kind = _mixer_kind(mixer, ("gates", "layer"))
+    if walk not in ("calls", "fused"):
+        raise ValueError(f"walk must be one of ('calls', 'fused'), not {walk!r}")
+    if walk == "fused" and kind != "layer":
+        raise ValueError('walk="fused" needs mixer="layer"')
     own = state is None
     psi = plus_state(diag.num_qubits, diag.device) if own else state
     lam = DeviceState.zeros(psi.num_qubits, psi.device)
@@ -88,9 +96,13 @@ def energy_and_gradient(diag: DiagonalOperator, gammas, betas, state: DeviceStat
         b_terms = mixer_terms(psi.num_qubits)
         d_gamma, d_beta = np.zeros_like(gammas), np.zeros_like(betas)
         for layer in range(len(gammas) - 1, -1, -1):
-            d_beta[layer] = 2.0 * lam.transition_pauli_sum(b_terms, psi).imag
-            _apply_mixer(psi, -betas[layer], kind)
-            _apply_mixer(lam, -betas[layer], kind)
+            if walk == "fused":
+                T = psi.layer_adjoint(layers.rx(2.0 * float(betas[layer])), lam)
+                d_beta[layer] = float(np.sum(layers.gradient(T, 2.0 * layers.generator("rx"))))
+            else:
+                d_beta[layer] = 2.0 * lam.transition_pauli_sum(b_terms, psi).imag
+                _apply_mixer(psi, -betas[layer], kind)
+                _apply_mixer(lam, -betas[layer], kind)
             d_gamma[layer] = 2.0 * psi.diagonal_phase_adjoint(diag, lam, -gammas[layer]).imag
     finally:
         lam.close()

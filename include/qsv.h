@@ -590,6 +590,40 @@ int qsv_ensemble_apply_matrices(qsv_state *st, int member_qubits, int k /* 1 or 
 int qsv_ensemble_apply_diag_phase(qsv_state *st, int member_qubits, qsv_diag *d, const double *gammas /* members */);
 int qsv_ensemble_expect_diag(qsv_state *st, int member_qubits, qsv_diag *d, const double *threshold /* NULL or one value */,
                              double *out /* [members][4] */);
+/* ---- per-member adjoint walks (csrc/qsv_ensemble_adjoint.hip) ----
+ * Two ensembles of one shape, psi and lambda (a and b), member by member; notation as above.
+ *  - qsv_ensemble_inner: values[m] = <a_m|b_m> (a conjugated), interleaved complex.  Read-only; a may be b, and <a_m|a_m> has an
+ *    imaginary part of exactly 0.  One read pass, one copy and one synchronisation.
+ *  - qsv_ensemble_apply_diag_mul: dst_m[i] = d[i] src_m[i], qsv_apply_diag_mul with the coefficient 1 and a diagonal of
+ *    member_qubits qubits: lambda = D psi for the cost-phase walk.  dst may be src; otherwise their memory must not meet.  One
+ *    pass on dst's stream, no synchronisation.
+ *  - qsv_ensemble_pauli_rotations_adjoint is qsv_pauli_rotations_adjoint member by member with row m of thetas: for t = T-1 .. 0,
+ *    values[m][t] = <lambda_m|P_t|psi_m>, then psi_m <- R_t(thetas[m][t])^dagger psi_m and the same for lambda_m.  Term list,
+ *    planner and *passes are those of qsv_ensemble_apply_pauli_rotations; the passes are taken last first.  Every pass is
+ *    followed by a per-member sum on the device; there is no host synchronisation between passes, and one copy and one
+ *    synchronisation at the end whatever the list length.
+ *  - qsv_ensemble_diag_phase_adjoint: values[m] = <lambda_m|D|psi_m> of the registers as they come in, then psi_m[i] *=
+ *    exp(-i gammas[m] d[i]) and the same for lambda_m, in one pass (the arithmetic of qsv_diag_phase_adjoint); d has
+ *    member_qubits qubits.
+ * After either walk psi_m and lambda_m are bit for bit what the single-register call leaves on registers of the member's size
+ * with the member's angles.  A member's values depend on member_qubits, the term list and QSV_OPT_GRID_CAP only: they are
+ * bit-identical wherever the member sits and for any number of members, and agree with the single-register values to
+ * rounding (the order of the sums differs).  Sums and partials live in psi's (a's) ensemble workspace.  After the checks both
+ * deferred queues are flushed, lambda's (b's) stream is synchronised and the launches go on psi's (a's).  n_terms = 0
+ * launches nothing.
+ * QSV_EINVAL for null pointers (passes may be NULL), a view, member_qubits outside 0 .. n_total, a qubit >= member_qubits or
+ * repeated, bad letters, offsets or lengths, any angle or gamma that is not finite, registers of different sizes or devices or
+ * (the two walks) whose memory meets, a diagonal of another size or device; QSV_ESTATE for a mode register, or a call that
+ * would change the member size while psi's (a's) ensemble log holds steps: each before any launch and with both deferred
+ * queues untouched. */
+int qsv_ensemble_inner(qsv_state *a, qsv_state *b, int member_qubits, double *values /* [members] complex */);
+int qsv_ensemble_apply_diag_mul(qsv_state *dst, qsv_state *src, int member_qubits, qsv_diag *d);
+int qsv_ensemble_pauli_rotations_adjoint(qsv_state *psi, qsv_state *lambda, int member_qubits, int n_terms,
+                                         const int *term_offsets, const int *qubits, const char *paulis,
+                                         const double *thetas /* [members][n_terms] */,
+                                         double *values /* [members][n_terms] complex */, uint64_t *passes);
+int qsv_ensemble_diag_phase_adjoint(qsv_state *psi, qsv_state *lambda, int member_qubits, qsv_diag *d,
+                                    const double *gammas /* [members] */, double *values /* [members] complex */);
 /* Reduced density matrix of the k <= 6 qubits `qubits` (all others traced out) in one read pass over the register:
  * rho[i][j] = sum_rest psi[i, rest] conj(psi[j, rest]), written row-major as 4^k complex numbers, qubits[0] the most
  * significant bit of i and j.  What a caller of the reference gets from npq.ket2dm (numpy_quantum.py:110-113)

@@ -113,6 +113,10 @@ SIGNATURES: dict[str, list] = {
     "qsv_ensemble_apply_matrices": [_state_p, C.c_int, C.c_int, _int_p, _dbl_p],
     "qsv_ensemble_apply_diag_phase": [_state_p, C.c_int, _state_p, _dbl_p],
     "qsv_ensemble_expect_diag": [_state_p, C.c_int, _state_p, _dbl_p, _dbl_p],
+    "qsv_ensemble_inner": [_state_p, _state_p, C.c_int, _dbl_p],
+    "qsv_ensemble_apply_diag_mul": [_state_p, _state_p, C.c_int, _state_p],
+    "qsv_ensemble_pauli_rotations_adjoint": [_state_p, _state_p, C.c_int, C.c_int, _int_p, _int_p, C.c_char_p, _dbl_p, _dbl_p, _u64_p],
+    "qsv_ensemble_diag_phase_adjoint": [_state_p, _state_p, C.c_int, _state_p, _dbl_p, _dbl_p],
     "qsv_ensemble_apply_layer": [_state_p, C.c_int, C.c_int, _int_p, _dbl_p, _u64_p],
     "qsv_ensemble_expect_pauli_sum": [_state_p, C.c_int, C.c_int, _int_p, _int_p, C.c_char_p, _dbl_p, _dbl_p, _dbl_p],
     "qsv_reduced_density": [_state_p, C.c_int, _int_p, C.c_void_p],

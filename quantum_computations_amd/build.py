@@ -11,7 +11,7 @@ PKG_DIR = Path(__file__).resolve().parent
 REPO_ROOT = PKG_DIR.parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = PKG_DIR / "libqsv.so"
-SOURCES = ["qsv_api.hip", "qsv_gate12.hip", "qsv_gatek.hip", "qsv_sequence.hip", "qsv_pass.hip", "qsv_state.hip", "qsv_readout.hip", "qsv_pauli.hip", "qsv_qft.hip", "qsv_layer.hip", "qsv_layer_adjoint.hip", "qsv_arith.hip", "qsv_krylov.hip", "qsv_diagonal.hip", "qsv_channel.hip", "qsv_ensemble.hip", "qsv_sweep.hip", "qsv_subsystem.hip", "qsv_qudit.hip", "qsv_gemm.hip", "qsv_decomp.hip", "qsv_rsvd.hip", "qsv_panel.hip", "qsv_skinny.hip",
+SOURCES = ["qsv_api.hip", "qsv_gate12.hip", "qsv_gatek.hip", "qsv_sequence.hip", "qsv_pass.hip", "qsv_state.hip", "qsv_readout.hip", "qsv_pauli.hip", "qsv_qft.hip", "qsv_layer.hip", "qsv_layer_adjoint.hip", "qsv_arith.hip", "qsv_krylov.hip", "qsv_diagonal.hip", "qsv_channel.hip", "qsv_ensemble.hip", "qsv_sweep.hip", "qsv_ensemble_adjoint.hip", "qsv_subsystem.hip", "qsv_qudit.hip", "qsv_gemm.hip", "qsv_decomp.hip", "qsv_rsvd.hip", "qsv_panel.hip", "qsv_skinny.hip",
            "qsv_circuit.hip", "qsv_phase_space.hip", "qsv_sampling.hip", "qsv_canonical.hip"]
 HEADERS = [CSRC / "qsv_internal.h", CSRC / "qsv_device.h", CSRC / "qsv_linalg.h", CSRC / "qsv_jacobi.h", CSRC / "qsv_split_rules.h", CSRC / "qsv_plan.h", CSRC / "qsv_layout.h",
            CSRC / "qsv_readout_layout.h", CSRC / "qsv_pauli_plan.h", CSRC / "qsv_pauli_rotation_plan.h", CSRC / "qsv_qft_plan.h", CSRC / "qsv_layer_plan.h", CSRC / "qsv_layer_item.h", CSRC / "qsv_arith_layout.h", CSRC / "qsv_krylov_layout.h", CSRC / "qsv_diagonal_layout.h", CSRC / "qsv_channel_layout.h", CSRC / "qsv_ensemble_layout.h", CSRC / "qsv_ensemble_control_layout.h", CSRC / "qsv_sweep_layout.h", CSRC / "qsv_pauli_rotate_item.h",
@@ -31,10 +31,11 @@ ARCH = "gfx950"
 # k_layer_tile's stage switch holds 16 amplitudes per thread, and without the option the compiler's remarks show 155 / 170
 # VGPRs (shared / per-member matrices) against 104 / 116 with it -- the second copy of the amplitudes.
 # qsv_layer_adjoint.hip takes it for the same reason: k_layer_adjoint_tile's stage switch holds 16 amplitudes of each of two
-# registers per thread.
+# registers per thread.  qsv_ensemble_adjoint.hip takes it because its walk kernel is
+# k_pauli_adjoint_group's item body (qsv_pauli.hip) on member-local items.
 _SKIP_UNIFORM = ["-mllvm", "-structurizecfg-skip-uniform-regions"]
 EXTRA_FLAGS = {name: _SKIP_UNIFORM for name in ("qsv_gate12.hip", "qsv_gatek.hip", "qsv_sequence.hip", "qsv_pass.hip", "qsv_state.hip",
-                                                "qsv_readout.hip", "qsv_pauli.hip", "qsv_sweep.hip", "qsv_layer.hip", "qsv_layer_adjoint.hip")}
+                                                "qsv_readout.hip", "qsv_pauli.hip", "qsv_sweep.hip", "qsv_layer.hip", "qsv_layer_adjoint.hip", "qsv_ensemble_adjoint.hip")}
 
 
 def check_extra_flags() -> None:

@@ -631,6 +631,22 @@ int qsvk_ens_sum_parts(qsv_state *st, const double *partials, uint64_t members, 
     return check_launch();
 }
 
+// What the ensemble calls of other translation units (qsv_ensemble_adjoint.hip) need of the register's workspace.
+// qsvk_ens_check_member_size: the refusal of check_member_size, before anything is flushed; allocates nothing.
+int qsvk_ens_check_member_size(qsv_state *st, int n) {
+    if (!st->ensemble_work) return QSV_OK;
+    return check_member_size(static_cast<const EnsembleWork *>(st->ensemble_work), n, st->amps >> n);
+}
+// The workspace sized for members of n qubits: *partials = its [members][P_max(n)][16] doubles, *slots = its [members][32].
+int qsvk_ens_workspace(qsv_state *st, int n, double **partials, double **slots) {
+    EnsembleWork *work = work_of(st);
+    const int rc = ensure_workspace(st, work, n, st->amps >> n);
+    if (rc) return rc;
+    *partials = work->dev + work->ws.partials;
+    *slots = work->dev + work->ws.matrix;
+    return QSV_OK;
+}
+
 extern "C" {
 
 int qsv_ensemble_broadcast(qsv_state *st, int member_qubits) {
@@ -947,25 +963,9 @@ int qsv_ensemble_expect_pauli_sum(qsv_state *st, int member_qubits, int n_terms,
     if (rc) return rc;
     // the whole list is checked and turned into masks of member bits before anything is flushed or launched
     const int n = member_qubits;
-    std::vector<qsv_pauli_plan::Term> terms(static_cast<size_t>(n_terms));
-    for (int t = 0; t < n_terms; ++t) {
-        const int first = term_offsets[t], len = term_offsets[t + 1] - first;
-        if (first < 0 || len < 0) return qsv_fail(QSV_EINVAL, "Pauli term offsets must start at or above 0 and never decrease");
-        if (len > 64) return qsv_fail(QSV_EINVAL, "bad Pauli string length");
-        if (len > 0 && (!qubits || !paulis)) return qsv_fail(QSV_EINVAL, "null pointer");
-        rc = check_member_qubits(n, len, len ? qubits + first : nullptr);
-        if (rc) return rc;
-        for (int j = first; j < first + len; ++j) {
-            const uint64_t bit = 1ull << (n - 1 - qubits[j]);
-            switch (paulis[j]) {
-                case 'I': case 'i': break;
-                case 'X': case 'x': terms[t].xmask |= bit; break;
-                case 'Z': case 'z': terms[t].zmask |= bit; break;
-                case 'Y': case 'y': terms[t].xmask |= bit; terms[t].zmask |= bit; break;
-                default: return qsv_fail(QSV_EINVAL, "Pauli letters must be I, X, Y or Z");
-            }
-        }
-    }
+    std::vector<qsv_pauli_plan::Term> terms;
+    rc = parse_member_terms(n, n_terms, term_offsets, qubits, paulis, &terms);
+    if (rc) return rc;
     const uint64_t members = st->amps >> n;
     for (uint64_t m = 0; m < members; ++m) values[m] = 0.0;
     if (n_terms == 0) return QSV_OK;

@@ -1,5 +1,5 @@
-// What the translation units of the ensemble kernels share (qsv_ensemble.hip, qsv_sweep.hip): who works on what in a unit
-// of qsv_ensemble_layout.h, how a member's sums are formed, and what every ensemble call refuses.  Everything here is
+// What the translation units of the ensemble kernels share (qsv_ensemble.hip, qsv_sweep.hip, qsv_ensemble_adjoint.hip): who
+// works on what in a unit of qsv_ensemble_layout.h, how a member's sums are formed, and what every ensemble call refuses.  Everything here is
 // static; no __global__ function lives here.
 #pragma once
 
@@ -25,6 +25,13 @@ static __device__ __forceinline__ Mine mine(const qsv_ensemble_layout::EnsArgs &
     t.items = 1ull << e.item_bits;
     t.live = t.member < e.members;
     return t;
+}
+
+// a 64-bit value that is the same in every lane of the wave, said so that the compiler can keep it in scalar registers
+static __device__ __forceinline__ uint64_t wave_uniform(uint64_t v) {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v));
+    const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
+    return (static_cast<uint64_t>(hi) << 32) | lo;
 }
 
 // The sums of R doubles per thread, member by member: partials[(member * P + part) * R + e].  A member of fewer than 64 items
@@ -87,6 +94,30 @@ static int check_member_qubits(int member_qubits, int count, const int *qubits) 
             return qsv_fail(QSV_EINVAL, "qubit index " + std::to_string(qubits[i]) + " out of range for members of " + std::to_string(member_qubits) + " qubits");
         for (int j = 0; j < i; ++j)
             if (qubits[i] == qubits[j]) return qsv_fail(QSV_EINVAL, "Indices must be distinct.");
+    }
+    return QSV_OK;
+}
+
+// A Pauli term list on member qubits, checked whole and turned into masks of member bits (qubit q is bit n - 1 - q).
+static int parse_member_terms(int n, int n_terms, const int *term_offsets, const int *qubits, const char *paulis, std::vector<qsv_pauli_plan::Term> *terms) {
+    terms->assign(static_cast<size_t>(n_terms), qsv_pauli_plan::Term{});
+    for (int t = 0; t < n_terms; ++t) {
+        const int first = term_offsets[t], len = term_offsets[t + 1] - first;
+        if (first < 0 || len < 0) return qsv_fail(QSV_EINVAL, "Pauli term offsets must start at or above 0 and never decrease");
+        if (len > 64) return qsv_fail(QSV_EINVAL, "bad Pauli string length");
+        if (len > 0 && (!qubits || !paulis)) return qsv_fail(QSV_EINVAL, "null pointer");
+        const int rc = check_member_qubits(n, len, len ? qubits + first : nullptr);
+        if (rc) return rc;
+        for (int j = first; j < first + len; ++j) {
+            const uint64_t bit = 1ull << (n - 1 - qubits[j]);
+            switch (paulis[j]) {
+                case 'I': case 'i': break;
+                case 'X': case 'x': (*terms)[t].xmask |= bit; break;
+                case 'Z': case 'z': (*terms)[t].zmask |= bit; break;
+                case 'Y': case 'y': (*terms)[t].xmask |= bit; (*terms)[t].zmask |= bit; break;
+                default: return qsv_fail(QSV_EINVAL, "Pauli letters must be I, X, Y or Z");
+            }
+        }
     }
     return QSV_OK;
 }

@@ -199,6 +199,11 @@ int qsvk_arith(qsv_state *st, const qsv_arith *op, const int *tbits, const int *
 int qsvk_arith_describe(const qsv_arith *op, int *device, int *m, int *mx);
 // qsv_ensemble.hip: out[m * R + r] = the sum over member m's parts of partials[(m * parts + p) * R + r], in index order, on st's stream
 int qsvk_ens_sum_parts(qsv_state *st, const double *partials, uint64_t members, int parts, int R, double *out);
+// qsv_ensemble.hip, for the ensemble calls of qsv_ensemble_adjoint.hip: QSV_ESTATE where members of n qubits would change the
+// member size while the ensemble log holds steps (no launch, no allocation); the workspace sized for members of n qubits,
+// *partials = its [members][P_max(n)][16] doubles and *slots = its [members][32]
+int qsvk_ens_check_member_size(qsv_state *st, int n);
+int qsvk_ens_workspace(qsv_state *st, int n, double **partials, double **slots);
 int qsvk_reduced_density(qsv_state *st, int k, const int *bits, double *rho_out);
 int qsvk_expect_density(qsv_state *ket, qsv_state *rho, double *re, double *im);
 int qsvk_sample(qsv_state *st, int shots, const double *u, uint64_t *out);

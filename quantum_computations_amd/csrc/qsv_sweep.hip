@@ -25,13 +25,6 @@ using qsv_readout_layout::PauliRotateArgs;
 
 namespace {
 
-// a 64-bit value that is the same in every lane of the wave, said so that the compiler can keep it in scalar registers
-__device__ __forceinline__ uint64_t wave_uniform(uint64_t v) {
-    const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v));
-    const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
-    return (static_cast<uint64_t>(hi) << 32) | lo;
-}
-
 // k_pauli_rotate_group's item loop on the items of one member: work item w of member m owns amplitude w of the member (DIAG)
 // or the pair {i, i ^ xmask}, i = insert_zero(w, pivot), inside a + (m << n); pivot <= n - 1, so the partner stays in the
 // member.  The member's cos / sin of the pass's s.count terms replace g.cs / g.sn (never read here: the slots beyond the
@@ -132,25 +125,9 @@ int qsv_ensemble_apply_pauli_rotations(qsv_state *st, int member_qubits, int n_t
     if (rc) return rc;
     // the whole list is checked and turned into masks of member bits before the queue is flushed or anything is launched
     const int n = member_qubits;
-    std::vector<qsv_pauli_plan::Term> terms(static_cast<size_t>(n_terms));
-    for (int t = 0; t < n_terms; ++t) {
-        const int first = term_offsets[t], len = term_offsets[t + 1] - first;
-        if (first < 0 || len < 0) return qsv_fail(QSV_EINVAL, "Pauli term offsets must start at or above 0 and never decrease");
-        if (len > 64) return qsv_fail(QSV_EINVAL, "bad Pauli string length");
-        if (len > 0 && (!qubits || !paulis)) return qsv_fail(QSV_EINVAL, "null pointer");
-        rc = check_member_qubits(n, len, len ? qubits + first : nullptr);
-        if (rc) return rc;
-        for (int j = first; j < first + len; ++j) {
-            const uint64_t bit = 1ull << (n - 1 - qubits[j]);
-            switch (paulis[j]) {
-                case 'I': case 'i': break;
-                case 'X': case 'x': terms[t].xmask |= bit; break;
-                case 'Z': case 'z': terms[t].zmask |= bit; break;
-                case 'Y': case 'y': terms[t].xmask |= bit; terms[t].zmask |= bit; break;
-                default: return qsv_fail(QSV_EINVAL, "Pauli letters must be I, X, Y or Z");
-            }
-        }
-    }
+    std::vector<qsv_pauli_plan::Term> terms;
+    rc = parse_member_terms(n, n_terms, term_offsets, qubits, paulis, &terms);
+    if (rc) return rc;
     const uint64_t members = st->amps >> n;
     if (n_terms > 0 && !all_finite(thetas, static_cast<size_t>(members) * n_terms)) return qsv_fail(QSV_EINVAL, "every angle must be finite");
     if (passes) *passes = 0;

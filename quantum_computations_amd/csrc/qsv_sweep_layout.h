@@ -1,5 +1,6 @@
-// Host-side launch shapes of the per-member parameter kernels (qsv_sweep.hip): plain C++, no HIP, so that the host tests can
-// compile it alone (tests/test_sweep_layout_host.py).  DESIGN.md section 27.
+// Host-side launch shapes of the per-member parameter kernels (qsv_sweep.hip) and of the per-member adjoint walks
+// (qsv_ensemble_adjoint.hip, at the end): plain C++, no HIP, so that the host tests can compile it alone
+// (tests/test_sweep_layout_host.py, tests/test_ensemble_adjoint_layout_host.py).  DESIGN.md sections 27 and 30.
 //
 // The register is an ensemble (qsv_ensemble_layout.h): 2^b members of n qubits, member m at [m 2^n, (m + 1) 2^n).  A
 // per-member rotation pass is a pass of qsv_pauli_rotation_plan.h planned on MEMBER-LOCAL masks and walked member by member:
@@ -89,5 +90,57 @@ inline EnsArgs expect_args(int n, uint64_t members, int grid_cap) {
 // doubles of the scratch buffer: [members][4] results first, then [members][parts][4] partials
 inline size_t expect_values(uint64_t members) { return static_cast<size_t>(members) * SWEEP_EXPECT_SLOTS; }
 inline size_t expect_doubles(const EnsArgs &e) { return expect_values(e.members) + (static_cast<size_t>(e.members) << e.part_bits) * SWEEP_EXPECT_SLOTS; }
+
+// ---- the per-member adjoint walk (qsv_ensemble_adjoint.hip) ---------------------------------------------
+// k_ens_pauli_adjoint_group walks the items of a rotation pass (2^n per member in a diagonal pass, 2^(n - 1) otherwise) on
+// the units of a READ pass: a thread takes 32 items where the member has them, so that the workgroup's sum of 2 T doubles
+// (shuffles, LDS, two barriers) is paid once per 32 items and a member's parts never exceed the P_max(n) of the ensemble
+// workspace, whose [members][P_max][16] partials hold the 2 x 8 doubles of the widest pass.  The cut of an update pass (one
+// item per thread, items / 256 parts) would need 2^(n - 8) x 16 doubles per member and does not fit that workspace.  The cut
+// depends on the items per member and the grid cap alone.
+inline EnsArgs adjoint_args(int n, uint64_t members, bool diag, int grid_cap) {
+    const int item_bits = rotate_item_bits(n, diag);
+    return qsv_ensemble_layout::ens_args(n, members, item_bits, qsv_ensemble_layout::part_bits(item_bits, grid_cap));
+}
+// Threads of a member >= members (the last shared unit of a small ensemble) stay in the unit for the sums and contribute
+// zeros; the row they fetch is the last member's, so that no fetch leaves the table.
+inline uint64_t adjoint_fetch_member(const EnsArgs &e, uint64_t member) { return member < e.members ? member : e.members - 1; }
+// The walk takes the terms of a pass in reverse order: slot t < count of the kernel is term count - 1 - t of the pass.  The
+// slots beyond the count are fetched in place (inside the row or the padding) and discarded.
+inline int adjoint_slot_term(const SweepArgs &s, int t) { return t < s.count ? s.count - 1 - t : t; }
+inline size_t adjoint_table_offset(const SweepArgs &s, uint64_t member, int t, int part) {
+    return table_offset(s, member, adjoint_slot_term(s, t), part);
+}
+// partials[((member << part_bits) + part) * 2 T + 2 t + {re, im}] (member_store_sums<2 T>), T = the pass's width
+inline size_t adjoint_partial_offset(const EnsArgs &e, uint64_t member, uint64_t part, int width, int t, int c) {
+    return ((static_cast<size_t>(member) << e.part_bits) + part) * 2 * width + 2 * static_cast<size_t>(t) + c;
+}
+inline size_t adjoint_partial_doubles(const EnsArgs &e, int width) { return (static_cast<size_t>(e.members) << e.part_bits) * 2 * width; }
+inline bool adjoint_fits_workspace(const EnsArgs &e, int width) {
+    const qsv_ensemble_layout::EnsWorkspace w = qsv_ensemble_layout::ens_workspace(e.n, e.members);
+    return 2 * width <= qsv_ensemble_layout::ENS_ENTRIES && adjoint_partial_doubles(e, width) <= w.matrix - w.partials;
+}
+// What k_ens_adjoint_sum needs of a pass.  Passed by value: field order and sizes are ABI.
+struct AdjointSumArgs {
+    int32_t index[SWEEP_MAX_SLOTS];   // the caller's term behind slot t (-1: padding)
+    int32_t width;                    // T of the pass
+    int32_t parts;
+    int32_t n_terms;
+    int32_t pad;
+};
+static_assert(sizeof(AdjointSumArgs) == 48, "kernel argument layout");
+// the scratch buffer of a walk, in doubles: the angle table, then the results [members][n_terms][2]
+inline size_t adjoint_results_offset(uint64_t members, int n_terms) { return table_doubles(members, n_terms); }
+inline size_t adjoint_results_doubles(uint64_t members, int n_terms) { return static_cast<size_t>(members) * static_cast<size_t>(n_terms) * 2; }
+inline size_t adjoint_scratch_doubles(uint64_t members, int n_terms) {
+    return adjoint_results_offset(members, n_terms) + adjoint_results_doubles(members, n_terms);
+}
+
+// ---- k_ens_inner, k_ens_diag_phase_adjoint: the units of a read pass over 2^n items per member, two sums per member ------------
+constexpr int SWEEP_PAIR_SLOTS = 2;       // re, im
+inline EnsArgs pair_args(int n, uint64_t members, int grid_cap) { return expect_args(n, members, grid_cap); }
+inline size_t pair_partial_doubles(const EnsArgs &e) { return (static_cast<size_t>(e.members) << e.part_bits) * SWEEP_PAIR_SLOTS; }
+// the sums [members][2] go to the first doubles of the workspace's [members][32] slots
+inline size_t pair_values(uint64_t members) { return static_cast<size_t>(members) * SWEEP_PAIR_SLOTS; }
 
 }  // namespace qsv_sweep_layout

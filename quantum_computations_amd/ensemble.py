@@ -313,6 +313,90 @@ class TrajectoryEnsemble:
                   per_term.ctypes.data_as(C.POINTER(C.c_double)) if return_terms else None)
         return (values, per_term) if return_terms else values
 
+    # ---- two ensembles, member by member: operators, inner products and adjoint walks ----------------
+    def _partner(self, other, name: str) -> "TrajectoryEnsemble":
+        if not isinstance(other, TrajectoryEnsemble):
+            raise ValueError(f"{name} must be an ensemble")
+        if other.member_qubits != self.member_qubits or other.members != self.members:
+            raise ValueError(f"{name} must have this ensemble's shape: {self.members} members of {self.member_qubits} qubits")
+        return other
+
+    def inner(self, other: "TrajectoryEnsemble") -> np.ndarray:
+        """``values[m] = <self_m|other_m>``, complex; ``other`` may be ``self`` (then the imaginary parts are exactly 0)."""
+        self._partner(other, "other")
+        values = np.zeros(self.members, dtype=np.complex128)
+        _lib.call("qsv_ensemble_inner", self.state._h, other.state._h, self.member_qubits,
+                  values.view(np.float64).ctypes.data_as(C.POINTER(C.c_double)))
+        return values
+
+    def apply_pauli_sum(self, terms, out: "TrajectoryEnsemble | None" = None, accumulate: bool = False) -> "TrajectoryEnsemble":
+        """``out_m = H self_m`` (``+=`` with ``accumulate``) for ``H = sum_t c_t P_t`` on member qubits: ``DeviceState.apply_pauli_sum``
+        on the whole register with the qubits shifted past the member index.  ``out`` is an ensemble of this shape, allocated
+        when None; it is returned.  A member's amplitudes are bit for bit those of a register of its own."""
+        terms = [(complex(c), str(paulis), [int(q) for q in qs]) for c, paulis, qs in terms]
+        _check_terms(terms, self.member_qubits)
+        own = out is None
+        if own:
+            out = TrajectoryEnsemble(DeviceState.zeros(self.member_qubits + self.member_bits, self.state.device), self.member_qubits)
+        try:
+            self._partner(out, "out")
+            self.state.apply_pauli_sum([(c, paulis, [q + self.member_bits for q in qs]) for c, paulis, qs in terms], out=out.state,
+                                       accumulate=accumulate)
+        except BaseException:
+            if own:
+                out.close()
+            raise
+        return out
+
+    def apply_diagonal_operator(self, diag, out: "TrajectoryEnsemble | None" = None) -> "TrajectoryEnsemble":
+        """``out_m = D self_m`` for a ``DiagonalOperator`` of ``member_qubits`` qubits.  ``out`` is an ensemble of this shape,
+        allocated when None; it may be ``self``.  Returns ``out``."""
+        _diagonal_operand(diag)
+        own = out is None
+        if own:
+            out = TrajectoryEnsemble(DeviceState.zeros(self.member_qubits + self.member_bits, self.state.device), self.member_qubits)
+        try:
+            self._partner(out, "out")
+            _lib.call("qsv_ensemble_apply_diag_mul", out.state._h, self.state._h, self.member_qubits, diag._h)
+        except BaseException:
+            if own:
+                out.close()
+            raise
+        return out
+
+    def pauli_rotations_adjoint(self, rotations, lam: "TrajectoryEnsemble", thetas=None) -> np.ndarray:
+        """``DeviceState.pauli_rotations_adjoint`` member by member: for the last rotation first, ``values[m, k] =
+        <lam_m|P_k|self_m>``, then both members are rotated back by ``R_k(thetas[m, k])``.  ``thetas[members, R]`` as in
+        ``apply_pauli_rotations`` (the list's own angles for every member when None).  Both ensembles are consumed.  Costs
+        the passes of the forward list on one member (``last_passes``), whatever the number of members."""
+        self._partner(lam, "lam")
+        count, offsets, qubits, letters, cbuf = _flat_terms(rotations)
+        if thetas is None:
+            table = np.ascontiguousarray(np.broadcast_to(cbuf.view(np.complex128).real, (self.members, count)), dtype=np.float64)
+        else:
+            table = np.ascontiguousarray(thetas, dtype=np.float64)
+            if table.shape != (self.members, count):
+                raise ValueError(f"thetas must have shape [members, rotations] = [{self.members}, {count}]")
+        values = np.zeros((self.members, count), dtype=np.complex128)
+        passes = C.c_uint64()
+        _lib.call("qsv_ensemble_pauli_rotations_adjoint", self.state._h, lam.state._h, self.member_qubits, count, offsets, qubits, letters,
+                  table.ctypes.data_as(C.POINTER(C.c_double)), values.view(np.float64).ctypes.data_as(C.POINTER(C.c_double)), C.byref(passes))
+        self.last_passes = int(passes.value)
+        return values
+
+    def diagonal_phase_adjoint(self, diag, lam: "TrajectoryEnsemble", gammas) -> np.ndarray:
+        """``values[m] = <lam_m| D |self_m>``, then ``exp(-i gammas[m] D)`` on ``self_m`` and on ``lam_m``, in one pass: the
+        step of an adjoint walk over a per-member cost layer.  ``D`` has ``member_qubits`` qubits."""
+        _diagonal_operand(diag)
+        self._partner(lam, "lam")
+        gbuf = np.ascontiguousarray(gammas, dtype=np.float64)
+        if gbuf.shape != (self.members,):
+            raise ValueError("one gamma per member")
+        values = np.zeros(self.members, dtype=np.complex128)
+        _lib.call("qsv_ensemble_diag_phase_adjoint", self.state._h, lam.state._h, self.member_qubits, diag._h,
+                  gbuf.ctypes.data_as(C.POINTER(C.c_double)), values.view(np.float64).ctypes.data_as(C.POINTER(C.c_double)))
+        return values
+
     def member(self, m: int) -> np.ndarray:
         """Member ``m`` as a NumPy ket."""
         m = int(m)

@@ -156,6 +156,55 @@ def energies(diag: DiagonalOperator, gammas, betas, batch: int = 256, threshold:
     return energy if threshold is None else (energy, below)
 
 
+def energies_and_gradients(diag: DiagonalOperator, gammas, betas, batch: int = 256):
+    """``(E[M], dE/dgamma[M, p], dE/dbeta[M, p])`` at ``M`` parameter points, every point a member of an ``Ensemble`` (DESIGN.md
+    section 30): ``energy_and_gradient`` member by member.  Forward as ``energies(mixer="rotations")``; ``E`` from
+    ``expect_diagonal`` and ``lambda_m = D psi_m``; then per layer backwards ``dE/dbeta_l[m] = 2 sum_q Im <lambda_m|X_q|psi_m>``
+    from one rotation walk over the ``n`` ``X`` rotations of angle ``2 beta_l[m]`` and ``dE/dgamma_l[m] = 2 Im <lambda_m|D|psi_m>``
+    from one ``diagonal_phase_adjoint``, which undoes the cost phase on both in the same pass.  Surplus members of the last
+    chunk take angles of zero and are dropped."""
+    from . import sweep
+    from .ensemble import Ensemble
+
+    gammas = np.atleast_2d(np.asarray(gammas, dtype=np.float64))
+    betas = np.atleast_2d(np.asarray(betas, dtype=np.float64))
+    if gammas.ndim != 2 or gammas.shape != betas.shape:
+        raise ValueError("gammas and betas must both have shape [points, layers]")
+    points, n_layers = gammas.shape
+    n = diag.num_qubits
+    plus = np.full(1 << n, 2.0 ** (-0.5 * n), dtype=np.complex128)
+    x_rotations = [(0.0, "X", [q]) for q in range(n)]
+    energy, d_gamma, d_beta = np.zeros(points), np.zeros((points, n_layers)), np.zeros((points, n_layers))
+    ens = lam = None
+    try:
+        for first, count, members in sweep.chunks(points, batch):
+            if ens is None or ens.members != members:      # both ensembles of a chunk before anything is touched
+                for old in (ens, lam):
+                    if old is not None:
+                        old.close()
+                ens = lam = None
+                ens = Ensemble.from_ket(plus, members, diag.device)
+                lam = Ensemble(DeviceState.zeros(n + members.bit_length() - 1, diag.device), n)
+            else:
+                ens.reset(plus)
+            g, b = np.zeros((members, n_layers)), np.zeros((members, n_layers))
+            g[:count], b[:count] = gammas[first:first + count], betas[first:first + count]
+            for layer in range(n_layers):
+                ens.apply_diagonal_phase(diag, g[:, layer])
+                ens.apply_pauli_rotations(x_rotations, np.repeat(2.0 * b[:, layer, None], n, axis=1))
+            energy[first:first + count] = ens.expect_diagonal(diag).mean[:count]
+            ens.apply_diagonal_operator(diag, out=lam)
+            for layer in range(n_layers - 1, -1, -1):
+                values = ens.pauli_rotations_adjoint(x_rotations, lam, np.repeat(2.0 * b[:, layer, None], n, axis=1))
+                d_beta[first:first + count, layer] = 2.0 * values.imag.sum(axis=1)[:count]
+                d_gamma[first:first + count, layer] = 2.0 * ens.diagonal_phase_adjoint(diag, lam, -g[:, layer]).imag[:count]
+    finally:
+        for old in (ens, lam):
+            if old is not None:
+                old.close()
+    return energy, d_gamma, d_beta
+
+
 def landscape(diag: DiagonalOperator, gamma_grid, beta_grid, batch: int = 256, mixer: str = "rotations") -> np.ndarray:
     """The ``p = 1`` surface ``E[G, B]`` over ``gamma_grid x beta_grid`` through ``energies``."""
     gamma_grid = np.asarray(gamma_grid, dtype=np.float64).reshape(-1)

@@ -71,6 +71,50 @@ def energies(rotations, thetas, terms, ket=None, batch: int = 256, device: int =
     return out
 
 
+def energies_and_gradients(rotations, thetas, terms, ket=None, batch: int = 256, device: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """``(E[M], G[M, R])`` with ``E[m]`` as in ``energies`` and ``G[m, r] = dE[m] / dtheta[m, r]`` by the adjoint method, every
+    point a member: per chunk the rotations forward, ``lambda_m = H psi_m``, ``E_m = Re <psi_m|lambda_m>``
+    and one backward walk whose values give ``G = Im <lambda_m|P_r|psi_m>`` -- about three forward walks per chunk, where
+    ``parameter_shift`` spends ``2 R + 1`` members on one point.  ``H`` must be hermitian (real coefficients).  Surplus
+    members of the last chunk take rows of zeros and are dropped."""
+    from .device import DeviceState, _check_terms, _real_terms
+
+    rotations = [(0.0, str(paulis), [int(q) for q in qs]) for _, paulis, qs in rotations]
+    terms = _real_terms(terms, "the gradient")
+    thetas = np.asarray(thetas, dtype=np.float64)
+    if thetas.ndim != 2 or thetas.shape[1] != len(rotations):
+        raise ValueError("thetas must have shape [points, rotations]")
+    ket = _default_ket(rotations, terms, ket)
+    n = ket.shape[0].bit_length() - 1
+    _check_terms(terms, n)
+    _check_terms(rotations, n)
+    energy = np.zeros(thetas.shape[0], dtype=np.float64)
+    gradient = np.zeros(thetas.shape, dtype=np.float64)
+    ens = lam = None
+    try:
+        for first, count, members in chunks(thetas.shape[0], batch):
+            if ens is None or ens.members != members:      # both ensembles of a chunk before anything is touched
+                for old in (ens, lam):
+                    if old is not None:
+                        old.close()
+                ens = lam = None
+                ens = Ensemble.from_ket(ket, members, device)
+                lam = Ensemble(DeviceState.zeros(n + members.bit_length() - 1, device), n)
+            else:
+                ens.reset(ket)
+            rows = np.zeros((members, len(rotations)), dtype=np.float64)
+            rows[:count] = thetas[first:first + count]
+            ens.apply_pauli_rotations(rotations, rows)
+            ens.apply_pauli_sum(terms, out=lam)
+            energy[first:first + count] = ens.inner(lam).real[:count]
+            gradient[first:first + count] = ens.pauli_rotations_adjoint(rotations, lam, rows).imag[:count]
+    finally:
+        for old in (ens, lam):
+            if old is not None:
+                old.close()
+    return energy, gradient
+
+
 def parameter_shift(rotations, theta, terms, ket=None, batch: int = 256, device: int = 0) -> tuple[float, np.ndarray]:
     """``(E(theta), dE/dtheta)`` by the parameter-shift rule, exact for Pauli rotations ``exp(-i theta_r / 2 P_r)``:
     ``dE/dtheta_r = (E(theta + pi/2 e_r) - E(theta - pi/2 e_r)) / 2``.  The ``2 R + 1`` circuits run as one sweep."""
